@@ -36,7 +36,18 @@ its own tree of the same 10M triangles (compared with the GPU tree field by fiel
 the whole 3840x2160 frame on it (OpenMP over rows), which is compared with the GPU frame of
 the reported mode pixel for pixel ("parity").
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c3]
+A plain run (no --full) does only what the headline needs: the scene, one BVH build, one untimed
+frame per stream in flight (set-up: it allocates the stream's trace buffers), --warmup steps and --steps timed steps of the reported mode (the certified walks; --traversal reference: the
+reference order), and the result line (metric, value, unit, ms_per_step, ...).  Everything else
+described above -- the other traversal modes and the frame comparisons between them, the three
+interleaved rounds, the one-frame latency, the visit counts and rooflines, the timed builds, the
+rebuilt / orbiting frames, C4 / C3 / C2, the CPU baseline and the oracle parity -- runs under --full.
+
+--dump-outputs DIR writes the frame the timed path assembled in its last timed step (rank 0) as
+DIR/frame.npy (float32): the whole (H, W, 4) frame when it fits DUMP_BUDGET, else the pixels of a fixed,
+seeded sample (the same pixels in every run), shape (n, 4).  The inputs are the same in every run.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c3] [--full] [--dump-outputs DIR]
        (N > 1 under `torch.distributed.run --nproc-per-node N`).
 """
 import argparse
@@ -178,6 +189,22 @@ def cpu_model() -> str:
 
 
 NODE_FIELDS = ("parent", "child_l", "child_r", "code", "index", "bb_min", "bb_max")
+DUMP_BUDGET = 48 << 20           # bytes --dump-outputs may write (a C5 frame is 133 MB: sampled)
+DUMP_SEED = 0x5EEDD0             # the sample's seed: the same pixels in every run
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the (H, W, 4) f32 frame of the last timed step as path/frame.npy, whole if it
+    fits DUMP_BUDGET, else the pixels (rows of 4 floats) of a fixed, seeded sample in ascending order."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes > DUMP_BUDGET:
+        px = a.reshape(-1, a.shape[-1])
+        n = DUMP_BUDGET // (4 * a.shape[-1])
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(px), size=n, replace=False))
+        a = np.ascontiguousarray(px[idx])
+    np.save(os.path.join(path, "frame.npy"), a)
+    log(f"wrote {a.shape} float32 to {os.path.join(path, 'frame.npy')}")
 
 
 def affinity_cpus():
@@ -274,9 +301,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c5", choices=["c5", "c3"])
-    ap.add_argument("--build-iters", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C4 build / C3 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (every traversal mode in three "
+                         "rounds, frame comparisons, one-frame latency, rooflines, timed builds, rebuilt and "
+                         "orbiting frames, C4 / C3 / C2, the CPU baseline and the oracle parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; a fixed, seeded "
+                         "sample of its pixels when the frame is larger than 48 MiB)")
+    ap.add_argument("--build-iters", type=int, default=10, help="timed builds (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the C4 build / C3 side measurements")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the bench); gloo only to rehearse N ranks on one GPU")
     ap.add_argument("--inflight", type=int, default=4, choices=[1, 2, 3, 4],
@@ -336,19 +371,20 @@ def main():
     ctx.set_camera(wvp, wv)
     log(f"scene {scene.num_tris} tris ready in {time.perf_counter() - t_setup:.1f}s (rank {rank}/{world})")
 
-    # ---- BVH build (replicated on every rank), hipEvent-timed
+    # ---- BVH build (replicated on every rank); --full: hipEvent-timed
     ctx.build()
-    ctx.build()
-    ctx.reset_stats()
-    for _ in range(args.build_iters):
-        ctx.build(sync=False)
-    ctx.synchronize()
-    bst = ctx.stats()
-    build = {"workload": f"{scene.num_tris} tris (bench scene)", "ms": bst["ms_build"],
-             "mtris_s": scene.num_tris / (bst["ms_build"] * 1e-3) / 1e6,
-             "achieved_gbs": round(S_BUILD_PER_TRI * scene.num_tris / (bst["ms_build"] * 1e-3) / 1e9, 1),
-             "stages_ms": dict(zip(["bounds", "morton", "sort", "karras", "refit"],
-                                   [round(x, 4) for x in bst["ms_stage"][:5]]))}
+    if args.full:
+        ctx.build()
+        ctx.reset_stats()
+        for _ in range(args.build_iters):
+            ctx.build(sync=False)
+        ctx.synchronize()
+        bst = ctx.stats()
+        build = {"workload": f"{scene.num_tris} tris (bench scene)", "ms": bst["ms_build"],
+                 "mtris_s": scene.num_tris / (bst["ms_build"] * 1e-3) / 1e6,
+                 "achieved_gbs": round(S_BUILD_PER_TRI * scene.num_tris / (bst["ms_build"] * 1e-3) / 1e9, 1),
+                 "stages_ms": dict(zip(["bounds", "morton", "sort", "karras", "refit"],
+                                       [round(x, 4) for x in bst["ms_stage"][:5]]))}
 
     # ---- frames in flight: frame i is traced on streams[i % inflight] (stream 0 is the
     # context's); the context keeps a trace-buffer set per stream, all over the one BVH
@@ -385,13 +421,17 @@ def main():
                 g.assemble(*pending)
         return g.band_buffer(max(nsteps - 1, 0))
 
-    def timed(flags, inflight=args.inflight):
-        """Warm up, then time exactly args.steps steps between barrier + synchronize."""
+    def timed(flags, inflight=args.inflight, prime=False):
+        """Warm up, then time exactly args.steps steps between barrier + synchronize.  prime: first one untimed
+        frame on every stream in flight, so that each stream's trace-buffer set exists before the warm-up
+        (a plain run's set-up: with fewer warm-up steps than streams the timed steps would allocate them)."""
         # the per-stage HIP events only one frame at a time (the kernels' durations below); in the frames-in-flight
         # loops they are host-clock timed and the events' barriers would only add gaps to the stream they land on
         timing = rt.FLAG_TIMING if inflight == 1 or args.timing_in_flight else 0
         for c in ctxs:
             c.set_flags(timing | flags)
+        if prime:
+            run(inflight, inflight)
         run(args.warmup, inflight)
         torch.cuda.synchronize()
         st = ctx.stats()
@@ -415,6 +455,11 @@ def main():
             dist.all_gather(allown, own)
             rank_ms = [round(float(x.item()), 4) for x in allown]
         ms = float(el.item()) / args.steps * 1e3
+        if args.warmup == 0:   # no warm-up frame was counted: the rays of a timed frame (every frame is the same)
+            st = ctx.stats()
+            tot = torch.tensor([st["primary_rays"] + st["bounce_rays"]], dtype=torch.float64, device=dev)
+            if world > 1:
+                dist.all_reduce(tot)
         rays = float(tot[0].item())
         # the output: the frame assembled on rank 0 (one rank: its band buffer is the frame)
         frame = g.frames[(args.steps - 1) % g.nbuf].clone() if rank == 0 else None
@@ -432,6 +477,41 @@ def main():
              "nearest-first-wide": FAST | rt.FLAG_NEAREST_FIRST | rt.FLAG_WIDE_BVH,
              "nearest-first-wide-binned": FAST | rt.FLAG_NEAREST_FIRST | rt.FLAG_WIDE_BVH | rt.FLAG_BINNED_PRIMARY,
              "certified": rt.FLAG_CERTIFIED}
+
+    def finish(result):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, use["frame"].cpu().numpy())
+        for c in ctxs:
+            c.close()
+        if world > 1:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+
+    def headline(use_name, use):
+        """The result line's fields of the headline itself (a plain run's whole line)."""
+        return {
+            "metric": "Mrays/s primary+1-bounce (BASELINE.json's metric, on its config C5: 3840x2160, the 1/2/4/8-GPU "
+                      "config; the metric's @1080p config C3 is the line c3_1080p); BVH build Mtris/s under build",
+            "value": round(use["value"], 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(use["ms_step"], 4), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic (splitmix64 generator, SURVEY §8(d))" if "obj" not in wl else "Obj/Test.obj fixture",
+            "config": {"workload": wl["name"], "width": W, "height": H, "bounces": bounces,
+                       "triangles": scene.num_tris, "rays_per_step": int(use["rays"]),
+                       "parallelism": f"image bands x{world} + RCCL gather" if world > 1 else "single GPU",
+                       "band_deal_root_share": share}}
+
+    if not args.full:
+        # the plain run: the reported mode alone, --warmup steps, then --steps timed steps
+        use_name = "certified" if args.traversal != "reference" else "reference-order"
+        use = timed(modes[use_name], prime=True)
+        result = headline(use_name, use)
+        result["traversal"] = {"mode": use_name, "inflight": args.inflight, "rank_ms_per_step": use["rank_ms"]}
+        result["full"] = False
+        finish(result)
+        return
+
     # three interleaved rounds over the modes, each mode's median run kept (one slow moment on the box --
     # seen as a 15% swing of one mode in one round -- moves no number)
     runs = {m: [] for m in modes}
@@ -827,17 +907,8 @@ def main():
             del gpu_frame
         reb = extras.get("c5_frame_rebuild") or extras.get("frame_rebuild") or {}
         orb = extras.get("c5_orbit") or extras.get("orbit") or {}
-        result = {
-            "metric": "Mrays/s primary+1-bounce (BASELINE.json's metric, on its config C5: 3840x2160, the 1/2/4/8-GPU "
-                      "config; the metric's @1080p config C3 is the line c3_1080p); BVH build Mtris/s under build",
-            "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (splitmix64 generator, SURVEY §8(d))" if "obj" not in wl else "Obj/Test.obj fixture",
-            "config": {"workload": wl["name"], "width": W, "height": H, "bounces": bounces,
-                       "triangles": scene.num_tris, "rays_per_step": int(rays_per_step),
-                       "parallelism": f"image bands x{world} + RCCL gather" if world > 1 else "single GPU",
-                       "band_deal_root_share": share},
+        result = headline(use_name, use)
+        result.update({
             "value_semantics": "frames in flight (--inflight per rank) traced over one BVH built before the timed "
                                "loop (static scene and camera: the camera-dependent build work -- the clip-space "
                                "transform, the leaf records and pixel footprints -- is part of the build, reported "
@@ -865,14 +936,10 @@ def main():
             "traversal": traversal,
             "build": build,
             "cpu_baseline": cpu,
-        }
+            "full": True,
+        })
         result.update(extras)
-    for c in ctxs:
-        c.close()
-    if world > 1:
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
+    finish(result)
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 # PMC passes (separate rocprofv3 runs, --kernel-trace only besides --pmc).
 # MODES: space-separated PROF_MODE values; SETS: ';'-separated counter sets.
 set -o pipefail
-R=$GRAFT_REPO_ROOT
-OUT=$R/gpurun_out/${PMC_OUT:-pmc}
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$R/bench_out/${PMC_OUT:-pmc}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 DEFAULT_SETS="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM;SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM;TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum;FETCH_SIZE;WRITE_SIZE;TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum;TA_BUSY_avr TA_FLAT_READ_WAVEFRONTS_sum"

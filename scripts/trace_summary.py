@@ -1,7 +1,7 @@
 """Per-kernel duration summary of a rocprofv3 --kernel-trace CSV (median / mean / min per
 kernel name and grid), the form of profiles/r02_kernel_trace_summary.json.
 
-usage: python scripts/trace_summary.py gpurun_out/prof_bench/run_kernel_trace.csv out.json
+usage: python scripts/trace_summary.py bench_out/prof_bench/run_kernel_trace.csv out.json
 """
 import csv
 import json

@@ -11,7 +11,7 @@ import pytest
 import raytracebvh_amd as rt
 from raytracebvh_amd import _lib
 from oracle import lib as orc
-from tests.conftest import REPO, load_scene_fixture
+from tests.conftest import GOLDEN, REPO, load_scene_fixture
 
 
 def test_library_exports_every_header_symbol():
@@ -35,10 +35,10 @@ def test_stats_mirror_matches_the_library():
     assert ctypes.sizeof(_lib.Stats) == rt.lib().rtbvh_stats_size()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Obj"), reason="reference not mounted")
 @pytest.mark.parametrize("name", ["Rect", "Image_Test", "Test"])
 def test_native_obj_loader_matches_oracle_loader(name):
-    s = rt.load_obj(f"/root/reference/Obj/{name}.obj")
+    # the reference's mesh and material files (tests/golden/obj); only the textures' names are compared
+    s = rt.load_obj(os.path.join(GOLDEN, "obj", name + ".obj"), load_textures=False)
     f = load_scene_fixture(name)
     np.testing.assert_array_equal(s.vertices, f["vertices"])
     np.testing.assert_array_equal(s.indices, f["indices"])
@@ -180,17 +180,21 @@ def test_bmp_decoder_matches_pil(tmp_path):
         np.testing.assert_array_equal(got, want[::-1], err_msg=path)
 
 
-def test_bmp_decoder_on_reference_textures():
-    """The reference's own texture files (Obj/*.bmp): 8-bit paletted and 24-bit."""
+def test_bmp_decoder_on_reference_textures(tmp_path):
+    """The reference's own texture files (Obj/*.bmp): Map__1_Composite.bmp as it is (tests/golden/textures),
+    the 24-bit one, and Balls.bmp (1.6 MB, too large to store) as the same picture, Balls.jpg, written out
+    again as a BMP of Balls.bmp's kind: 8-bit paletted (256 entries), 1600x1000, 1,601,078 bytes."""
     from raytracebvh_amd.scene import load_texture
     from PIL import Image
-    obj = os.path.join("/root/reference", "Obj")
-    if not os.path.isdir(obj):
-        pytest.skip("reference tree not present")
-    for name in ("Balls.bmp", "Map__1_Composite.bmp"):
-        got = load_texture(os.path.join(obj, name))
-        want = np.asarray(Image.open(os.path.join(obj, name)).convert("RGBA"))
-        np.testing.assert_array_equal(got, want[::-1], err_msg=name)
+    tex = os.path.join(GOLDEN, "textures")
+    with Image.open(os.path.join(tex, "Balls.jpg")) as im:
+        assert im.size == (1600, 1000)
+        im.convert("RGB").quantize(256).save(tmp_path / "Balls.bmp")
+    assert os.path.getsize(tmp_path / "Balls.bmp") == 1601078
+    for path in (str(tmp_path / "Balls.bmp"), os.path.join(tex, "Map__1_Composite.bmp")):
+        got = load_texture(path)
+        want = np.asarray(Image.open(path).convert("RGBA"))
+        np.testing.assert_array_equal(got, want[::-1], err_msg=path)
 
 
 def test_srgb_table_and_sampler_properties():

@@ -163,11 +163,11 @@ def test_shadersim_kats(name):
     assert int((((np.sort(codes & mask)) >> 18) & 1).sum()) == k["bit18_count"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Obj"), reason="reference not mounted")
 @pytest.mark.parametrize("name", ["Rect", "Image_Test", "Test"])
 def test_scene_fixtures_are_current(name):
+    """The parsed scenes (tests/golden/scenes) against the reference's mesh files (tests/golden/obj)."""
     from oracle import obj_oracle
-    d = obj_oracle.load_obj(f"/root/reference/Obj/{name}.obj")
+    d = obj_oracle.load_obj(os.path.join(GOLDEN, "obj", name + ".obj"))
     f = load_scene_fixture(name)
     for key in ("vertices", "indices", "mat_indices", "material_blob"):
         np.testing.assert_array_equal(d[key], f[key])

@@ -104,7 +104,7 @@ def test_host_code_under_asan_and_ubsan(tmp_path):
         "usemtl B\nf 1/1/1 2/1/1 3/2/1\nusemtl A\nf 1/1/2 2/2/2 4/1/1\nf 2/1/1 3/2/2 4/2/1\n")
     files = [str(tmp_path / "q.obj"), os.path.join(REPO, "tests", "golden", "textures", "Balls.jpg"),
              os.path.join(REPO, "tests", "golden", "textures", "Map__1_Composite.bmp")]
-    files += [f"/root/reference/Obj/{n}.obj" for n in ("Rect", "Test") if os.path.exists(f"/root/reference/Obj/{n}.obj")]
+    files += [os.path.join(REPO, "tests", "golden", "obj", n + ".obj") for n in ("Rect", "Test")]
     env = dict(os.environ, TMPDIR=str(tmp_path), ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
                UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([os.path.join(REPO, "tools", "sanitize_host"), "--mutations", "60"] + files,
