@@ -329,6 +329,65 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* ctx, uint32_t width, uint32_t height, 
                                uint32_t nranks, void* comm);
 rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
 
+/* ---- ray queries: closest-hit and any-hit for rays the caller chose ----------------------------
+ * (No reference equivalent: findCollision, RayTraceTraversal.hlsl:106-193, is reachable only through
+ * the reference's own pixel rays.)
+ *
+ * Ray space: rays live in the space the BVH was built in -- vertex positions times the WVP of the last
+ * build, .xyz, with no divide: the space of the RayPresent records and of rtbvh_read_bvh's boxes.  The map is
+ * affine, so t is the same in object space when the caller transforms the origin as a point and the direction
+ * as a vector WITHOUT renormalising it.  With an identity WVP the BVH space is object space.  The direction
+ * need not be unit; 1 / direction is computed by the kernel. */
+/* A ray, 32 B (two 16-B words): {origin.xyz, t_max}, {direction.xyz, reserved}.  t_max = +inf: no limit. */
+typedef struct {
+    float origin[3];
+    float t_max;
+    float direction[3];
+    uint32_t reserved;
+} rtbvh_ray;
+/* A hit, 16 B: the distance t along the ray (hit point = origin + t * direction), the barycentrics of the hit
+ * on vertices 1 and 2 of the triangle (rayTriangleCollision's u and v, RayTraceTraversal.hlsl:41-86), and the
+ * triangle's id in triangle order (Node.index / 3).  A miss: t = -1, u = v = 0, tri = 0xFFFFFFFF. */
+typedef struct {
+    float t, u, v;
+    uint32_t tri;
+} rtbvh_hit;
+enum {
+    RTBVH_QUERY_CLOSEST = 0,      /* findCollision exactly: the left-first DFS, rayTriangleCollision's EPSILON, the
+                                     strict `<` replacement.  t_max enters in two places only: a triangle's t is
+                                     accepted iff the reference accepts it and t <= t_max; a box passes iff the
+                                     reference's first two conditions hold and (hit ? mn <= dist : !(mn > t_max)).
+                                     With t_max = +inf the reference, bit for bit.  A ray with a zero or
+                                     non-finite direction or origin is a miss */
+    RTBVH_QUERY_ANY = 1u << 0,    /* occlusion: the box test without the `hit` branch, the walk ends at the first
+                                     accepted triangle, whose {t, u, v, tri} is the result (which triangle is
+                                     unspecified).  Whether a ray hits equals the closest-hit answer */
+    RTBVH_QUERY_SORT = 1u << 1,   /* walk the rays in (direction octant, origin Morton) order, as
+                                     RTBVH_FLAG_SORT_BOUNCE does: same results, each at its ray's own index */
+    RTBVH_QUERY_COUNT = 1u << 2   /* count rays, hits and visits for rtbvh_query_counts (slower) */
+};
+/* n rays at dev_rays and n hits at dev_hits (device memory of the context's device, 16-B aligned), hit k for
+ * ray k, enqueued on `stream` (hipStream_t, NULL = the context stream).  The walk reads the tree the last build
+ * wrote.  Ordering: a query waits for the last build, the next build waits for the outstanding queries, and
+ * rtbvh_synchronize waits for them; queries may be enqueued on any stream -- the library orders them among
+ * themselves (they share scratch owned by the context, grown on demand), so queries on different streams run
+ * one after the other.  The caller orders the rays' producer before, and the hits' consumer after, on `stream`.
+ * The call only enqueues, with one exception: the first RTBVH_QUERY_SORT query of a context, and each one with
+ * more rays than any before it, grows the sort's buffers, which waits on the host for the outstanding queries
+ * and allocates device memory (size the first SORT query for the largest batch to keep later ones asynchronous).
+ * n == 0 returns RTBVH_OK and touches nothing; RTBVH_ERR_NOT_READY before a build; RTBVH_ERR_INVALID_ARG for
+ * NULL pointers with n > 0, unknown mode bits, and n >= 2^31.  Rays that hit rtbvh_config.stack_limit end early
+ * with the best hit found so far, and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW as after a
+ * trace.  rtbvh_stats.stack_overflows stays the last trace's: the stats are read from the trace's own counter
+ * block, which a query on another stream must not write while a trace or rtbvh_get_stats uses it. */
+rtbvh_status rtbvh_query_async(rtbvh_ctx* ctx, const rtbvh_ray* dev_rays, uint64_t n, rtbvh_hit* dev_hits,
+                               uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream; the hits are complete
+ * when it returns RTBVH_ERR_STACK_OVERFLOW). */
+rtbvh_status rtbvh_query_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode);
+/* The last RTBVH_QUERY_COUNT query (waits for it): rays, hits, internal-node visits, leaf visits. */
+rtbvh_status rtbvh_query_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */
 rtbvh_status rtbvh_read_framebuffer(rtbvh_ctx* ctx, float* rgba);

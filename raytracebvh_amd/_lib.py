@@ -45,6 +45,7 @@ EXPORTS = [
     "rtbvh_texture_load", "rtbvh_texture_free", "rtbvh_srgb_table",
     "rtbvh_present", "rtbvh_save_bmp", "rtbvh_assemble_bands", "rtbvh_comm_unique_id", "rtbvh_comm_init",
     "rtbvh_comm_destroy", "rtbvh_trace_tiles",
+    "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts",
 ]
 COMM_ID_BYTES = 128
 
@@ -54,6 +55,11 @@ MATERIAL_DTYPE = np.dtype([("ambient", "<f4", (4,)), ("diffuse", "<f4", (4,)), (
                            ("shininess", "<f4"), ("optical_density", "<f4"), ("alpha", "<f4"),
                            ("specularb", "<u4"), ("tex_num", "<i4")])
 assert NODE_DTYPE.itemsize == 44 and MATERIAL_DTYPE.itemsize == 68
+# rtbvh_ray (32 B) and rtbvh_hit (16 B), include/rtbvh.h; a miss: t = -1, u = v = 0, tri = 0xFFFFFFFF
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "<f4", (3,)), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
+QUERY_CLOSEST, QUERY_ANY, QUERY_SORT, QUERY_COUNT = 0, 1, 2, 4   # RTBVH_QUERY_*
 
 
 class Config(ctypes.Structure):
@@ -61,6 +67,17 @@ class Config(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("scene_bb_min", ctypes.c_float * 3),
                 ("scene_bb_max", ctypes.c_float * 3), ("stream", ctypes.c_void_p),
                 ("stack_limit", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class Ray(ctypes.Structure):
+    """rtbvh_ray (include/rtbvh.h)."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("t_max", ctypes.c_float), ("direction", ctypes.c_float * 3),
+                ("reserved", ctypes.c_uint32)]
+
+
+class Hit(ctypes.Structure):
+    """rtbvh_hit (include/rtbvh.h)."""
+    _fields_ = [("t", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float), ("tri", ctypes.c_uint32)]
 
 
 class Texture(ctypes.Structure):
@@ -183,6 +200,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_srgb_table": (None, [vp]),
         "rtbvh_present": (i32, [vp, vp]),
         "rtbvh_save_bmp": (i32, [ctypes.c_char_p, vp, u32, u32]),
+        "rtbvh_query_async": (i32, [vp, vp, u64, vp, u32, vp]),
+        "rtbvh_query_host": (i32, [vp, vp, u64, vp, u32]),
+        "rtbvh_query_counts": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -191,6 +191,17 @@ struct rtbvh_ctx {
     };
     std::deque<DealTab> deals;       // the MAX_DEALS most recently used (H, nranks, share), most recent first
     static constexpr size_t MAX_DEALS = 8;
+    // Ray queries (rtbvh_query_async), on any stream.  They share one scratch block (the walk's work counters and
+    // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
+    // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
+    uint32_t* d_qscratch = nullptr;          // [QUERY_SCRATCH_WORDS]
+    uint32_t* d_qsort = nullptr;             // RTBVH_QUERY_SORT: 6 arrays of cap_qsort words (keys and values: in,
+    uint32_t* d_qsort_scratch = nullptr;     //   A, B), and the sort's digit counts; grown on demand
+    size_t cap_qsort = 0;
+    hipEvent_t ev_query = nullptr;
+    bool query_busy = false;
+    bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
+    bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
 };
 
 namespace {
@@ -671,6 +682,17 @@ rtbvh_status sync_all(rtbvh_ctx* c) {
     HIPC(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
         if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+    if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
+    return RTBVH_OK;
+}
+
+// The next writer of the BVH on stream s (a build) waits for the outstanding ray queries, which read it.  (Never
+// inside a capture: rtbvh_compute_bvh's plain frame before it has cleared query_busy.)
+rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
+    if (c->query_busy) {
+        HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+        c->query_busy = false;
+    }
     return RTBVH_OK;
 }
 
@@ -1147,6 +1169,11 @@ void rtbvh_destroy(rtbvh_ctx* c) {
             (void)hipEventDestroy(c->ev_slot[k]);
         }
     if (c->ev_built) (void)hipEventDestroy(c->ev_built);
+    if (c->ev_query) {
+        (void)hipEventSynchronize(c->ev_query);   // ray queries on caller streams
+        (void)hipEventDestroy(c->ev_query);
+    }
+    dfree(c->d_qscratch); dfree(c->d_qsort); dfree(c->d_qsort_scratch);
     drop_graph(c);
     for (uint32_t g = 1; g < rtbvh_ctx::MAXSPLIT; g++) {
         if (c->sub[g]) {
@@ -1214,6 +1241,8 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
         if (mat_idx[t] >= nmats) return fail(c, RTBVH_ERR_INVALID_ARG, "set_scene: material index out of range");
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipStreamSynchronize(c->stream));
+    if (c->ev_query) HIPC(c, hipEventSynchronize(c->ev_query));   // ray queries on caller streams read the old BVH
+    c->query_busy = false;
     try {
         std::vector<float4> opos(nverts);
         for (uint32_t i = 0; i < nverts; i++)
@@ -1301,7 +1330,9 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
             HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
             c->slot_busy[k] = false;
         }
-    rtbvh_status cst = sync_camera(c, s);
+    rtbvh_status cst = wait_queries(c, s);   // ... and so do the outstanding ray queries
+    if (cst) return cst;
+    cst = sync_camera(c, s);
     if (cst) return cst;
     hipEvent_t* ev = c->evb[c->n_builds % rtbvh_ctx::RING];
     if (timing) HIPC(c, hipEventRecord(ev[0], s));
@@ -1470,7 +1501,9 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
             HIPC(c, hipStreamWaitEvent(c->stream, c->ev_slot[k], 0));
             c->slot_busy[k] = false;
         }
-    rtbvh_status cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
+    rtbvh_status cst = wait_queries(c, c->stream);
+    if (cst) return cst;
+    cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
     if (cst) return cst;
     HIPC(c, hipGraphLaunch(c->graph_exec, c->stream));
     HIPC(c, hipEventRecord(c->ev_built, c->stream));
@@ -1714,10 +1747,20 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* c) {
     HIPC(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)   // and the frames in flight on caller streams
         if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+    if (c->query_busy) {   // and the ray queries
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        c->query_busy = false;
+    }
     // each trace ends by copying the never-reset overflow word into its slot's pinned word
     unsigned long long ovf = c->ovf_seen;
     for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++)
         if (c->h_ovf[k] > ovf) ovf = c->h_ovf[k];
+    if (c->query_ovf) {   // queries run on any stream: the word itself, once they are all done
+        unsigned long long v = 0;
+        HIPC(c, hipMemcpy(&v, c->d_ovf, sizeof(v), hipMemcpyDeviceToHost));
+        c->query_ovf = false;
+        if (v > ovf) ovf = v;
+    }
     if (ovf > c->ovf_seen) {
         const unsigned long long n = ovf - c->ovf_seen;
         c->ovf_seen = ovf;
@@ -2003,6 +2046,8 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
                                     rtbvh_node* out) {
     if (!c || !sorted_codes || !leaf_boxes || !out || n == 0 || n >= (1u << 30)) return RTBVH_ERR_INVALID_ARG;
     HIPC(c, hipSetDevice(c->cfg.device));
+    if (c->ev_query) HIPC(c, hipEventSynchronize(c->ev_query));   // (the scene's BVH buffers are reused)
+    c->query_busy = false;
     rtbvh_status st = ensure_build_capacity(c, n);
     if (st) return st;
     float* d_boxes = nullptr;
@@ -2030,6 +2075,103 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     c->built = false;   // the scene's BVH buffers were reused
     c->build_nbox = false;
     c->rec_ok = c->nbox_ok = false;
+    return RTBVH_OK;
+}
+
+// ---- ray queries -------------------------------------------------------------------------------------
+// The walk reads the tree form the last build wrote (build_nbox: the topology and node boxes, else the node
+// records), never a derived one.  Queries on any stream are chained by ev_query (they share the scratch block
+// and the sort's buffers); each waits for the last build (ev_built), the next build for them (wait_queries).
+rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, rtbvh_hit* dev_hits,
+                               uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_QUERY_ANY | RTBVH_QUERY_SORT | RTBVH_QUERY_COUNT))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "query: unknown mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "query: 2^31 rays or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "query: NULL rays or hits");
+    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "query before build");
+    static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "query record layouts");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool any = (mode & RTBVH_QUERY_ANY) != 0, sort = (mode & RTBVH_QUERY_SORT) != 0;
+    const bool count = (mode & RTBVH_QUERY_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, dalloc(c->d_qscratch, QUERY_SCRATCH_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    if (sort && (n > c->cap_qsort || !c->d_qsort)) {
+        // earlier queries sort in the old buffers: the first RTBVH_QUERY_SORT query and each larger one wait
+        // for them on the host here (and hipMalloc blocks too), as include/rtbvh.h says
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        c->cap_qsort = 0;
+        HIPC(c, dalloc(c->d_qsort, 6 * (size_t)n));
+        HIPC(c, dalloc(c->d_qsort_scratch, sort_scratch_words(N)));
+        c->cap_qsort = n;
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    // the work counters, and a counting query's count block behind them
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0,
+                           sizeof(uint32_t) * (count ? QUERY_SCRATCH_WORDS : NEXT_SEGS * NEXT_STRIDE), s));
+    QueryArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->build_nbox;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.rays = reinterpret_cast<const float4*>(dev_rays);
+    a.hits = reinterpret_cast<float4*>(dev_hits);
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + NEXT_SEGS * NEXT_STRIDE);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->cap_qsort;
+        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    launch_query(a, any, count, s);
+    rtbvh_status st = check_launch(c, "query kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->query_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_query_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->built)   // (nothing to stage: the checks of the query)
+        return rtbvh_query_async(c, rays, n, hits, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    char* d = nullptr;
+    HIPC(c, hipMalloc((void**)&d, (size_t)n * (sizeof(rtbvh_ray) + sizeof(rtbvh_hit))));
+    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d);
+    rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d + (size_t)n * sizeof(rtbvh_ray));
+    rtbvh_status st = RTBVH_OK;
+    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
+        st = fail(c, RTBVH_ERR_HIP, "query_host: upload failed");
+    if (!st) st = rtbvh_query_async(c, dr, n, dh, mode, nullptr);
+    if (!st && hipStreamSynchronize(c->stream) != hipSuccess) st = fail(c, RTBVH_ERR_HIP, "query_host: sync");
+    if (!st && hipMemcpy(hits, dh, (size_t)n * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
+        st = fail(c, RTBVH_ERR_HIP, "query_host: download failed");
+    (void)hipFree(d);
+    if (st) return st;
+    return rtbvh_synchronize(c);   // (the hits are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_query_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->query_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_QUERY_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "count block words");
+    HIPC(c, hipMemcpy(out, c->d_qscratch + NEXT_SEGS * NEXT_STRIDE, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 

@@ -274,4 +274,32 @@ void launch_present(const float4* color, uint32_t W, uint32_t H, uint32_t* out, 
 void launch_bounce_keys(const RayQ* q, const uint32_t* count, const float* box, uint32_t P, uint32_t* keys,
                         uint32_t* vals, hipStream_t s);
 
+// ---- ray queries (trace.hip k_query; rtbvh_query_async) ----------------------
+// Caller rays (rtbvh_ray: two float4, {origin, t_max}, {direction, reserved}) walked in the reference order on
+// the tree form the last build wrote -- the node records, or (nb) the topology and the node boxes -- and one
+// rtbvh_hit (a float4: t, u, v, tri) stored per ray at the ray's own index.
+struct QueryArgs {
+    const Inner* inner;       // node records in slots (BuildArgs::rec), !nb
+    const uint4* topo;        // nb: BuildArgs::topo, BuildArgs::nbox
+    const float* nbox;
+    bool nb;
+    const float4* leaf;       // [4T] sorted leaf records
+    uint32_t T;
+    const float4* rays;       // [2n]
+    float4* hits;             // [n]
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_QUERY_SORT: ray perm[k] is the k-th claimed), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_QUERY_COUNT: [4] rays, hits, internal visits, leaf visits (zeroed)
+    unsigned long long* overflow;   // the context's overflow word (TraceArgs::overflow)
+    int stack_limit;          // <= STACK_SIZE
+};
+constexpr uint32_t QUERY_COUNT_WORDS = 4;
+// words of a query's scratch block: the work counters, then the count block (8-byte aligned)
+constexpr uint32_t QUERY_SCRATCH_WORDS = NEXT_SEGS * NEXT_STRIDE + 2 * QUERY_COUNT_WORDS;
+void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s);
+// the coherence keys of caller rays (launch_bounce_keys' scheme over the root box) and vals[i] = i
+void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                       hipStream_t s);
+
 }  // namespace rtbvh

@@ -2436,7 +2436,230 @@ void launch_bounce_trav_t(const TraceArgs& a, const RayQ* qin, const uint32_t* q
 #undef RTBVH_BTE
 }
 
+// ---- ray queries (rtbvh_query_async): caller rays in, (t, u, v, triangle) out ------------------------
+// findCollision for rays the caller chose, in the space the BVH was built in.  One ray per lane on the per-lane
+// walk state of k_bounce_trav's reference-order mode (the stack top cached in a register, entries [0, SB) in LDS
+// columns, deeper ones in scratch; one 64-B fetch a step, leaf or node), the same claims (per-wave segment claims
+// on per-XCD counters, a refill once REFILL_MIN lanes are idle): caller rays are incoherent, and any-hit walks
+// end at very different lengths.  A ray is two float4 loads, a hit one 16-B store at the ray's own index.
+// t_max enters in two places only: a triangle's t is accepted iff the reference accepts it and t <= t_max; a
+// box passes iff the reference's first two conditions hold and (hit ? mn <= dist : !(mn > t_max)) -- with
+// t_max = +inf the reference, bit for bit.  A zero or non-finite direction or origin needs no special case:
+// the arithmetic makes the ray a miss.
+// ANY: the box test without the `hit` branch, the walk ends at the first accepted triangle.
+// NB: on the topology and the node boxes (traverse_nb's fetches), for a build that wrote no records.
+// Every instance keeps the walk-length guard and reads the stack limit at run time (compiling them out where no
+// context needs them, as k_bounce_trav's GUARD and LIM do, measured 12.13 -> 12.06 ms at C5: less than the
+// figure moves between runs, so not worth twice the instances).
+// (u, v) of the winning triangle are recomputed once at the end, not carried through the walk.
+__device__ __forceinline__ void ray_triangle_uv(f3 o, f3 d, f3 p0, f3 e1, f3 e2, float& u, float& v) {
+    const f3 tmp = cross(d, e2);
+    const float idx = 1.f / dot(e1, tmp);
+    const f3 rt = sub(o, p0);
+    u = dot(rt, tmp) * idx;
+    v = dot(d, cross(rt, e1)) * idx;
+}
+template <bool ANY>
+__device__ __forceinline__ bool query_box(f3 o, f3 inv, f2v lo, f2v hi, float lz, float hz, bool hit, float best,
+                                          float tmax) {
+    float mn;
+    const bool base = ray_box_xy(o, inv, lo, hi, lz, hz, false, 0.f, mn);
+    return base && (!ANY && hit ? mn <= best : !(mn > tmax));
+}
+template <bool ANY, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query(QueryArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id(), tid = threadIdx.x;
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nrays = 0, nhits = 0;
+    bool has = false, hit = false;
+    uint32_t r = 0, node = 0, top = INVALID, bl = 0, guard = 0;
+    int sp = 0;
+    float best = 0.f, tmax = 0.f;
+    f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    auto spush = [&](uint32_t v) {
+        if (sp < SB) s_stk[sp][tid] = v;
+        else stack[sp - SB] = v;
+        ++sp;
+    };
+    auto spop = [&]() {   // the next node from the cached top; refill the top from entry --sp
+        node = top;
+        if (--sp >= 0) top = sp < SB ? s_stk[sp][tid] : stack[sp - SB];
+    };
+    auto start = [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
+        r = a.perm ? a.perm[p] : p;
+        const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
+        o = mk(q0.x, q0.y, q0.z);
+        tmax = q0.w;
+        d = mk(q1.x, q1.y, q1.z);
+        inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+        has = true;
+        hit = false;
+        best = 0.f;
+        bl = 0;
+        sp = 0;
+        top = INVALID;
+        node = NB ? (T > 1 ? 0u : LEAF_BIT) : root_slot(T);
+        guard = 2 * T + 2;
+    };
+    bool drained = false;
+    uint32_t kseg = 0;   // segments claimed from so far (wave-uniform)
+    while (true) {
+        const uint64_t idle = __ballot(!has);
+        const uint32_t nidle = (uint32_t)__popcll(idle);
+        if (!drained && (nidle >= REFILL_MIN || nidle == 64)) {
+            const uint32_t seg = claim_segment(kseg);
+            const uint32_t s0 = (uint32_t)((uint64_t)n * seg / NEXT_SEGS);
+            const uint32_t len = (uint32_t)((uint64_t)n * (seg + 1) / NEXT_SEGS) - s0;
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(a.next + NEXT_STRIDE * seg, nidle);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + nidle >= len && ++kseg == NEXT_SEGS) drained = true;   // segment (and the last) used up
+            if (!has) {
+                const uint32_t p = base + lane_rank(idle);
+                if (p < len) start(s0 + p);
+            }
+        }
+        if (__ballot(has) == 0 && drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_bounce_trav); NB: a node's
+        // children from the topology, then their boxes
+        v4f q0, q1, q2;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2];
+            v4f q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const uint4 tp = a.topo[node];
+            cl = tp.x;
+            cr = tp.y;
+            f2v lmn, lmx, rmn, rmx;
+            float lz0, lz1, rz0, rz1;
+            nb_child_box(a.nbox, leaf, cl, lmn, lmx, lz0, lz1);
+            nb_child_box(a.nbox, leaf, cr, rmn, rmx, rz0, rz1);
+            q0 = v4f{lmn.x, lmn.y, lmx.x, lmx.y};   // the record's layout
+            q1 = v4f{rmn.x, rmn.y, rmx.x, rmx.y};
+            q2 = v4f{lz0, lz1, rz0, rz1};
+        }
+        if (--guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            const uint32_t j = node & ~LEAF_BIT;
+            if (COUNT) c.leaf++;
+            const float t = ray_triangle(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x));
+            if (t != -1.f && t <= tmax && (ANY || !hit || t < best)) {
+                best = t;
+                bl = j;
+                hit = true;
+                if (ANY) done = true;
+            }
+            if (!done) {
+                spop();
+                done = sp == -1;
+            }
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = query_box<ANY>(o, inv, q0.xy, q0.zw, q2.x, q2.y, hit, best, tmax);
+            const bool rh = query_box<ANY>(o, inv, q1.xy, q1.zw, q2.z, q2.w, hit, best, tmax);
+            if (!lh && !rh) {
+                spop();
+                done = sp == -1;
+            } else if (lh && rh) {
+                if (sp + 1 >= limit) {
+                    c.overflow++;
+                    spop();
+                    done = sp == -1;
+                } else {
+                    spush(top);   // push the second child
+                    top = cr;
+                    node = cl;
+                }
+            } else {
+                node = lh ? cl : cr;
+            }
+        }
+        if (done) {
+            // (u, v) of the winning triangle, recomputed once from its leaf record.  (Fetching the record with the
+            // wave's next common fetch instead -- the ray taking one more step at its leaf -- gained nothing: C5,
+            // closest-hit 12.06 -> 12.32 ms)
+            float4 h = make_float4(-1.f, 0.f, 0.f, __uint_as_float(INVALID));
+            if (hit) {
+                const float4* lr = leaf + 4 * (size_t)bl;
+                const float4 la = lr[0], lb = lr[1], lc = lr[2];
+                float u, v;
+                ray_triangle_uv(o, d, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y), mk(lb.z, lb.w, lc.x), u, v);
+                h = make_float4(best, u, v, __uint_as_float(__float_as_uint(lc.y) & ~LEAF_BIT));
+            }
+            a.hits[r] = h;
+            has = false;
+            if (COUNT) {
+                nrays++;
+                nhits += hit;
+            }
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nrays, nhits, c.internal, c.leaf, c.overflow};
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
+// the coherence key of caller rays: k_bounce_keys' (octant, origin Morton) over the root box
+__global__ __launch_bounds__(BLOCK) void k_query_keys(const float4* __restrict__ rays, uint32_t n,
+                                                      const float* __restrict__ box, uint32_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 q0 = rays[2 * (size_t)i], q1 = rays[2 * (size_t)i + 1];
+    const uint32_t oct = (q1.x < 0.f) | ((q1.y < 0.f) << 1) | ((q1.z < 0.f) << 2);
+    const uint32_t m = spread9(q9(q0.x, box[0], box[3])) << 2 | spread9(q9(q0.y, box[1], box[4])) << 1 |
+                       spread9(q9(q0.z, box[2], box[5]));
+    keys[i] = oct << 27 | m;
+    vals[i] = i;
+}
+
 }  // namespace
+
+void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    // the persistent grid of the bounce walk (8 waves per SIMD), or a workgroup per 256 rays when that is fewer
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+#define RTBVH_Q(A, C, N) hipLaunchKernelGGL((k_query<A, C, N>), dim3(blocks), dim3(BLOCK), 0, s, a)
+#define RTBVH_QC(A, C) do { if (a.nb) RTBVH_Q(A, C, true); else RTBVH_Q(A, C, false); } while (0)
+    if (any) { if (count) RTBVH_QC(true, true); else RTBVH_QC(true, false); }
+    else { if (count) RTBVH_QC(false, true); else RTBVH_QC(false, false); }
+#undef RTBVH_QC
+#undef RTBVH_Q
+}
+
+void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                       hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_query_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rays, n, box, keys, vals);
+}
 
 void launch_primary(const TraceArgs& a, RayQ* q, uint32_t* qcount, bool count, bool emit, PrimaryKind kind,
                     hipStream_t s) {

@@ -17,6 +17,64 @@ from . import _lib as _L
 from .scene import EYE_REFERENCE, Scene, camera_look, camera_orbit, camera_reference
 
 
+def _is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def make_rays(origins, directions, t_max=float("inf")):
+    """Packs (N, 3) origins and directions (and one t_max, or N of them) as query rays: torch tensors give an
+    (N, 8) float32 tensor on their device, anything else a RAY_DTYPE array (include/rtbvh.h rtbvh_ray).  The
+    rays live in the space the BVH was built in; directions need not be unit."""
+    if _is_tensor(origins) or _is_tensor(directions):
+        import torch
+        dev = origins.device if _is_tensor(origins) else directions.device
+        o = torch.as_tensor(origins, dtype=torch.float32, device=dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=dev).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"make_rays: {tuple(o.shape)} origins and {tuple(d.shape)} directions")
+        rays = torch.zeros((o.shape[0], 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = o
+        rays[:, 3] = torch.as_tensor(t_max, dtype=torch.float32, device=dev)
+        rays[:, 4:7] = d
+        return rays
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f"make_rays: {o.shape} origins and {d.shape} directions")
+    rays = np.zeros(len(o), _L.RAY_DTYPE)
+    rays["origin"] = o
+    rays["t_max"] = np.asarray(t_max, np.float32)
+    rays["direction"] = d
+    return rays
+
+
+def check_query_rays(rays, device=None):
+    """Context.query's input check: ("torch", rays) for an (N, 8) float32 contiguous CUDA tensor (on `device`
+    when given), ("numpy", RAY_DTYPE view) for a C-contiguous RAY_DTYPE array or (N, 8) float32 array;
+    ValueError for anything else.  Calls nothing in the library."""
+    if _is_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"query: rays must be an (N, 8) float32 tensor, got {tuple(rays.shape)} {rays.dtype}")
+        if not rays.is_cuda:
+            raise ValueError("query: a torch tensor of rays must be on the context's GPU (numpy arrays take the host path)")
+        if device is not None and rays.device.index != device:
+            raise ValueError(f"query: rays on {rays.device}, the context on device {device}")
+        if not rays.is_contiguous():
+            raise ValueError("query: rays must be contiguous")
+        return "torch", rays
+    if not isinstance(rays, np.ndarray):
+        raise ValueError("query: rays must be a torch CUDA tensor or a numpy array")
+    if rays.dtype == _L.RAY_DTYPE:
+        if rays.ndim != 1:
+            raise ValueError(f"query: a RAY_DTYPE array must be one-dimensional, got shape {rays.shape}")
+    elif rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError(f"query: rays must be RAY_DTYPE or (N, 8) float32, got {rays.shape} {rays.dtype}")
+    if not rays.flags["C_CONTIGUOUS"]:
+        raise ValueError("query: rays must be C-contiguous")
+    return "numpy", rays.view(_L.RAY_DTYPE).reshape(-1)
+
+
 class Context:
     """One rtbvh_ctx: one HIP device, one stream, the scene/BVH/frame buffers."""
 
@@ -37,6 +95,7 @@ class Context:
         h = ctypes.c_void_p()
         _L.check(L.rtbvh_create(ctypes.byref(cfg), ctypes.byref(h)), None)
         self._h = h
+        self.device = device
         self.num_tris = 0
         self.width = self.height = 0
 
@@ -133,6 +192,53 @@ class Context:
 
     def synchronize(self):
         self._check(_L.lib().rtbvh_synchronize(self._h))
+
+    # -- ray queries --
+    def query(self, rays, mode: int = 0, out=None, stream=None):
+        """rtbvh_query_async / rtbvh_query_host: the closest hit (or with QUERY_ANY any hit) of each ray, in the
+        space the BVH was built in (include/rtbvh.h).
+
+        An (N, 8) float32 contiguous CUDA tensor on the context's device (make_rays) goes to the device entry with
+        no host copy, enqueued on `stream` (a torch stream or a hipStream_t handle; default: the current torch
+        stream), and returns an (N, 4) float32 device tensor {t, u, v, tri}: read the triangle ids with
+        hits[:, 3].view(torch.int32) (a miss: t = -1, tri = -1).  On torch's legacy default stream (handle 0,
+        which the library cannot name) the query runs on the context stream between two synchronisations.
+        A RAY_DTYPE or (N, 8) float32 numpy array goes through the synchronous host entry and returns a HIT_DTYPE
+        array.  `out` receives the hits when given.  ValueError for a wrong shape, dtype, device or layout."""
+        kind, rays = check_query_rays(rays, getattr(self, "device", None))
+        n = len(rays)
+        L = _L.lib()
+        if kind == "numpy":
+            if out is None:
+                out = np.zeros(n, _L.HIT_DTYPE)
+            elif not (isinstance(out, np.ndarray) and out.dtype == _L.HIT_DTYPE and out.shape == (n,) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"query: out must be a contiguous HIT_DTYPE array of {n} hits")
+            self._check(L.rtbvh_query_host(self._h, ctypes.c_void_p(rays.ctypes.data), n,
+                                           ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 4) and
+                  out.device == rays.device and out.is_contiguous()):
+            raise ValueError(f"query: out must be a contiguous ({n}, 4) float32 tensor on {rays.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(rays.device).synchronize()
+        self._check(L.rtbvh_query_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                        mode, ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def query_counts(self) -> dict:
+        """rtbvh_query_counts: rays, hits, internal and leaf visits of the last QUERY_COUNT query."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_query_counts(self._h, _L.ptr(out)))
+        return dict(zip(("rays", "hits", "internal_visits", "leaf_visits"), (int(v) for v in out)))
 
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
