@@ -12,6 +12,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rtbvh.h"
@@ -19,70 +20,120 @@
 
 using namespace rtbvh;
 
+#ifndef RTBVH_MAXSPLIT
+#define RTBVH_MAXSPLIT 4
+#endif
+
+// Move-only owners of what the context allocates: a handle, released by Del when its owner goes.  They convert
+// to the handle, so launch sites read as with raw pointers; out() is for the HIP call that creates the handle.
+template <typename H, void (*Del)(H)>
+struct Owner {
+    H h{};
+    Owner() = default;
+    Owner(Owner&& o) noexcept : h(o.h) { o.h = H{}; }
+    Owner& operator=(Owner&& o) noexcept {
+        std::swap(h, o.h);
+        return *this;
+    }
+    ~Owner() { reset(); }
+    void reset() {
+        if (h) Del(h);
+        h = H{};
+    }
+    H* out() {
+        reset();
+        return &h;
+    }
+    operator H() const { return h; }
+};
+template <typename T> void del_device(T* p) { (void)hipFree((void*)p); }
+template <typename T> void del_pinned(T* p) { (void)hipHostFree((void*)p); }
+inline void del_event(hipEvent_t e) { (void)hipEventDestroy(e); }
+inline void del_stream(hipStream_t s) {
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+}
+template <typename T>
+struct DevBuf : Owner<T*, del_device<T>> {   // alloc: frees first; a count of 0 allocates one element
+    hipError_t alloc(size_t count) { return hipMalloc((void**)this->out(), (count ? count : 1) * sizeof(T)); }
+};
+template <typename T>
+struct Pinned : Owner<T*, del_pinned<T>> {
+    hipError_t alloc(size_t count) {
+        return hipHostMalloc((void**)this->out(), count * sizeof(T), hipHostMallocDefault);
+    }
+};
+using Event = Owner<hipEvent_t, del_event>;
+using Stream = Owner<hipStream_t, del_stream>;
+
+// The forms of the built tree a walk or a reader may ask for (Tree::valid, ensure_form)
+enum Form : uint32_t { RECORDS = 1, NBOX = 2, PSEUDO = 4, QNODES = 8 };
+// The built tree.  A build assigns it whole, set_scene and build_from_codes reset it, and a replayed graph
+// (compute_graph) restores the record its capture ended with: the replayed build rewrote the tree.
+struct Tree {
+    bool built = false;
+    bool clz64 = false;      // built with the clz64 delta: a valid tree (no cycles)
+    Form wrote = RECORDS;    // the node form the build wrote: records, or (a certified-only context's) node boxes;
+                             //   the other is derived on first use
+    uint32_t valid = 0;      // the forms that are complete now: node records (the binary and packet walks'), node
+                             //   boxes (a certified trace's reference-order re-traces), the leaf pseudo-records
+                             //   (the packet walks') and the QNodes (the 4-wide bounce walk's)
+};
+
 struct rtbvh_ctx {
     rtbvh_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // Members are destroyed last to first: the streams the context created stand first, so they outlive every
+    // buffer and event below (rtbvh_destroy has drained them by then).
+    Stream own_stream, side, sub[RTBVH_MAXSPLIT];
+    hipStream_t stream = nullptr;   // the context stream: the caller's (cfg.stream) or own_stream
     std::string err;
 
     // scene (set_scene)
     uint32_t V = 0, T = 0, nmat = 0;
-    float4* d_opos = nullptr;
-    float* d_verts = nullptr;
-    uint32_t* d_idx = nullptr;
-    uint32_t* d_matidx = nullptr;
-    Mat* d_mats = nullptr;
+    DevBuf<float4> d_opos;
+    DevBuf<float> d_verts;
+    DevBuf<uint32_t> d_idx, d_matidx;
+    DevBuf<Mat> d_mats;
     float wvp[16], wv[16];
-    float* d_cam = nullptr;     // [32] the kernels' camera (BuildArgs::cam): WVP, WV, uploaded in stream order
+    DevBuf<float> d_cam;        // [32] the kernels' camera (BuildArgs::cam): WVP, WV, uploaded in stream order
     bool cam_dirty = false;     //   (sync_camera) when set_camera changed it
-    bool have_scene = false, have_camera = false, built = false;
-    bool built_clz64 = false;   // the BVH was built with the clz64 delta: a valid tree (no cycles)
+    bool have_scene = false, have_camera = false;
+    Tree tree;
 
     // build buffers (capacity cap_T)
     uint32_t cap_T = 0;
-    uint32_t *d_codes = nullptr, *d_ids = nullptr, *d_ka = nullptr, *d_va = nullptr, *d_kb = nullptr, *d_vb = nullptr;
-    uint32_t* d_sort_scratch = nullptr;
-    float4 *d_tclip = nullptr, *d_leaf = nullptr;
-    float4* d_band = nullptr;                // rtbvh_trace_tiles: this rank's bands; rank 0: all ranks'
+    DevBuf<uint32_t> d_codes, d_ids, d_ka, d_va, d_kb, d_vb, d_sort_scratch;
+    DevBuf<float4> d_tclip, d_leaf;
+    DevBuf<float4> d_band;                   // rtbvh_trace_tiles: this rank's bands; rank 0: all ranks'
     size_t cap_band = 0;                     //   (float4 capacity)
-    Inner* d_inner = nullptr;                // box hand-off of refit nodes spanning workgroups
-    uint4* d_topo = nullptr;                 // Karras node: child ids + leaf range
-    Inner* d_rec = nullptr;                  // node records in slots (rtbvh_device.h), 2T-1
-    QNode* d_qnode = nullptr;                // quantized 4-wide nodes in slots (rtbvh_device.h), 2T-1
-    uint4* d_lfp = nullptr;                  // leaf footprints on the primary pixel grid (binned primary pass)
-    uint32_t* d_texels = nullptr;            // textures (rtbvh_texture), concatenated RGBA8
-    uint4* d_texinfo = nullptr;
-    float* d_srgb = nullptr;
+    DevBuf<Inner> d_inner;                   // box hand-off of refit nodes spanning workgroups
+    DevBuf<uint4> d_topo;                    // Karras node: child ids + leaf range
+    DevBuf<Inner> d_rec;                     // node records in slots (rtbvh_device.h), 2T-1
+    DevBuf<QNode> d_qnode;                   // quantized 4-wide nodes in slots (rtbvh_device.h), 2T-1
+    DevBuf<uint4> d_lfp;                     // leaf footprints on the primary pixel grid (binned primary pass)
+    DevBuf<uint32_t> d_texels;               // textures (rtbvh_texture), concatenated RGBA8
+    DevBuf<uint4> d_texinfo;
+    DevBuf<float> d_srgb;
     uint32_t ntex = 0;
-    float* d_refl_rec = nullptr;             // RTBVH_FLAG_REFRACT_RECORDS: reflectRay / refractRay
-    float* d_refr_rec = nullptr;             //   RayPresent records, 14 floats per traced pixel
+    DevBuf<float> d_refl_rec;                // RTBVH_FLAG_REFRACT_RECORDS: reflectRay / refractRay
+    DevBuf<float> d_refr_rec;                //   RayPresent records, 14 floats per traced pixel
     size_t cap_rec = 0, rec_P = 0;           // record capacity; pixels of the last records trace
-    uint32_t *d_pleaf = nullptr, *d_pint = nullptr, *d_cnt = nullptr;
-    uint32_t *d_xlist = nullptr, *d_xcnt = nullptr;   // refit: crossing nodes per workgroup
-    uint32_t* d_qlate = nullptr;                        // BuildArgs::qlate
-    unsigned long long* d_ovf = nullptr;     // stack overflows + guard trips of every trace (never reset)
-    unsigned long long* h_ovf = nullptr;     // pinned: a snapshot of *d_ovf copied at the end of each trace,
+    DevBuf<uint32_t> d_pleaf, d_pint, d_cnt;
+    DevBuf<uint32_t> d_xlist, d_xcnt;        // refit: crossing nodes per workgroup
+    DevBuf<uint32_t> d_qlate;                // BuildArgs::qlate
+    DevBuf<unsigned long long> d_ovf;        // stack overflows + guard trips of every trace (never reset)
+    Pinned<unsigned long long> h_ovf;        // pinned: a snapshot of *d_ovf copied at the end of each trace,
                                              //   one word per slot; ovf_seen: the value last reported
     unsigned long long ovf_seen = 0;
-    float* d_bounds = nullptr;
-    float* d_rootbox = nullptr;
-    float* d_zpart = nullptr;
+    DevBuf<float> d_bounds, d_rootbox, d_zpart;
     // rtbvh_compute_bvh: the binned primary pass of the frame starts on `side` once the build's
     // leaves are written (ev_leaf, between k_zrange and k_refit_group) and joins the context stream
     // (ev_prim) before the walk of its overflowed tiles, which reads the whole BVH
-    hipStream_t side = nullptr;
-    hipEvent_t ev_leaf = nullptr, ev_prim = nullptr;
-    bool pseudo_ok = false;      // the built tree has its leaf pseudo-records (read by the packet walks only)
-    // the built tree's node records (the binary and packet walks') and node boxes (a certified trace's
-    // reference-order re-traces): a certified-only context's build writes the boxes alone (records_skipped),
-    // any other build the records alone; the other form is derived on first use (ensure_records / ensure_nbox)
-    bool rec_ok = false, nbox_ok = false;
-    bool build_nbox = false;     // the last build wrote node boxes, not records
-    float* d_nbox = nullptr;     // [6 (T-1)] internal node boxes
-    bool qnode_ok = false;       // the built tree has its QNodes (read by the 4-wide bounce walk only)
+    Event ev_leaf, ev_prim;
+    DevBuf<float> d_nbox;        // [6 (T-1)] internal node boxes
     // rtbvh_compute_bvh: the build leaves its crossing nodes (launch_refit_tail) to the frame's binned
     // pass, which runs them in its bin launches (launch_pb_bin_tail); any other first use of the tree
-    // runs them first (flush_tail)
+    // runs them first (flush_tail).  The two *_pending are the build's hand-off to the trace, reset with `tree`
     bool tail_want = false, tail_pending = false;
     bool leaf_want = false;      // the next build records ev_leaf
     bool leaf_pending = false;   // ev_leaf recorded and nothing enqueued on the stream since
@@ -91,40 +142,35 @@ struct rtbvh_ctx {
     // trace buffers (capacity cap_P pixels)
     size_t cap_P = 0;
     uint32_t W = 0, H = 0, bounces = 0, rank = 0, nranks = 1;
-    float4* d_color = nullptr;
-    float* d_intensity = nullptr;
-    RayQ* d_q[2] = {nullptr, nullptr};
-    uint32_t *d_bkin = nullptr, *d_bvin = nullptr, *d_bka = nullptr, *d_bva = nullptr, *d_bkb = nullptr,
-             *d_bvb = nullptr, *d_bscratch = nullptr;   // bounce coherence sort
-    uint32_t* d_qcount = nullptr;             // [32 x MAXSPLIT]: per pipeline, queue counts [0..15] and
+    DevBuf<float4> d_color;
+    DevBuf<float> d_intensity;
+    DevBuf<RayQ> d_q[2];
+    DevBuf<uint32_t> d_bkin, d_bvin, d_bka, d_bva, d_bkb, d_bvb, d_bscratch;   // bounce coherence sort
+    DevBuf<uint32_t> d_qcount;                // [32 x MAXSPLIT]: per pipeline, queue counts [0..15] and
                                               //   bounce work counters [16..31]
-    float2* d_hit = nullptr;                  // per queued bounce ray: (t, leaf | INVALID)
-    uint32_t* d_next = nullptr;               // [NEXT_WORDS x MAXSPLIT]: segmented bounce work counters
+    DevBuf<float2> d_hit;                     // per queued bounce ray: (t, leaf | INVALID)
+    DevBuf<uint32_t> d_next;                  // [NEXT_WORDS x MAXSPLIT]: segmented bounce work counters
     // pipelines 1.. of a split trace (pipeline 0 = d_q / d_hit on the context stream): a
     // rank's bands dealt over `nsplit` independent primary -> bounce chains on their own
     // streams, so one chain's kernel tail overlaps the others' work
-#ifndef RTBVH_MAXSPLIT
-#define RTBVH_MAXSPLIT 4
-#endif
     static constexpr uint32_t MAXSPLIT = RTBVH_MAXSPLIT;   // buffer sets: the context stream's + caller-stream slots
-    RayQ* d_qs[MAXSPLIT][2] = {};
-    float2* d_hits[MAXSPLIT] = {};
+    DevBuf<RayQ> d_qs[MAXSPLIT][2];
+    DevBuf<float2> d_hits[MAXSPLIT];
     size_t cap_split = 0;                     // rays per pipeline queue
-    hipStream_t sub[MAXSPLIT] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAXSPLIT] = {};
+    Event ev_fork, ev_join[MAXSPLIT];
     uint32_t nsplit = 1;                      // pipelines of the last trace
     // RTBVH_FLAG_BINNED_PRIMARY, per buffer set (chain / frames-in-flight slot): leaf footprints,
     // tile counts / offsets, fill cursors and the bins (trace.hip k_pb_bin)
     struct PbBufs {
-        uint32_t *off = nullptr, *cur = nullptr, *sums = nullptr;
-        uint4* bins = nullptr;
-        unsigned long long* keys = nullptr;
+        DevBuf<uint32_t> off, cur, sums;
+        DevBuf<uint4> bins;
+        DevBuf<unsigned long long> keys;
         uint32_t cap_T = 0, cap_tiles = 0, cap_bins = 0;
         size_t cap_px = 0;
-        uint32_t* list = nullptr;   // N > 1: the rank's leaves (TraceArgs::pb_list)
+        DevBuf<uint32_t> list;      // N > 1: the rank's leaves (TraceArgs::pb_list)
         size_t cap_list = 0;
     } pb[MAXSPLIT];
-    unsigned long long* d_counters = nullptr; // [64]: see rtbvh_get_stats
+    DevBuf<unsigned long long> d_counters;    // [64]: see rtbvh_get_stats
     bool traced = false;
     bool frame_here = false;                 // d_color holds the last trace's whole frame
     bool intensity_here = false;             // d_intensity holds its intensities
@@ -132,17 +178,18 @@ struct rtbvh_ctx {
     // hipEvent rings: per build 6 events (before bounds, after bounds/morton/sort/karras/refit),
     // per trace 3 (before primary, after primary, after bounces)
     static constexpr int RING = 32;
-    hipEvent_t evb[RING][6] = {};
-    hipEvent_t evt[RING][5] = {};   // trace start, primary done, end, first bounce traversal start/end
+    Event evb[RING][6];
+    Event evt[RING][5];             // trace start, primary done, end, first bounce traversal start/end
     bool evt_trav[RING] = {};
     uint32_t n_builds = 0, n_traces = 0;   // timed samples since reset
     // Frames in flight (rtbvh_trace_band_async on a caller stream other than the context's):
     // such a stream gets a trace-buffer set of its own -- slot k >= 1: d_qs[k], d_hits[k],
     // the queue counts at d_qcount + 32k and the counters at d_counters + 64k -- so traces on
     // different streams run concurrently over the one BVH.  They wait only for the last
-    // build (ev_built); the next build waits for them (ev_slot).
-    hipStream_t slot_stream[MAXSPLIT] = {};
-    hipEvent_t ev_built = nullptr, ev_slot[MAXSPLIT] = {};
+    // build (ev_built: the tree and every form marked valid in `tree` are complete, order_after_context); the
+    // next build waits for them (ev_slot).
+    hipStream_t slot_stream[MAXSPLIT] = {};   // (the callers' streams)
+    Event ev_built, ev_slot[MAXSPLIT];
     bool slot_busy[MAXSPLIT] = {};
     uint32_t last_slot = 0;   // slot of the last trace (its counters are the stats)
     bool slots_used = false;  // a foreign-stream slot was used: trace chains are off
@@ -159,11 +206,12 @@ struct rtbvh_ctx {
         uint32_t walk, walk_state;
         bool cert;
     } graph_state{};
+    Tree graph_tree;          // ... and the tree that frame leaves (its build's, with the forms its trace derived)
     // RTBVH_FLAG_AUTO_WALK above AUTO_WALK_MAX_TRIS: the certified fast walks: per buffer
     // set, the list of rays a pass re-traces in the reference order (their counts: d_qcount 16..31)
-    uint32_t* d_redo[MAXSPLIT] = {};
+    DevBuf<uint32_t> d_redo[MAXSPLIT];
     size_t cap_redo[MAXSPLIT] = {};
-    uint32_t* d_defer[MAXSPLIT] = {};   // the certified bounce walk's deferred rays (trace.hip DEFER_*), kept clean
+    DevBuf<uint32_t> d_defer[MAXSPLIT]; // the certified bounce walk's deferred rays (trace.hip DEFER_*), kept clean
     size_t cap_defer[MAXSPLIT] = {};
     uint64_t cert_traces = 0;                         // certified traces so far
     uint32_t last_walk = 0;                           // walk flags of the last trace
@@ -173,7 +221,7 @@ struct rtbvh_ctx {
     uint64_t small_key = 0;
     uint32_t small_flags = 0;     // the flags the small-scene primary kind was timed under
     bool small_packet = false;
-    hipEvent_t ev_small[2] = {};  // its timing events (created on first use, destroyed with the context)
+    Event ev_small[2];            // its timing events (created on first use)
     bool last_cert = false;                           // the last trace was certified (its re-trace counts)
     // tuning knobs of A/B runs, read once by rtbvh_create (RTBVH_BOUNCE_BLOCKS, RTBVH_OVERLAP,
     // RTBVH_SIDE_PRIORITY): a shipped context does not change its launches per frame
@@ -184,21 +232,21 @@ struct rtbvh_ctx {
     uint32_t root_share = 16;
     struct DealTab {   // a weighted deal's device table: every rank's bands, then slots[b] = r << 24 | pos
         uint32_t H, nranks, share;
-        uint32_t* d;
+        DevBuf<uint32_t> d;
         std::vector<uint32_t> off;   // rank r's bands at d[off[r] .. off[r + 1])
-        uint32_t* h;                 // its pinned staging copy (the upload is asynchronous; freed with d)
-        hipEvent_t ready;            // recorded after the upload on the context stream
+        Pinned<uint32_t> h;          // its pinned staging copy (the upload is asynchronous; freed with d)
+        Event ready;                 // recorded after the upload on the context stream
     };
     std::deque<DealTab> deals;       // the MAX_DEALS most recently used (H, nranks, share), most recent first
     static constexpr size_t MAX_DEALS = 8;
     // Ray queries (rtbvh_query_async), on any stream.  They share one scratch block (the walk's work counters and
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
-    uint32_t* d_qscratch = nullptr;          // [QUERY_SCRATCH_WORDS]
-    uint32_t* d_qsort = nullptr;             // RTBVH_QUERY_SORT: 6 arrays of cap_qsort words (keys and values: in,
-    uint32_t* d_qsort_scratch = nullptr;     //   A, B), and the sort's digit counts; grown on demand
+    DevBuf<uint32_t> d_qscratch;             // [QUERY_SCRATCH_WORDS]
+    DevBuf<uint32_t> d_qsort;                // RTBVH_QUERY_SORT: 6 arrays of cap_qsort words (keys and values: in,
+    DevBuf<uint32_t> d_qsort_scratch;        //   A, B), and the sort's digit counts; grown on demand
     size_t cap_qsort = 0;
-    hipEvent_t ev_query = nullptr;
+    Event ev_query;
     bool query_busy = false;
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
     bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
@@ -222,19 +270,6 @@ rtbvh_status fail(rtbvh_ctx* c, rtbvh_status st, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(_e));                      \
     } while (0)
 
-template <typename T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-template <typename T>
-hipError_t dalloc(T*& p, size_t count) {
-    dfree(p);
-    if (count == 0) count = 1;
-    return hipMalloc((void**)&p, count * sizeof(T));
-}
-
 // A captured frame (RTBVH_FLAG_GRAPH) holds the device pointers of capture time: every
 // reallocation below drops it, so a replay never writes to a freed buffer.
 void drop_graph(rtbvh_ctx* c) {
@@ -244,34 +279,92 @@ void drop_graph(rtbvh_ctx* c) {
     c->graph = nullptr;
 }
 
+// No tree: the buffers of the built one are about to be rewritten (set_scene, build_from_codes)
+void reset_tree(rtbvh_ctx* c) {
+    c->tree = Tree{};
+    c->tail_pending = c->leaf_pending = false;
+}
+
+rtbvh_status check_launch(rtbvh_ctx* c, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, RTBVH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return RTBVH_OK;
+}
+
+// ---- stream ordering ---------------------------------------------------------------------------------
+// The frames in flight on caller streams, drained on the host
+rtbvh_status drain_slots(rtbvh_ctx* c) {
+    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
+        if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+    return RTBVH_OK;
+}
+// ... with the context stream and the ray queries: the one host drain
+rtbvh_status sync_all(rtbvh_ctx* c) {
+    HIPC(c, hipStreamSynchronize(c->stream));
+    rtbvh_status st = drain_slots(c);
+    if (st) return st;
+    if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
+    return RTBVH_OK;
+}
+
+// The next writer of what the frames in flight read (a build: the BVH; a camera upload) on stream s waits for them
+rtbvh_status wait_slots(rtbvh_ctx* c, hipStream_t s) {
+    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
+        if (c->slot_busy[k]) {
+            HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
+            c->slot_busy[k] = false;
+        }
+    return RTBVH_OK;
+}
+
+// The next writer of the BVH on stream s (a build) waits for the outstanding ray queries, which read it.  (Never
+// inside a capture: rtbvh_compute_bvh's plain frame before it has cleared query_busy.)
+rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
+    if (c->query_busy) {
+        HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+        c->query_busy = false;
+    }
+    return RTBVH_OK;
+}
+
+// Stream s is ordered after what the context stream holds now.  ev_built is recorded again every time (not inside
+// a capture, whose nodes are ordered by the capture), so it keeps meaning "the tree and every form marked valid
+// are complete" for every later caller stream, which waits for it alone (rtbvh_trace_band_async).
+rtbvh_status order_after_context(rtbvh_ctx* c, hipStream_t s) {
+    if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    return RTBVH_OK;
+}
+
 rtbvh_status ensure_build_capacity(rtbvh_ctx* c, uint32_t T) {
     if (T <= c->cap_T && c->d_codes) return RTBVH_OK;
     drop_graph(c);
+    reset_tree(c);   // (its buffers go)
     const size_t n = T, ni = T > 1 ? T - 1 : 1;
-    HIPC(c, dalloc(c->d_codes, n));
-    HIPC(c, dalloc(c->d_ids, n));
-    HIPC(c, dalloc(c->d_ka, n));
-    HIPC(c, dalloc(c->d_va, n));
-    HIPC(c, dalloc(c->d_kb, n));
-    HIPC(c, dalloc(c->d_vb, n));
-    HIPC(c, dalloc(c->d_sort_scratch, sort_scratch_words(T)));
-    HIPC(c, dalloc(c->d_tclip, TCS * n));
-    HIPC(c, dalloc(c->d_leaf, 4 * n));
-    HIPC(c, dalloc(c->d_inner, ni));
-    HIPC(c, dalloc(c->d_topo, ni));
-    HIPC(c, dalloc(c->d_rec, 2 * (size_t)n - 1));
-    HIPC(c, dalloc(c->d_nbox, 6 * (size_t)ni));
-    HIPC(c, dalloc(c->d_qnode, 2 * (size_t)n - 1));
-    HIPC(c, dalloc(c->d_lfp, n));
-    HIPC(c, dalloc(c->d_pleaf, n));
-    HIPC(c, dalloc(c->d_pint, ni));
-    HIPC(c, dalloc(c->d_cnt, ni));
-    HIPC(c, dalloc(c->d_xlist, n));
-    HIPC(c, dalloc(c->d_qlate, n + 1));
-    HIPC(c, dalloc(c->d_xcnt, refit_blocks(T)));
-    HIPC(c, dalloc(c->d_zpart, ZPART * (size_t)refit_blocks(T)));
-    HIPC(c, dalloc(c->d_bounds, BOUNDS_WORDS));
-    HIPC(c, dalloc(c->d_rootbox, ROOTBOX_WORDS));
+    HIPC(c, c->d_codes.alloc(n));
+    HIPC(c, c->d_ids.alloc(n));
+    HIPC(c, c->d_ka.alloc(n));
+    HIPC(c, c->d_va.alloc(n));
+    HIPC(c, c->d_kb.alloc(n));
+    HIPC(c, c->d_vb.alloc(n));
+    HIPC(c, c->d_sort_scratch.alloc(sort_scratch_words(T)));
+    HIPC(c, c->d_tclip.alloc(TCS * n));
+    HIPC(c, c->d_leaf.alloc(4 * n));
+    HIPC(c, c->d_inner.alloc(ni));
+    HIPC(c, c->d_topo.alloc(ni));
+    HIPC(c, c->d_rec.alloc(2 * (size_t)n - 1));
+    HIPC(c, c->d_nbox.alloc(6 * (size_t)ni));
+    HIPC(c, c->d_qnode.alloc(2 * (size_t)n - 1));
+    HIPC(c, c->d_lfp.alloc(n));
+    HIPC(c, c->d_pleaf.alloc(n));
+    HIPC(c, c->d_pint.alloc(ni));
+    HIPC(c, c->d_cnt.alloc(ni));
+    HIPC(c, c->d_xlist.alloc(n));
+    HIPC(c, c->d_qlate.alloc(n + 1));
+    HIPC(c, c->d_xcnt.alloc(refit_blocks(T)));
+    HIPC(c, c->d_zpart.alloc(ZPART * (size_t)refit_blocks(T)));
+    HIPC(c, c->d_bounds.alloc(BOUNDS_WORDS));
+    HIPC(c, c->d_rootbox.alloc(ROOTBOX_WORDS));
     c->cap_T = T;
     return RTBVH_OK;
 }
@@ -279,29 +372,28 @@ rtbvh_status ensure_build_capacity(rtbvh_ctx* c, uint32_t T) {
 rtbvh_status ensure_trace_capacity(rtbvh_ctx* c, size_t P) {
     if (P <= c->cap_P && c->d_color) return RTBVH_OK;
     drop_graph(c);
-    HIPC(c, dalloc(c->d_color, P));
-    HIPC(c, dalloc(c->d_intensity, P));
-    HIPC(c, dalloc(c->d_q[0], P));
-    HIPC(c, dalloc(c->d_q[1], P));
-    HIPC(c, dalloc(c->d_bkin, P));
-    HIPC(c, dalloc(c->d_bvin, P));
-    HIPC(c, dalloc(c->d_bka, P));
-    HIPC(c, dalloc(c->d_bva, P));
-    HIPC(c, dalloc(c->d_bkb, P));
-    HIPC(c, dalloc(c->d_bvb, P));
-    HIPC(c, dalloc(c->d_bscratch, sort_scratch_words((uint32_t)P)));
-    HIPC(c, dalloc(c->d_hit, P));
-    if (!c->d_qcount) HIPC(c, dalloc(c->d_qcount, 32 * rtbvh_ctx::MAXSPLIT));
-    if (!c->d_next) HIPC(c, dalloc(c->d_next, (size_t)NEXT_WORDS * rtbvh_ctx::MAXSPLIT));
-    if (!c->d_counters) HIPC(c, dalloc(c->d_counters, 64 * rtbvh_ctx::MAXSPLIT));
+    HIPC(c, c->d_color.alloc(P));
+    HIPC(c, c->d_intensity.alloc(P));
+    HIPC(c, c->d_q[0].alloc(P));
+    HIPC(c, c->d_q[1].alloc(P));
+    HIPC(c, c->d_bkin.alloc(P));
+    HIPC(c, c->d_bvin.alloc(P));
+    HIPC(c, c->d_bka.alloc(P));
+    HIPC(c, c->d_bva.alloc(P));
+    HIPC(c, c->d_bkb.alloc(P));
+    HIPC(c, c->d_bvb.alloc(P));
+    HIPC(c, c->d_bscratch.alloc(sort_scratch_words((uint32_t)P)));
+    HIPC(c, c->d_hit.alloc(P));
+    if (!c->d_qcount) HIPC(c, c->d_qcount.alloc(32 * rtbvh_ctx::MAXSPLIT));
+    if (!c->d_next) HIPC(c, c->d_next.alloc((size_t)NEXT_WORDS * rtbvh_ctx::MAXSPLIT));
+    if (!c->d_counters) HIPC(c, c->d_counters.alloc(64 * rtbvh_ctx::MAXSPLIT));
     c->cap_P = P;
     return RTBVH_OK;
 }
 
 // chains of a trace (enqueue_trace): RTBVH_FLAG_SPLIT_SHIFT bits, 0 = automatic
-uint32_t trace_split(const rtbvh_ctx* c, size_t pixels) {
+uint32_t trace_split(const rtbvh_ctx* c) {
     const uint32_t v = (c->cfg.flags >> RTBVH_FLAG_SPLIT_SHIFT) & 7u;
-    (void)pixels;
     if (v) return v < rtbvh_ctx::MAXSPLIT ? v : rtbvh_ctx::MAXSPLIT;
     return 1;
 }
@@ -311,21 +403,21 @@ rtbvh_status ensure_split_capacity(rtbvh_ctx* c, uint32_t nsplit, size_t rays) {
     const bool grow = rays > c->cap_split;
     if (grow) {
         drop_graph(c);   // every chain's queues hold cap_split rays: drop the smaller ones
-        for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)   // (after any frame in flight on them)
-            if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+        rtbvh_status st = drain_slots(c);   // (after any frame in flight on them)
+        if (st) return st;
         c->cap_split = rays;
         for (uint32_t g = nsplit; g < rtbvh_ctx::MAXSPLIT; g++) {
-            dfree(c->d_qs[g][0]); dfree(c->d_qs[g][1]); dfree(c->d_hits[g]);
+            c->d_qs[g][0].reset(); c->d_qs[g][1].reset(); c->d_hits[g].reset();
         }
     }
     for (uint32_t g = 1; g < nsplit; g++) {
-        if (!c->sub[g]) HIPC(c, hipStreamCreateWithFlags(&c->sub[g], hipStreamNonBlocking));
-        if (!c->ev_join[g]) HIPC(c, hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
-        if (!c->ev_fork) HIPC(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        if (!c->sub[g]) HIPC(c, hipStreamCreateWithFlags(c->sub[g].out(), hipStreamNonBlocking));
+        if (!c->ev_join[g]) HIPC(c, hipEventCreateWithFlags(c->ev_join[g].out(), hipEventDisableTiming));
+        if (!c->ev_fork) HIPC(c, hipEventCreateWithFlags(c->ev_fork.out(), hipEventDisableTiming));
         if (c->d_qs[g][0] && !grow) continue;
-        HIPC(c, dalloc(c->d_qs[g][0], c->cap_split));
-        HIPC(c, dalloc(c->d_qs[g][1], c->cap_split));
-        HIPC(c, dalloc(c->d_hits[g], c->cap_split));
+        HIPC(c, c->d_qs[g][0].alloc(c->cap_split));
+        HIPC(c, c->d_qs[g][1].alloc(c->cap_split));
+        HIPC(c, c->d_hits[g].alloc(c->cap_split));
     }
     return RTBVH_OK;
 }
@@ -340,15 +432,15 @@ rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t t
     if (T <= p.cap_T && tiles <= p.cap_tiles && bins <= p.cap_bins && pixels <= p.cap_px && p.off) return RTBVH_OK;
     drop_graph(c);
     if (pixels > p.cap_px) {
-        HIPC(c, dalloc(p.keys, pixels));
+        HIPC(c, p.keys.alloc(pixels));
         p.cap_px = pixels;
     }
     const uint32_t nT = std::max(T, p.cap_T), nt = std::max(tiles, p.cap_tiles);
     const uint32_t nb = std::max(BINS_PER_LEAF * nT + 16 * nt, p.cap_bins);
-    HIPC(c, dalloc(p.off, (size_t)nt * PB_NZ + 1));
-    HIPC(c, dalloc(p.cur, (size_t)nt * PB_NZ));
-    HIPC(c, dalloc(p.sums, (size_t)nt * PB_NZ / 1024 + 1));
-    HIPC(c, dalloc(p.bins, nb));
+    HIPC(c, p.off.alloc((size_t)nt * PB_NZ + 1));
+    HIPC(c, p.cur.alloc((size_t)nt * PB_NZ));
+    HIPC(c, p.sums.alloc((size_t)nt * PB_NZ / 1024 + 1));
+    HIPC(c, p.bins.alloc(nb));
     p.cap_T = nT;
     p.cap_tiles = nt;
     p.cap_bins = nb;
@@ -394,8 +486,9 @@ BuildArgs build_args(rtbvh_ctx* c) {
     a.pseudo = (f & RTBVH_FLAG_PACKET_PRIMARY) &&
                !(f & (RTBVH_FLAG_BINNED_PRIMARY | RTBVH_FLAG_AUTO_WALK | RTBVH_FLAG_CERTIFIED));
     // the last build's outputs: node records, or (a certified-only context's) node boxes instead
-    a.rec_on = c->build_nbox ? 0u : 1u;
-    a.nbox = c->build_nbox ? c->d_nbox : nullptr;
+    const bool boxes = c->tree.wrote == NBOX;
+    a.rec_on = boxes ? 0u : 1u;
+    a.nbox = boxes ? c->d_nbox.h : nullptr;
     return a;
 }
 // the same, with the node-box array for a kernel that reads (or writes) it
@@ -448,20 +541,12 @@ uint32_t deal_max_rows(uint32_t H, uint32_t nranks, uint32_t share) {
     for (uint32_t r = 0; r < nranks; r++) m = std::max(m, deal_rows(H, r, nranks, share));
     return m;
 }
-rtbvh_status sync_all(rtbvh_ctx* c);
 // The device table of a weighted deal (null for round-robin: the kernels compute it).  Uploaded on
 // first use (a few KB, once per frame size and deal), so not from inside a graph capture (whose frames
 // have one rank): an asynchronous copy from pinned staging on the context stream, and an event the
 // caller's stream `s` waits for (a trace on a caller stream, an assembly on another).  The MAX_DEALS
 // most recently used tables are kept; evicting one first waits for the context's work (traces in
 // flight may read it).
-void free_deal(rtbvh_ctx::DealTab& t) {
-    dfree(t.d);
-    if (t.h) (void)hipHostFree(t.h);
-    if (t.ready) (void)hipEventDestroy(t.ready);
-    t.h = nullptr;
-    t.ready = nullptr;
-}
 rtbvh_status get_deal(rtbvh_ctx* c, uint32_t H, uint32_t nranks, const rtbvh_ctx::DealTab** out, hipStream_t s) {
     *out = nullptr;
     if (c->root_share == 16 || nranks <= 1) return RTBVH_OK;
@@ -480,21 +565,17 @@ rtbvh_status get_deal(rtbvh_ctx* c, uint32_t H, uint32_t nranks, const rtbvh_ctx
     if (c->deals.size() >= rtbvh_ctx::MAX_DEALS) {
         rtbvh_status st = sync_all(c);
         if (st) return st;
-        free_deal(c->deals.back());
         c->deals.pop_back();
     }
     std::vector<uint32_t> owner;
     deal_owners(H, nranks, c->root_share, owner);
     const uint32_t nb = (uint32_t)owner.size();
-    rtbvh_ctx::DealTab t{H, nranks, c->root_share, nullptr, std::vector<uint32_t>(nranks + 1, 0), nullptr, nullptr};
+    rtbvh_ctx::DealTab t{H, nranks, c->root_share, {}, std::vector<uint32_t>(nranks + 1, 0), {}, {}};
     const size_t words = 2 * (size_t)nb + 1;
     std::vector<uint32_t> cnt(nranks, 0);
-    if (hipHostMalloc((void**)&t.h, words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&t.d, words * sizeof(uint32_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&t.ready, hipEventDisableTiming) != hipSuccess) {
-        free_deal(t);
+    if (t.h.alloc(words) != hipSuccess || t.d.alloc(words) != hipSuccess ||
+        hipEventCreateWithFlags(t.ready.out(), hipEventDisableTiming) != hipSuccess)
         return fail(c, RTBVH_ERR_OOM, "band deal table");
-    }
     for (uint32_t b = 0; b < nb; b++) t.off[owner[b] + 1]++;
     for (uint32_t r = 0; r < nranks; r++) t.off[r + 1] += t.off[r];
     t.h[2 * nb] = 0;
@@ -551,7 +632,7 @@ TraceArgs trace_args(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t rank, uint32
     a.stack_limit4 = lim && lim < (uint32_t)STACK4 ? (int)lim : STACK4;
     a.stack_limit4b = lim && lim < (uint32_t)STACK4B ? (int)lim : STACK4B;
     a.limited = lim != 0 && lim < (uint32_t)STACK4B;
-    a.acyclic = c->built_clz64;
+    a.acyclic = c->tree.clz64;
     return a;
 }
 
@@ -571,20 +652,8 @@ bool auto_checked(const rtbvh_ctx* c) {
 // (leaf footprints and records), the certified 4-wide bounce walk (QNodes; a node without a grid flags the ray),
 // and reference-order re-traces of the few flagged rays on the topology and node boxes (trace.hip traverse_nb).
 // Its multi-kernel build writes the 24-B node boxes instead of the 64-B node records (C4
-// refit stage 0.94 -> 0.81 ms without them); records are derived if another walk needs them (ensure_records).
+// refit stage 0.94 -> 0.81 ms without them); records are derived if another walk needs them (ensure_form).
 // RTBVH_KEEP_RECORDS=1 (A/B): write the records anyway.
-bool records_skipped(const rtbvh_ctx* c);
-rtbvh_status ensure_records(rtbvh_ctx* c, hipStream_t s) {
-    if (c->rec_ok || !c->built) return RTBVH_OK;
-    launch_records(build_args_nbox(c), c->stream);
-    HIPC(c, hipGetLastError());
-    c->rec_ok = true;
-    if (s != c->stream) {
-        if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-        HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    }
-    return RTBVH_OK;
-}
 bool records_skipped(const rtbvh_ctx* c) {
     const uint32_t f = c->cfg.flags;
     const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
@@ -592,18 +661,23 @@ bool records_skipped(const rtbvh_ctx* c) {
     return !small && !c->knob_keep_records && ((f & RTBVH_FLAG_CERTIFIED) || auto_checked(c)) &&
            c->cfg.delta_mode == RTBVH_DELTA_CLZ64 && !limited;
 }
-rtbvh_status ensure_nbox(rtbvh_ctx* c, hipStream_t s) {
-    if (c->nbox_ok || !c->built) return RTBVH_OK;
-    BuildArgs a = build_args_nbox(c);
-    a.rec_on = 1;
-    launch_nbox(a, c->stream);
-    HIPC(c, hipGetLastError());
-    c->nbox_ok = true;
-    if (s != c->stream) {
-        if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-        HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+// A form of the built tree that the build did not write, derived on first use from the complete tree: on the
+// context stream (no walk of a slot stream reads what the kernels write), with stream s ordered behind it.
+// The node records come from the topology and node boxes, the boxes from the records (a build writes one of the
+// two); the leaf pseudo-records and the QNodes only when the context's walks at the build read none.
+rtbvh_status ensure_form(rtbvh_ctx* c, Form form, hipStream_t s) {
+    if ((c->tree.valid & form) || !c->tree.built) return RTBVH_OK;
+    BuildArgs a = form == RECORDS || form == NBOX ? build_args_nbox(c) : build_args(c);
+    if (form == RECORDS) launch_records(a, c->stream);
+    if (form == NBOX) {
+        a.rec_on = 1;
+        launch_nbox(a, c->stream);
     }
-    return RTBVH_OK;
+    if (form == PSEUDO) launch_pseudo(a, c->stream);
+    if (form == QNODES) launch_qnodes(a, c->stream);
+    HIPC(c, hipGetLastError());
+    c->tree.valid |= form;
+    return order_after_context(c, s);
 }
 struct Walks {
     PrimaryKind primary;
@@ -671,31 +745,6 @@ const Rccl& rccl() {
     return lib;
 }
 
-rtbvh_status check_launch(rtbvh_ctx* c, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, RTBVH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return RTBVH_OK;
-}
-
-// the context stream and the frames in flight on caller streams, drained
-rtbvh_status sync_all(rtbvh_ctx* c) {
-    HIPC(c, hipStreamSynchronize(c->stream));
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
-    if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
-    return RTBVH_OK;
-}
-
-// The next writer of the BVH on stream s (a build) waits for the outstanding ray queries, which read it.  (Never
-// inside a capture: rtbvh_compute_bvh's plain frame before it has cleared query_busy.)
-rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
-    if (c->query_busy) {
-        HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-        c->query_busy = false;
-    }
-    return RTBVH_OK;
-}
-
 // The camera the kernels read (BuildArgs::cam), uploaded in stream order on the context stream when
 // rtbvh_set_camera changed it -- after the frames in flight, which read the old one -- and ordered
 // before stream s.  A captured frame (RTBVH_FLAG_GRAPH) reads the buffer, so it survives a camera change
@@ -706,19 +755,12 @@ rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
 // camera in.
 rtbvh_status sync_camera(rtbvh_ctx* c, hipStream_t s) {
     if (!c->cam_dirty) return RTBVH_OK;
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) {
-            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_slot[k], 0));
-            c->slot_busy[k] = false;
-        }
+    rtbvh_status st = wait_slots(c, c->stream);
+    if (st) return st;
     launch_set_camera(c->wvp, c->wv, c->d_cam, c->stream);
     HIPC(c, hipGetLastError());
-    if (s != c->stream) {
-        HIPC(c, hipEventRecord(c->ev_built, c->stream));
-        HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    }
     c->cam_dirty = false;
-    return RTBVH_OK;
+    return order_after_context(c, s);
 }
 
 // The kernels of one trace with the walks of `flags` (timed: record the stage events when
@@ -742,7 +784,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         ~TailGuard() { run(); }
     } tail{c, c->tail_pending};
     c->tail_pending = false;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
     if (W == 0 || H == 0 || nranks == 0 || rank >= nranks || bounces > 14)
         return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
     rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
@@ -760,7 +802,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         a.band_slots = deal->d + (H + 7) / 8;
     }
     a.counters = c->d_counters + 64 * slot;
-    hipEvent_t* ev = c->evt[c->n_traces % rtbvh_ctx::RING];
+    Event* ev = c->evt[c->n_traces % rtbvh_ctx::RING];
     const Walks wk = choose_walks(flags);
     const bool sort = wk.sort, refill = wk.refill;
     const bool records = (flags & RTBVH_FLAG_REFRACT_RECORDS) != 0;
@@ -786,8 +828,8 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     if (records) {
         if (c->cap_rec < P) {
             drop_graph(c);
-            HIPC(c, dalloc(c->d_refl_rec, 14 * (size_t)P));
-            HIPC(c, dalloc(c->d_refr_rec, 14 * (size_t)P));
+            HIPC(c, c->d_refl_rec.alloc(14 * (size_t)P));
+            HIPC(c, c->d_refr_rec.alloc(14 * (size_t)P));
             c->cap_rec = P;
         }
         a.refl_rec = c->d_refl_rec;
@@ -798,7 +840,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     // (band k of this rank goes to chain k % nsplit), each with its own queues and work
     // counters, chain 0 on the context stream, chain g on sub[g]; joined before the end event
     const uint32_t my_bands = a.my_bands;
-    uint32_t nsplit = trace_split(c, (size_t)W * 8 * my_bands);
+    uint32_t nsplit = trace_split(c);
     // the coherence sort has one set of buffers; frames-in-flight slots use the chains' buffers
     // the binned primary pass covers the rank's whole frame in one chain; the build's leaf footprints
     // are exact for frames of up to 32768 pixels a side (rtbvh_device.h leaf_footprint)
@@ -811,57 +853,45 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     if (sort || my_bands < nsplit || slot || c->slots_used || binned) nsplit = 1;
     // the walks' node data: a certified trace's re-traces walk the node boxes (a.nb), every other walk the node
     // records; a build writes one of the two, the other is derived here from the complete tree (after the tail)
-    const bool need_conv = cert ? !c->nbox_ok : !c->rec_ok;
+    const Form nodes = cert ? NBOX : RECORDS;
+    const bool need_conv = !(c->tree.valid & nodes);
     const bool fuse_tail = tail.pending && pkind == PrimaryKind::BINNED && s == c->stream && slot == 0 && rows > 0 &&
                            !need_conv;
     if (!fuse_tail && tail.pending) {   // before any walk reads the tree
         tail.run();
-        if (s != c->stream) {   // (a caller stream: ordered after it like after the build)
-            if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-            HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-        }
-    }
-    if (need_conv) {
-        st = cert ? ensure_nbox(c, s) : ensure_records(c, s);
+        st = order_after_context(c, s);   // (a caller stream: ordered after it like after the build)
         if (st) return st;
     }
+    st = ensure_form(c, nodes, s);
+    if (st) return st;
     a.nb = cert;
     const uint32_t Pg = nsplit == 1 ? P : W * 8 * ((my_bands + nsplit - 1) / nsplit);   // max live rays per chain
     st = ensure_split_capacity(c, slot ? slot + 1 : nsplit, Pg);
     if (st) return st;
-    if (!c->qnode_ok && bounces > 0 && wk.refill && wk.bounce == BounceWalk::WIDE_QUANTIZED) {
-        // a 4-wide bounce walk over a one-workgroup build that quantized no nodes (the context's
-        // walks took none): k_qnodes now, as for the pseudo-records below
-        launch_qnodes(build_args(c), c->stream);
-        c->qnode_ok = true;
-        if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-        if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    // a 4-wide bounce walk over a one-workgroup build that quantized no nodes (the context's walks took none)
+    if (bounces > 0 && wk.refill && wk.bounce == BounceWalk::WIDE_QUANTIZED) {
+        st = ensure_form(c, QNODES, s);
+        if (st) return st;
     }
-    if (!c->pseudo_ok && (pkind == PrimaryKind::PACKET_REFERENCE || pkind == PrimaryKind::PACKET_NEAREST ||
-                          pkind == PrimaryKind::PACKET_WIDE)) {
-        // a packet walk over a tree built without the leaf pseudo-records (the context's walks took
-        // none; set_flags since, or a frame past the binned pass's 32768 pixels a side): written now,
-        // on the context stream (no walk of a slot stream reads those slots)
-        launch_pseudo(build_args(c), c->stream);
-        c->pseudo_ok = true;
-        if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-        if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    // a packet walk over a tree built without the leaf pseudo-records (the context's walks took none;
+    // set_flags since, or a frame past the binned pass's 32768 pixels a side)
+    if (pkind == PrimaryKind::PACKET_REFERENCE || pkind == PrimaryKind::PACKET_NEAREST ||
+        pkind == PrimaryKind::PACKET_WIDE) {
+        st = ensure_form(c, PSEUDO, s);
+        if (st) return st;
     }
     // a certified trace's re-trace list (one chain: buffer set `slot`; counts at d_qcount 16 + pass)
     if (cert && bounces > 0 && c->cap_defer[slot] < P) {   // (zeroed once: its readers clear what they take)
         drop_graph(c);
-        dfree(c->d_defer[slot]);
-        HIPC(c, dalloc(c->d_defer[slot], P));
+        HIPC(c, c->d_defer[slot].alloc(P));
         HIPC(c, hipMemsetAsync(c->d_defer[slot], 0, sizeof(uint32_t) * P, c->stream));
-        if (s != c->stream) {
-            if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, c->stream));
-            HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-        }
+        st = order_after_context(c, s);
+        if (st) return st;
         c->cap_defer[slot] = P;
     }
     if (cert && c->cap_redo[slot] < P) {
         drop_graph(c);
-        HIPC(c, dalloc(c->d_redo[slot], P));
+        HIPC(c, c->d_redo[slot].alloc(P));
         c->cap_redo[slot] = P;
     }
     // the binned pass's buffers (one chain: buffer set `slot`)
@@ -871,7 +901,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         if (st) return st;
         if (nranks > 1 && c->pb[slot].cap_list < pb_list_words(c->T)) {
             drop_graph(c);
-            HIPC(c, dalloc(c->pb[slot].list, pb_list_words(c->T)));
+            HIPC(c, c->pb[slot].list.alloc(pb_list_words(c->T)));
             c->pb[slot].cap_list = pb_list_words(c->T);
         }
     }
@@ -1018,7 +1048,7 @@ TracePlan plan_trace(const rtbvh_ctx* c, uint32_t f) {
     // stack limit makes the reference order end rays early, which no fast walk reproduces)
     const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
     const bool want = (f & RTBVH_FLAG_CERTIFIED) || auto_checked(c);
-    if (!want || !c->built_clz64 || limited) return TracePlan{ref, false, 0};
+    if (!want || !c->tree.clz64 || limited) return TracePlan{ref, false, 0};
     return TracePlan{ref | RTBVH_FLAG_NEAREST_FIRST | RTBVH_FLAG_REFILL_BOUNCE | RTBVH_FLAG_WIDE_BVH |
                          RTBVH_FLAG_BINNED_PRIMARY,
                      true, 2};
@@ -1026,7 +1056,7 @@ TracePlan plan_trace(const rtbvh_ctx* c, uint32_t f) {
 
 rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint32_t rank, uint32_t nranks,
                            float4* color, float* inten, hipStream_t s, uint32_t slot = 0) {
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
     rtbvh_status st = sync_camera(c, s);
     if (st) return st;
     TracePlan p = plan_trace(c, c->cfg.flags);
@@ -1042,16 +1072,16 @@ rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     // differ from a lane's) nor the CPUTests delta.
     const uint32_t f = c->cfg.flags;
     const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
-    if ((f & RTBVH_FLAG_AUTO_WALK) && !p.cert && c->built_clz64 && !limited) {
+    if ((f & RTBVH_FLAG_AUTO_WALK) && !p.cert && c->tree.clz64 && !limited) {
         const uint64_t key = (uint64_t)W << 48 | (uint64_t)H << 32 | c->T;
         // (the first frame of a key is synchronous: it waits for its own timed passes; the key includes the
         // walk flags, so a set_flags that changes the walks times them again)
         const uint32_t fw = f & (WALK_FLAGS | RTBVH_FLAG_AUTO_WALK | RTBVH_FLAG_CERTIFIED | RTBVH_FLAG_SORT_BOUNCE);
         if ((c->small_key != key || c->small_flags != fw) && !c->capturing && s == c->stream && slot == 0 &&
             nranks == 1) {
-            hipEvent_t* ev = c->ev_small;
+            Event* ev = c->ev_small;
             for (int k = 0; k < 2; k++)
-                if (!ev[k]) HIPC(c, hipEventCreate(&ev[k]));
+                if (!ev[k]) HIPC(c, hipEventCreate(ev[k].out()));
             float best[2] = {INFINITY, INFINITY};
             for (int round = 0; round < 2; round++)
                 for (int k = 0; k < 2; k++) {
@@ -1116,34 +1146,32 @@ rtbvh_status rtbvh_create(const rtbvh_config* cfg, rtbvh_ctx** out) {
     if (c->cfg.stream) {
         c->stream = (hipStream_t)c->cfg.stream;
     } else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+        if (hipStreamCreateWithFlags(c->own_stream.out(), hipStreamNonBlocking) != hipSuccess) {
             delete c;
             return fail(nullptr, RTBVH_ERR_HIP, "hipStreamCreate failed");
         }
-        c->own_stream = true;
+        c->stream = c->own_stream;
     }
     bool ev_ok = true;
     for (auto& row : c->evb)
-        for (auto& e : row) ev_ok = ev_ok && hipEventCreate(&e) == hipSuccess;
+        for (auto& e : row) ev_ok = ev_ok && hipEventCreate(e.out()) == hipSuccess;
     for (auto& row : c->evt)
-        for (auto& e : row) ev_ok = ev_ok && hipEventCreate(&e) == hipSuccess;
+        for (auto& e : row) ev_ok = ev_ok && hipEventCreate(e.out()) == hipSuccess;
     if (!ev_ok) {
         rtbvh_destroy(c);
         return fail(nullptr, RTBVH_ERR_HIP, "hipEventCreate failed");
     }
-    if (hipEventCreateWithFlags(&c->ev_built, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(c->ev_built.out(), hipEventDisableTiming) != hipSuccess) {
         rtbvh_destroy(c);
         return fail(nullptr, RTBVH_ERR_HIP, "hipEventCreate failed");
     }
-    if (hipMalloc((void**)&c->d_ovf, sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(c->d_ovf, 0, sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_ovf, sizeof(unsigned long long) * rtbvh_ctx::MAXSPLIT, hipHostMallocDefault) !=
-            hipSuccess) {
+    if (c->d_ovf.alloc(1) != hipSuccess || hipMemset(c->d_ovf, 0, sizeof(unsigned long long)) != hipSuccess ||
+        c->h_ovf.alloc(rtbvh_ctx::MAXSPLIT) != hipSuccess) {
         rtbvh_destroy(c);
         return fail(nullptr, RTBVH_ERR_OOM, "overflow counter allocation failed");
     }
     memset(c->h_ovf, 0, sizeof(unsigned long long) * rtbvh_ctx::MAXSPLIT);
-    if (hipMalloc((void**)&c->d_cam, 32 * sizeof(float)) != hipSuccess ||
+    if (c->d_cam.alloc(32) != hipSuccess ||
         hipMemset(c->d_cam, 0, 32 * sizeof(float)) != hipSuccess) {
         rtbvh_destroy(c);
         return fail(nullptr, RTBVH_ERR_OOM, "camera buffer allocation failed");
@@ -1162,61 +1190,8 @@ rtbvh_status rtbvh_create(const rtbvh_config* cfg, rtbvh_ctx** out) {
 void rtbvh_destroy(rtbvh_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->ev_slot[k]) {
-            (void)hipEventSynchronize(c->ev_slot[k]);   // frames in flight on caller streams
-            (void)hipEventDestroy(c->ev_slot[k]);
-        }
-    if (c->ev_built) (void)hipEventDestroy(c->ev_built);
-    if (c->ev_query) {
-        (void)hipEventSynchronize(c->ev_query);   // ray queries on caller streams
-        (void)hipEventDestroy(c->ev_query);
-    }
-    dfree(c->d_qscratch); dfree(c->d_qsort); dfree(c->d_qsort_scratch);
+    (void)sync_all(c);   // the context stream, then the frames in flight and the ray queries on caller streams
     drop_graph(c);
-    for (uint32_t g = 1; g < rtbvh_ctx::MAXSPLIT; g++) {
-        if (c->sub[g]) {
-            (void)hipStreamSynchronize(c->sub[g]);
-            (void)hipStreamDestroy(c->sub[g]);
-        }
-        if (c->ev_join[g]) (void)hipEventDestroy(c->ev_join[g]);
-        dfree(c->d_qs[g][0]); dfree(c->d_qs[g][1]); dfree(c->d_hits[g]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->side) {
-        (void)hipStreamSynchronize(c->side);
-        (void)hipStreamDestroy(c->side);
-    }
-    for (hipEvent_t e : c->ev_small)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_leaf) (void)hipEventDestroy(c->ev_leaf);
-    if (c->ev_prim) (void)hipEventDestroy(c->ev_prim);
-    for (auto& p : c->pb) { dfree(p.off); dfree(p.cur); dfree(p.bins); dfree(p.sums); dfree(p.keys); }
-    dfree(c->d_opos); dfree(c->d_verts); dfree(c->d_idx); dfree(c->d_matidx); dfree(c->d_mats);
-    dfree(c->d_codes); dfree(c->d_ids); dfree(c->d_ka); dfree(c->d_va); dfree(c->d_kb); dfree(c->d_vb);
-    dfree(c->d_sort_scratch); dfree(c->d_tclip); dfree(c->d_leaf); dfree(c->d_inner); dfree(c->d_topo); dfree(c->d_rec); dfree(c->d_nbox); dfree(c->d_qnode); dfree(c->d_lfp);
-    dfree(c->d_band);
-    dfree(c->d_pleaf); dfree(c->d_pint); dfree(c->d_cnt); dfree(c->d_xlist); dfree(c->d_qlate); dfree(c->d_xcnt); dfree(c->d_bounds); dfree(c->d_rootbox); dfree(c->d_zpart);
-    dfree(c->d_color); dfree(c->d_intensity); dfree(c->d_q[0]); dfree(c->d_q[1]); dfree(c->d_qcount); dfree(c->d_next); dfree(c->d_hit);
-    dfree(c->d_bkin); dfree(c->d_bvin); dfree(c->d_bka); dfree(c->d_bva); dfree(c->d_bkb); dfree(c->d_bvb);
-    dfree(c->d_bscratch); dfree(c->d_refl_rec); dfree(c->d_refr_rec);
-    dfree(c->d_texels); dfree(c->d_texinfo); dfree(c->d_srgb);
-    dfree(c->d_counters);
-    dfree(c->d_ovf);
-    for (auto& r : c->d_redo) dfree(r);
-    for (auto& r : c->d_defer) dfree(r);
-    for (auto& p : c->pb) dfree(p.list);
-    dfree(c->d_cam);
-    for (auto& t : c->deals) free_deal(t);
-    if (c->h_ovf) (void)hipHostFree(c->h_ovf);
-    for (auto& row : c->evb)
-        for (auto& e : row)
-            if (e) (void)hipEventDestroy(e);
-    for (auto& row : c->evt)
-        for (auto& e : row)
-            if (e) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1240,18 +1215,19 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
     for (uint32_t t = 0; t < T; t++)
         if (mat_idx[t] >= nmats) return fail(c, RTBVH_ERR_INVALID_ARG, "set_scene: material index out of range");
     HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (c->ev_query) HIPC(c, hipEventSynchronize(c->ev_query));   // ray queries on caller streams read the old BVH
+    rtbvh_status st = sync_all(c);   // frames in flight and ray queries on caller streams read the old scene and BVH
+    if (st) return st;
     c->query_busy = false;
+    reset_tree(c);
     try {
         std::vector<float4> opos(nverts);
         for (uint32_t i = 0; i < nverts; i++)
             opos[i] = make_float4(verts[i].position[0], verts[i].position[1], verts[i].position[2], 0.f);
-        HIPC(c, dalloc(c->d_opos, nverts));
-        HIPC(c, dalloc(c->d_verts, (size_t)nverts * 8));
-        HIPC(c, dalloc(c->d_idx, nidx));
-        HIPC(c, dalloc(c->d_matidx, T));
-        HIPC(c, dalloc(c->d_mats, nmats));
+        HIPC(c, c->d_opos.alloc(nverts));
+        HIPC(c, c->d_verts.alloc((size_t)nverts * 8));
+        HIPC(c, c->d_idx.alloc(nidx));
+        HIPC(c, c->d_matidx.alloc(T));
+        HIPC(c, c->d_mats.alloc(nmats));
         HIPC(c, hipMemcpy(c->d_opos, opos.data(), sizeof(float4) * nverts, hipMemcpyHostToDevice));
         HIPC(c, hipMemcpy(c->d_verts, verts, sizeof(rtbvh_vertex) * nverts, hipMemcpyHostToDevice));
         HIPC(c, hipMemcpy(c->d_idx, indices, sizeof(uint32_t) * nidx, hipMemcpyHostToDevice));
@@ -1266,8 +1242,8 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
             total += (size_t)textures[k].width * textures[k].height;
         }
         if (total >= (1ull << 32)) return fail(c, RTBVH_ERR_INVALID_ARG, "set_scene: textures too large");
-        HIPC(c, dalloc(c->d_texels, total ? total : 1));
-        HIPC(c, dalloc(c->d_texinfo, info.size()));
+        HIPC(c, c->d_texels.alloc(total ? total : 1));
+        HIPC(c, c->d_texinfo.alloc(info.size()));
         for (uint32_t k = 0; k < ntex; k++)
             HIPC(c, hipMemcpy(c->d_texels + info[k].x, textures[k].rgba8,
                               (size_t)textures[k].width * textures[k].height * 4, hipMemcpyHostToDevice));
@@ -1275,7 +1251,7 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
         if (!c->d_srgb) {
             float tab[256];
             rtbvh_srgb_table(tab);
-            HIPC(c, dalloc(c->d_srgb, 256));
+            HIPC(c, c->d_srgb.alloc(256));
             HIPC(c, hipMemcpy(c->d_srgb, tab, sizeof(tab), hipMemcpyHostToDevice));
         }
         c->ntex = ntex;
@@ -1286,7 +1262,7 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
     c->V = nverts;
     c->T = T;
     c->nmat = nmats;
-    rtbvh_status st = ensure_build_capacity(c, T);
+    st = ensure_build_capacity(c, T);
     if (st) return st;
     if (c->cfg.morton_mode == RTBVH_MORTON_CPUTESTS) {
         // the object-space mesh box the CPUTests Morton codes are normalised by: a property of
@@ -1299,7 +1275,6 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
         HIPC(c, hipStreamSynchronize(c->stream));
     }
     c->have_scene = true;
-    c->built = false;
     c->small_key = 0;   // (the primary kind of a small scene is timed again)
     return RTBVH_OK;
 }
@@ -1325,16 +1300,12 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     hipStream_t s = c->stream;
     const bool timing = (c->cfg.flags & RTBVH_FLAG_TIMING) != 0 && !c->capturing;
     BuildArgs a = build_args(c);
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)   // frames in flight read the old BVH
-        if (c->slot_busy[k]) {
-            HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
-            c->slot_busy[k] = false;
-        }
-    rtbvh_status cst = wait_queries(c, s);   // ... and so do the outstanding ray queries
+    rtbvh_status cst = wait_slots(c, s);   // frames in flight read the old BVH
+    if (!cst) cst = wait_queries(c, s);    // ... and so do the outstanding ray queries
+    if (!cst) cst = sync_camera(c, s);
     if (cst) return cst;
-    cst = sync_camera(c, s);
-    if (cst) return cst;
-    hipEvent_t* ev = c->evb[c->n_builds % rtbvh_ctx::RING];
+    const bool clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
+    Event* ev = c->evb[c->n_builds % rtbvh_ctx::RING];
     if (timing) HIPC(c, hipEventRecord(ev[0], s));
     if (c->T <= small_build_max() && !(c->cfg.flags & RTBVH_FLAG_MULTI_KERNEL_BUILD)) {
         // one workgroup (build.hip k_build_small); its time is reported as stage 0
@@ -1344,30 +1315,23 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
         a.pseudo = 1;   // (the one-workgroup build writes them anyway)
         a.rec_on = 1;   // (and the node records)
         a.nbox = nullptr;
-        c->build_nbox = false;
-        c->rec_ok = true;
-        c->nbox_ok = false;
         launch_build_small(a, s);
         // the QNodes only for walks that read them (the 4-wide bounce walk; enqueue_walks otherwise)
-        c->qnode_ok = (c->cfg.flags & (RTBVH_FLAG_WIDE_BVH | RTBVH_FLAG_CERTIFIED)) != 0 || auto_checked(c);
-        if (c->qnode_ok) launch_qnodes(a, s);
+        const bool qnodes = (c->cfg.flags & (RTBVH_FLAG_WIDE_BVH | RTBVH_FLAG_CERTIFIED)) != 0 || auto_checked(c);
+        if (qnodes) launch_qnodes(a, s);
         c->leaf_pending = false;
         c->tail_pending = false;
-        c->pseudo_ok = true;
         if (timing) for (int k = 1; k <= 5; k++) HIPC(c, hipEventRecord(ev[k], s));
         if (timing) c->n_builds++;
         if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, s));
-        c->built = true;
-        c->built_clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
+        c->tree = Tree{true, clz64, RECORDS, RECORDS | PSEUDO | (qnodes ? QNODES : 0u)};
         return check_launch(c, "build kernel");
     }
     if (timing) HIPC(c, hipEventRecord(ev[1], s));   // (the mesh box is the scene's: rtbvh_set_scene)
     // a certified-only context's build: node boxes instead of node records (records_skipped)
-    c->build_nbox = records_skipped(c);
-    c->rec_ok = !c->build_nbox;
-    c->nbox_ok = c->build_nbox;
-    a.rec_on = c->build_nbox ? 0u : 1u;
-    a.nbox = c->build_nbox ? c->d_nbox : nullptr;
+    const Form nodes = records_skipped(c) ? NBOX : RECORDS;
+    a.rec_on = nodes == RECORDS ? 1u : 0u;
+    a.nbox = nodes == NBOX ? c->d_nbox.h : nullptr;
     if (c->T <= small_sort_max() && !(c->cfg.flags & RTBVH_FLAG_MULTI_KERNEL_BUILD)) {
         // the Morton pass and the sort in one workgroup (build.hip k_morton_sort_small; stage "morton")
         c->sorted = SortResult{c->d_ka, c->d_va};
@@ -1389,18 +1353,16 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     // leaf records, boxes, node records and QNodes; rtbvh_compute_bvh's primary pass may start
     // after the leaves (ev_leaf)
     launch_refit_leaves(a, s);
-    c->pseudo_ok = a.pseudo != 0;
-    c->qnode_ok = true;   // (quantized by the refit kernels)
     c->leaf_pending = false;
     if (c->leaf_want) {
         if (!c->side) {   // high priority: its workgroups go first while the crossing nodes' fill the CUs
             int lo = 0, hi = 0;
             HIPC(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
             if (!c->knob_side_priority) hi = lo;   // (A/B runs: RTBVH_SIDE_PRIORITY=0)
-            HIPC(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, hi));
+            HIPC(c, hipStreamCreateWithPriority(c->side.out(), hipStreamNonBlocking, hi));
         }
-        if (!c->ev_leaf) HIPC(c, hipEventCreateWithFlags(&c->ev_leaf, hipEventDisableTiming));
-        if (!c->ev_prim) HIPC(c, hipEventCreateWithFlags(&c->ev_prim, hipEventDisableTiming));
+        if (!c->ev_leaf) HIPC(c, hipEventCreateWithFlags(c->ev_leaf.out(), hipEventDisableTiming));
+        if (!c->ev_prim) HIPC(c, hipEventCreateWithFlags(c->ev_prim.out(), hipEventDisableTiming));
         HIPC(c, hipEventRecord(c->ev_leaf, s));
         c->leaf_pending = true;
     }
@@ -1409,8 +1371,8 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     if (timing) HIPC(c, hipEventRecord(ev[5], s));
     if (timing) c->n_builds++;
     if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, s));
-    c->built = true;
-    c->built_clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
+    // (the refit kernels quantize the QNodes)
+    c->tree = Tree{true, clz64, nodes, (uint32_t)nodes | (a.pseudo ? PSEUDO : 0u) | QNODES};
     return check_launch(c, "build kernels");
 }
 
@@ -1492,22 +1454,20 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
         memcpy(c->graph_key, key, sizeof(key));
         c->graph_state = rtbvh_ctx::TraceState{c->W,     c->H,         c->bounces,        c->nsplit,
                                                 c->rec_P, c->last_walk, c->last_walk_state, c->last_cert};
+        c->graph_tree = c->tree;   // (the forms the captured trace derived are in the graph too)
         c->graph_captures++;
     }
     // the replayed build rewrites the BVH (and a split trace the slot queues): after the
     // frames in flight on caller streams, as rtbvh_build_async
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) {
-            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_slot[k], 0));
-            c->slot_busy[k] = false;
-        }
-    rtbvh_status cst = wait_queries(c, c->stream);
-    if (cst) return cst;
-    cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
+    rtbvh_status cst = wait_slots(c, c->stream);
+    if (!cst) cst = wait_queries(c, c->stream);
+    if (!cst) cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
     if (cst) return cst;
     HIPC(c, hipGraphLaunch(c->graph_exec, c->stream));
     HIPC(c, hipEventRecord(c->ev_built, c->stream));
-    // the host-side state of the captured trace (a trace in between may have changed it)
+    // the host-side state of the captured frame: its tree (the replayed build rewrote it for this camera, so
+    // whatever was derived since belongs to the old one) and its trace (one in between may have changed it)
+    c->tree = c->graph_tree;
     const rtbvh_ctx::TraceState& g = c->graph_state;
     c->W = g.W;
     c->H = g.H;
@@ -1521,8 +1481,7 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
     c->rank = 0;
     c->nranks = 1;
     c->last_slot = 0;
-    c->traced = c->built = true;
-    c->built_clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
+    c->traced = true;
     c->frame_here = c->intensity_here = true;
     return rtbvh_synchronize(c);
 }
@@ -1546,7 +1505,7 @@ rtbvh_status rtbvh_compute_bvh(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
 // on the device.  Leaves the context as rtbvh_trace with its own flags does.
 rtbvh_status rtbvh_verify_walk(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint64_t* differing) {
     if (!c || !differing) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "verify_walk before build");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "verify_walk before build");
     if (W == 0 || H == 0 || bounces > 14) return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
     HIPC(c, hipSetDevice(c->cfg.device));
     rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
@@ -1632,7 +1591,7 @@ rtbvh_status rtbvh_trace_band_async(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32
                 slot = k;
             }
         if (!slot) return fail(c, RTBVH_ERR_INVALID_ARG, "more caller streams trace one context than it has slots");
-        if (!c->ev_slot[slot]) HIPC(c, hipEventCreateWithFlags(&c->ev_slot[slot], hipEventDisableTiming));
+        if (!c->ev_slot[slot]) HIPC(c, hipEventCreateWithFlags(c->ev_slot[slot].out(), hipEventDisableTiming));
         c->slots_used = true;
         HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
     }
@@ -1709,7 +1668,7 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     const uint32_t rows0 = deal_max_rows(H, nranks, c->root_share);
     const size_t need = (size_t)(rank == 0 ? nranks : 1) * rows0 * W;
     if (c->cap_band < need) {
-        HIPC(c, dalloc(c->d_band, need));
+        HIPC(c, c->d_band.alloc(need));
         c->cap_band = need;
     }
     rtbvh_status st = enqueue_trace(c, W, H, bounces, rank, nranks, c->d_band, nullptr, c->stream);
@@ -1744,13 +1703,9 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
 
 rtbvh_status rtbvh_synchronize(rtbvh_ctx* c) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    HIPC(c, hipStreamSynchronize(c->stream));
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)   // and the frames in flight on caller streams
-        if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
-    if (c->query_busy) {   // and the ray queries
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        c->query_busy = false;
-    }
+    rtbvh_status st = sync_all(c);
+    if (st) return st;
+    c->query_busy = false;
     // each trace ends by copying the never-reset overflow word into its slot's pinned word
     unsigned long long ovf = c->ovf_seen;
     for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++)
@@ -1791,11 +1746,11 @@ rtbvh_status rtbvh_read_intensity(rtbvh_ctx* c, float* inten) {
     return RTBVH_OK;
 }
 
-const float* rtbvh_framebuffer_device(rtbvh_ctx* c) { return c ? (const float*)c->d_color : nullptr; }
+const float* rtbvh_framebuffer_device(rtbvh_ctx* c) { return c ? (const float*)c->d_color.h : nullptr; }
 
 rtbvh_status rtbvh_read_bvh(rtbvh_ctx* c, rtbvh_node* out, uint32_t capacity) {
     if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
     const size_t total = 2 * (size_t)c->T - 1;
     if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_bvh: capacity < 2n-1");
     HIPC(c, hipSetDevice(c->cfg.device));
@@ -1834,16 +1789,13 @@ rtbvh_status rtbvh_present(rtbvh_ctx* c, uint8_t* rgba8) {
 
 rtbvh_status rtbvh_read_wide(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
     if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
     const size_t total = c->T > 1 ? 2 * (size_t)(c->T - 1) : 0;
     if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_wide: capacity < 2(n-1)");
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status rs = ensure_records(c, c->stream);   // (a certified-only build wrote node boxes instead)
+    rtbvh_status rs = ensure_form(c, RECORDS, c->stream);   // (a certified-only build wrote node boxes instead)
+    if (!rs) rs = ensure_form(c, PSEUDO, c->stream);        // (binned / AUTO walks: a build without them)
     if (rs) return rs;
-    if (!c->pseudo_ok) {   // a build that wrote no leaf pseudo-records (binned / AUTO walks): now
-        launch_pseudo(build_args(c), c->stream);
-        c->pseudo_ok = true;
-    }
     HIPC(c, hipStreamSynchronize(c->stream));
     if (total) HIPC(c, hipMemcpy(out, c->d_rec, total * sizeof(Inner), hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -1851,14 +1803,12 @@ rtbvh_status rtbvh_read_wide(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
 
 rtbvh_status rtbvh_read_qnodes(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
     if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
     const size_t total = c->T > 1 ? 2 * (size_t)c->T - 1 : 0;
     if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_qnodes: capacity < 2n-1");
     HIPC(c, hipSetDevice(c->cfg.device));
-    if (!c->qnode_ok) {
-        launch_qnodes(build_args(c), c->stream);
-        c->qnode_ok = true;
-    }
+    rtbvh_status rs = ensure_form(c, QNODES, c->stream);
+    if (rs) return rs;
     HIPC(c, hipStreamSynchronize(c->stream));
     if (total) HIPC(c, hipMemcpy(out, c->d_qnode, total * sizeof(QNode), hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -1866,7 +1816,7 @@ rtbvh_status rtbvh_read_qnodes(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
 
 rtbvh_status rtbvh_read_morton(rtbvh_ctx* c, uint32_t* codes) {
     if (!c || !codes) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipMemcpy(codes, c->d_codes, sizeof(uint32_t) * c->T, hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -1874,7 +1824,7 @@ rtbvh_status rtbvh_read_morton(rtbvh_ctx* c, uint32_t* codes) {
 
 rtbvh_status rtbvh_read_sorted(rtbvh_ctx* c, uint32_t* keys, uint32_t* ids) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
     HIPC(c, hipStreamSynchronize(c->stream));
     if (keys) HIPC(c, hipMemcpy(keys, c->sorted.keys, sizeof(uint32_t) * c->T, hipMemcpyDeviceToHost));
     if (ids) HIPC(c, hipMemcpy(ids, c->sorted.vals, sizeof(uint32_t) * c->T, hipMemcpyDeviceToHost));
@@ -1896,9 +1846,7 @@ rtbvh_status rtbvh_read_rays(rtbvh_ctx* c, rtbvh_ray_present* reflect_out, rtbvh
 rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
     if (!c || !out) return RTBVH_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+    if (rtbvh_status st = sync_all(c)) return st;
     out->num_tris = c->T;
     out->num_nodes = c->T ? 2 * c->T - 1 : 0;
     out->width = c->W;
@@ -2050,10 +1998,11 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     c->query_busy = false;
     rtbvh_status st = ensure_build_capacity(c, n);
     if (st) return st;
-    float* d_boxes = nullptr;
-    void* d_out = nullptr;
-    HIPC(c, hipMalloc((void**)&d_boxes, (size_t)n * 24));
-    HIPC(c, hipMalloc(&d_out, (2 * (size_t)n - 1) * sizeof(rtbvh_node)));
+    DevBuf<float> d_boxes;
+    DevBuf<rtbvh_node> d_out;
+    HIPC(c, d_boxes.alloc((size_t)n * 6));
+    HIPC(c, d_out.alloc(2 * (size_t)n - 1));
+    reset_tree(c);   // the scene's BVH buffers are reused from here on
     HIPC(c, hipMemcpy(c->d_ka, sorted_codes, (size_t)n * 4, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(d_boxes, leaf_boxes, (size_t)n * 24, hipMemcpyHostToDevice));
     BuildArgs a = build_args(c);
@@ -2066,20 +2015,15 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     launch_from_codes(a, d_boxes, c->stream);
     launch_export(a, d_out, c->stream);
     st = check_launch(c, "build_from_codes kernels");
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (!st && e == hipSuccess) e = hipMemcpy(out, d_out, (2 * (size_t)n - 1) * sizeof(rtbvh_node), hipMemcpyDeviceToHost);
-    (void)hipFree(d_boxes);
-    (void)hipFree(d_out);
+    const hipError_t e = hipStreamSynchronize(c->stream);
     if (st) return st;
     HIPC(c, e);
-    c->built = false;   // the scene's BVH buffers were reused
-    c->build_nbox = false;
-    c->rec_ok = c->nbox_ok = false;
+    HIPC(c, hipMemcpy(out, d_out, (2 * (size_t)n - 1) * sizeof(rtbvh_node), hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 
 // ---- ray queries -------------------------------------------------------------------------------------
-// The walk reads the tree form the last build wrote (build_nbox: the topology and node boxes, else the node
+// The walk reads the tree form the last build wrote (Tree::wrote NBOX: the topology and node boxes, else the node
 // records), never a derived one.  Queries on any stream are chained by ev_query (they share the scratch block
 // and the sort's buffers); each waits for the last build (ev_built), the next build for them (wait_queries).
 rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, rtbvh_hit* dev_hits,
@@ -2090,22 +2034,22 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "query: 2^31 rays or more");
     if (n == 0) return RTBVH_OK;
     if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "query: NULL rays or hits");
-    if (!c->built) return fail(c, RTBVH_ERR_NOT_READY, "query before build");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "query before build");
     static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "query record layouts");
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool any = (mode & RTBVH_QUERY_ANY) != 0, sort = (mode & RTBVH_QUERY_SORT) != 0;
     const bool count = (mode & RTBVH_QUERY_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, dalloc(c->d_qscratch, QUERY_SCRATCH_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_SCRATCH_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
     if (sort && (n > c->cap_qsort || !c->d_qsort)) {
         // earlier queries sort in the old buffers: the first RTBVH_QUERY_SORT query and each larger one wait
         // for them on the host here (and hipMalloc blocks too), as include/rtbvh.h says
         HIPC(c, hipEventSynchronize(c->ev_query));
         c->cap_qsort = 0;
-        HIPC(c, dalloc(c->d_qsort, 6 * (size_t)n));
-        HIPC(c, dalloc(c->d_qsort_scratch, sort_scratch_words(N)));
+        HIPC(c, c->d_qsort.alloc(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.alloc(sort_scratch_words(N)));
         c->cap_qsort = n;
     }
     if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
@@ -2117,7 +2061,7 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     a.inner = c->d_rec;
     a.topo = c->d_topo;
     a.nbox = c->d_nbox;
-    a.nb = c->build_nbox;
+    a.nb = c->tree.wrote == NBOX;
     a.leaf = c->d_leaf;
     a.T = c->T;
     a.rays = reinterpret_cast<const float4*>(dev_rays);
@@ -2145,22 +2089,20 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
 
 rtbvh_status rtbvh_query_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->built)   // (nothing to stage: the checks of the query)
+    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->tree.built)   // (nothing to stage: the query's checks)
         return rtbvh_query_async(c, rays, n, hits, mode, nullptr);
     HIPC(c, hipSetDevice(c->cfg.device));
-    char* d = nullptr;
-    HIPC(c, hipMalloc((void**)&d, (size_t)n * (sizeof(rtbvh_ray) + sizeof(rtbvh_hit))));
-    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d);
+    DevBuf<char> d;
+    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_ray) + sizeof(rtbvh_hit))));
+    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d.h);
     rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d + (size_t)n * sizeof(rtbvh_ray));
-    rtbvh_status st = RTBVH_OK;
     if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
-        st = fail(c, RTBVH_ERR_HIP, "query_host: upload failed");
-    if (!st) st = rtbvh_query_async(c, dr, n, dh, mode, nullptr);
-    if (!st && hipStreamSynchronize(c->stream) != hipSuccess) st = fail(c, RTBVH_ERR_HIP, "query_host: sync");
-    if (!st && hipMemcpy(hits, dh, (size_t)n * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
-        st = fail(c, RTBVH_ERR_HIP, "query_host: download failed");
-    (void)hipFree(d);
+        return fail(c, RTBVH_ERR_HIP, "query_host: upload failed");
+    rtbvh_status st = rtbvh_query_async(c, dr, n, dh, mode, nullptr);
     if (st) return st;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "query_host: sync");
+    if (hipMemcpy(hits, dh, (size_t)n * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "query_host: download failed");
     return rtbvh_synchronize(c);   // (the hits are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
 }
 

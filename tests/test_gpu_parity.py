@@ -1003,6 +1003,78 @@ def test_graph_replay_after_a_larger_trace_reallocates():
         assert g.stats()["graph_captures"] == 2
 
 
+def _two_cameras():
+    """Two cameras that differ (camera_reference depends on the aspect ratio alone: 320x240 and 640x480 give
+    the same matrices, and set_camera then keeps the old tree)."""
+    a, b = rt.camera_reference(320, 240), rt.camera_reference(400, 200)
+    assert not np.array_equal(a[0], b[0])
+    return a, b
+
+
+def _graph_replayed_at_camera_b(s, flags, reader):
+    """A graph context after: camera A, compute_bvh twice (capture, then replay), `reader` (which derives a
+    tree form the build did not write), camera B, compute_bvh (a replay).  Returns it with the first read."""
+    cam_a, cam_b = _two_cameras()
+    g = rt.Context(device=0, flags=rt.FLAG_GRAPH | flags)
+    g.set_scene(s)
+    g.set_camera(*cam_a)
+    g.compute_bvh(320, 240, 1)
+    g.compute_bvh(320, 240, 1)
+    first = getattr(g, reader)()
+    g.set_camera(*cam_b)
+    g.compute_bvh(320, 240, 1)
+    return g, first
+
+
+@pytest.mark.parametrize("case", ["records from node boxes", "leaf pseudo-records", "qnodes of a one-workgroup build"])
+def test_graph_replay_invalidates_derived_tree_forms(case):
+    """A replayed graph rebuilds the tree for the new camera, so a form derived between two replays -- node
+    records from a certified-only build's node boxes, the leaf pseudo-records, the QNodes of a one-workgroup
+    build -- belongs to the old tree: the reader after the replay returns the new camera's data, bit for bit
+    what a plain context reads after set_camera(B) and build(), not what it returned at camera A."""
+    flags, ntris, reader = {"records from node boxes": (rt.FLAG_CERTIFIED, 3000, "read_wide"),
+                            "leaf pseudo-records": (BINNED_FAST, 3000, "read_wide"),
+                            "qnodes of a one-workgroup build": (0, 1000, "read_qnodes")}[case]
+    s = rt.synthetic(ntris, seed=0x5EED0015, half_extent=(30, 30, 20))
+    g, first = _graph_replayed_at_camera_b(s, flags, reader)
+    with g, rt.Context(device=0, flags=flags) as plain:
+        got = getattr(g, reader)()
+        assert g.stats()["graph_captures"] == 1
+        plain.set_scene(s)
+        plain.set_camera(*_two_cameras()[1])
+        plain.build()
+        want = getattr(plain, reader)()
+        if reader == "read_qnodes":
+            # QNodes sit at their internal node's slot (test_qnodes_contain_the_exact_boxes); the leaves' slots
+            # are never written, so only the T - 1 slots that hold a QNode compare
+            nodes = plain.read_bvh()
+            for f in ("parent", "child_l", "child_r"):
+                np.testing.assert_array_equal(g.read_bvh()[f], nodes[f])
+            x = np.arange(ntris + 1, 2 * ntris - 1)
+            par = nodes["parent"][x]
+            keep = np.concatenate([[2 * ntris - 2], 2 * (par - ntris) + (nodes["child_l"][par] != x)])
+            assert len(np.unique(keep)) == ntris - 1
+            got, want, first = got[keep], want[keep], first[keep]
+    assert not np.array_equal(want, first)   # (the two cameras' trees differ)
+    np.testing.assert_array_equal(got, want)
+
+
+def test_trace_after_graph_replay_rederives_records():
+    """After the same sequence on a certified-only context (its build writes node boxes; read_wide derived the
+    records at camera A), set_flags to the packet walk and trace: the walk reads node records and leaf
+    pseudo-records derived from camera B's tree, and the frame is a plain packet context's at camera B."""
+    s = rt.synthetic(3000, seed=0x5EED0015, half_extent=(30, 30, 20))
+    packet = TRACE_MODES["packet"]
+    g, _ = _graph_replayed_at_camera_b(s, rt.FLAG_CERTIFIED, "read_wide")
+    with g, rt.Context(device=0, flags=packet) as plain:
+        g.set_flags(rt.FLAG_GRAPH | packet)
+        g.trace(320, 240, 1)
+        plain.set_scene(s)
+        plain.set_camera(*_two_cameras()[1])
+        plain.compute_bvh(320, 240, 1)
+        np.testing.assert_array_equal(g.read_framebuffer(), plain.read_framebuffer())
+
+
 @pytest.mark.parametrize("mode", ["reference", "nearest", "packet", "nearest+packet", "nearest+packet+refill",
                                   "nearest+packet+wide", "refill+sort"])
 def test_stack_limit_reports_overflow(mode):
