@@ -10,6 +10,7 @@ import pytest
 
 import raytracebvh_amd as rt
 from oracle import lib as orc
+from tests.cert_scenes import _grid, _mesh
 from tests.conftest import GOLDEN, load_scene_fixture
 
 pytestmark = pytest.mark.gpu
@@ -533,7 +534,7 @@ def test_wide_view_records_match_binary_tree():
             assert rec[15] == gen
 
 
-def _tiny_scene(seed=5):
+def _denormal_scene(seed=5):
     """Triangles at every scale down to the denormals (for the identity camera: clip space = object space):
     groups of a synthetic scene scaled by 2^0, 2^-40, 2^-70, 2^-100, 2^-118, 2^-126, 2^-135 -- edge bounds whose
     squares underflow and whose margin constant c is denormal (margin.h mt_edge_bound / mt_tcap_down)."""
@@ -576,7 +577,7 @@ def test_qnodes_contain_the_exact_boxes(scene):
     elif scene == "general boxes":
         s = _general_box_scene()
     elif scene == "tiny triangles":
-        s = _tiny_scene()
+        s = _denormal_scene()
     else:
         d = load_scene_fixture("Test")
         s = rt.Scene(d["vertices"], d["indices"], d["mat_indices"], d["material_blob"])
@@ -1212,35 +1213,6 @@ def test_auto_walk_orbit_replays_one_graph():
                 ofb, _, _ = orc.trace(_oscene(s), nodes, wvp, wv, W, H, B, 0, H, 8)
                 np.testing.assert_array_equal(want[0:H:8], ofb)
         assert len({c[0].tobytes() for c in cams}) == 5
-
-
-def _material(ns=300.0):
-    m = np.zeros(1, rt._lib.MATERIAL_DTYPE)
-    m[0]["diffuse"] = (0.64, 0.64, 0.64, 1.0)
-    m[0]["specular"] = (0.5, 0.5, 0.5, 1.0)
-    m[0]["shininess"] = ns
-    m[0]["alpha"] = 1.0
-    m[0]["tex_num"] = -1
-    return m
-
-
-def _mesh(tris, normals):
-    """rt.Scene from (n, 3, 3) positions and (n, 3) per-triangle vertex normals, one material."""
-    n = len(tris)
-    v = np.zeros((3 * n, 8), np.float32)
-    v[:, :3] = tris.reshape(-1, 3)
-    v[:, 3:6] = np.repeat(normals, 3, axis=0)
-    return rt.Scene(v, np.arange(3 * n, dtype=np.uint32), np.zeros(n, np.uint32), _material())
-
-
-def _grid(n0, n1, lo0, lo1, step):
-    """Two triangles per cell of an n0 x n1 grid (cell corners at lo + step * i): (2 n0 n1, 3, 2)."""
-    i, j = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
-    a0, a1 = (lo0 + step * i).ravel(), (lo1 + step * j).ravel()
-    b0, b1 = a0 + step, a1 + step
-    t1 = np.stack([np.stack([a0, a1], 1), np.stack([b0, a1], 1), np.stack([b0, b1], 1)], 1)
-    t2 = np.stack([np.stack([a0, a1], 1), np.stack([b0, b1], 1), np.stack([a0, b1], 1)], 1)
-    return np.concatenate([t1, t2])
 
 
 def _far_wall_scene(big=True):
