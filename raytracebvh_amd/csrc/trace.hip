@@ -28,6 +28,8 @@
 // from the CPUTests delta can trip it) counts the same way.
 #include "rtbvh_internal.h"
 
+#include <type_traits>
+
 namespace rtbvh {
 namespace {
 
@@ -104,86 +106,155 @@ __device__ __forceinline__ bool ray_box_xy(f3 o, f3 inv, f2v lo, f2v hi, float l
     return 0 <= mx && mn <= mx && (!hit || mn <= best);
 }
 
-// findCollision, RayTraceTraversal.hlsl:106-193.  The reference keeps stack[0] = -1
-// and loops `do { ... } while (stackIndex != -1)`; here the entry at the top of
-// the stack is cached in a register (`top`), so a pop hands over the next node at
-// once and refills `top` from scratch in the background.  Returns hit;
-// best_leaf = sorted leaf index.  `limit` <= STACK_SIZE entries.
-// LSB > 0: stack entries [0, LSB) in LDS (`lst`: this lane's column, entry k at lst[k * BLOCK]; a
-// wave's lanes on 64 distinct banks), deeper ones in scratch (the one-ray-per-lane kernels).  The pop
-// compiles to one flat load of a selected pointer (LDS or scratch); forcing ds_read (a module-scope
-// array, every lane reading LDS and the deeper ones scratch as well) was 1-2% slower at C3
+// ---- the per-lane binary walk: findCollision, RayTraceTraversal.hlsl:106-193 ------------------
+// One ray's walk state.  The reference keeps stack[0] = -1 and loops `do { ... } while (stackIndex != -1)`;
+// here the entry at the top of the stack is cached in a register (`top`), so a pop hands over the next node
+// at once and refills `top` from the stack in the background.  sp: the reference stack index (entries
+// [0, sp) below the cached top; entry 0 is the sentinel = top at start; -1: the walk is over).
+// bl: the best hit's sorted leaf index.  guard: a valid tree is walked in <= 2T-1 steps.
+struct Walk {
+    uint32_t node, top;
+    int sp;
+    bool hit;
+    float best;
+    uint32_t bl, guard;
+};
+__device__ __forceinline__ Walk walk_start(uint32_t root, uint32_t T) {
+    return Walk{root, INVALID, 0, false, 0.f, 0u, 2 * T + 2};
+}
+
+// The rules of a walk: its order, which triangle distance replaces the best hit, and which box is entered.
+// WalkRule: the reference's (strict `<` replacement; NEAREST: the nearer child first, the lexicographic
+// (t, leaf index) minimum kept).
+template <bool NEAREST_FIRST> struct WalkRule {
+    static constexpr bool NEAREST = NEAREST_FIRST, FIRST_HIT = false;
+    __device__ __forceinline__ bool accept(const Walk& w, float t, uint32_t j) const {
+        return t != -1.f && (!w.hit || t < w.best || (NEAREST && t == w.best && j < w.bl));
+    }
+    __device__ __forceinline__ bool box(f3 o, f3 inv, f2v lo, f2v hi, float lz, float hz, const Walk& w,
+                                        float& tmin) const {
+        return ray_box_xy(o, inv, lo, hi, lz, hz, w.hit, w.best, tmin);
+    }
+};
+// QueryRule (k_query): t_max enters in two places only: a triangle's t is accepted iff the reference accepts
+// it and t <= t_max; a box passes iff the reference's first two conditions hold and
+// (hit ? mn <= dist : !(mn > t_max)) -- with t_max = +inf the reference, bit for bit.
+// ANY: the box test without the `hit` branch, the walk ends at the first accepted triangle.
+template <bool ANY>
+__device__ __forceinline__ bool query_box(f3 o, f3 inv, f2v lo, f2v hi, float lz, float hz, bool hit, float best,
+                                          float tmax, float& mn) {
+    const bool base = ray_box_xy(o, inv, lo, hi, lz, hz, false, 0.f, mn);
+    return base && (!ANY && hit ? mn <= best : !(mn > tmax));
+}
+template <bool ANY> struct QueryRule {
+    static constexpr bool NEAREST = false, FIRST_HIT = ANY;
+    float tmax;
+    __device__ __forceinline__ bool accept(const Walk& w, float t, uint32_t) const {
+        return t != -1.f && t <= tmax && (ANY || !w.hit || t < w.best);
+    }
+    __device__ __forceinline__ bool box(f3 o, f3 inv, f2v lo, f2v hi, float lz, float hz, const Walk& w,
+                                        float& tmin) const {
+        return query_box<ANY>(o, inv, lo, hi, lz, hz, w.hit, w.best, tmax, tmin);
+    }
+};
+
+// The stack of a one-ray-per-lane kernel (a Stack supplies store(k, v) and load(k) of entry k): entries
+// [0, LSB) in LDS (`lst`: this lane's column, entry k at lst[k * BLOCK]; a wave's lanes on 64 distinct banks),
+// deeper ones in scratch (`s`: the walk's own array); LSB = 0: all in scratch.  The pop is one flat load of a
+// selected pointer (LDS or scratch); forcing ds_read (a module-scope array, every lane reading LDS and the
+// deeper ones scratch as well) was 1-2% slower at C3.  The push stays a ds_write or a scratch store: `s` is
+// typed as a scratch pointer, or the compiler merges the two into one flat store of a selected pointer too.
+// (The persistent kernels' stack: BlockStack, below.)
 #ifndef RTBVH_LANE_LSB
 #define RTBVH_LANE_LSB 16
 #endif
 constexpr int LANE_LSB = RTBVH_LANE_LSB;
-template <bool COUNT, bool NEAREST, int LSB = 0>
-__device__ __forceinline__ bool traverse(const Inner* __restrict__ inner, const float4* __restrict__ leaf, uint32_t T,
-                                         f3 o, f3 d, f3 inv, int limit, float& best, uint32_t& best_leaf, Counts& c,
-                                         uint32_t* lst = nullptr) {
-    bool hit = false;
-    best = 0.f;
-    best_leaf = 0;
-    uint32_t stack[STACK_SIZE];   // reference entries [0, sp) below the cached top
-    int sp = 0;                   // reference stack index; stack[0] is the sentinel = top at start
-    uint32_t top = INVALID;
-    uint32_t node = root_slot(T);
-    uint32_t guard = 2 * T + 2;   // a valid tree is walked in <= 2T-1 steps
-    do {
-        if (--guard == 0) { c.overflow++; break; }
-        if (node & LEAF_BIT) {
-            const uint32_t j = node & ~LEAF_BIT;
-            const float4* r = leaf + 4 * (size_t)j;
-            float4 a = r[0], b = r[1];
-            float e2z = r[2].x;
-            pin(a); pin(b); pin(e2z);
-            if (COUNT) c.leaf++;
-            const float t = ray_triangle(o, d, mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), mk(b.z, b.w, e2z));
-            if (t != -1.f && (!hit || t < best || (NEAREST && t == best && j < best_leaf))) {
-                best = t;
-                best_leaf = j;
-                hit = true;
-            }
-            node = top;                                 // pop
-            if (--sp >= 0) top = LSB > 0 && sp < LSB ? lst[sp * BLOCK] : stack[sp];
-            continue;
+template <int LSB> struct LaneStack {
+    uint32_t* lst;
+    __attribute__((address_space(5))) uint32_t* s;
+    __device__ __forceinline__ void store(int k, uint32_t v) {
+        if (LSB > 0 && k < LSB) lst[k * BLOCK] = v;
+        else s[k] = v;
+    }
+    __device__ __forceinline__ uint32_t load(int k) const {
+        return LSB > 0 ? *(k < LSB ? lst + k * BLOCK : (uint32_t*)(s + k)) : s[k];
+    }
+};
+
+// pop: the next node from the cached top; refill the top from entry --sp
+template <class Stack> __device__ __forceinline__ void walk_pop(Walk& w, const Stack& st) {
+    w.node = w.top;
+    if (--w.sp >= 0) w.top = st.load(w.sp);
+}
+// The ray is at leaf j (its triangle p0, e1, e2 already fetched): the triangle test, the rule's replacement of
+// the best hit, the pop.  Returns whether the triangle was accepted (a FIRST_HIT walk then stays at the leaf).
+template <bool COUNT, class Rule, class Stack>
+__device__ __forceinline__ bool walk_leaf(Walk& w, Stack& st, const Rule& rule, Counts& c, f3 o, f3 d, uint32_t j,
+                                          f3 p0, f3 e1, f3 e2) {
+    if (COUNT) c.leaf++;
+    const float t = ray_triangle(o, d, p0, e1, e2);
+    const bool acc = rule.accept(w, t, j);
+    if (acc) {
+        w.best = t;
+        w.bl = j;
+        w.hit = true;
+    }
+    if (!(Rule::FIRST_HIT && acc)) walk_pop(w, st);
+    return acc;
+}
+// the two children of an internal node: ids as the walk keeps them (a Tree's), boxes as aligned (x, y) pairs and z
+struct ChildPair {
+    uint32_t cl, cr;
+    f2v llo, lhi, rlo, rhi;
+    float lz0, lz1, rz0, rz1;
+};
+// The ray is at an internal node (its children already fetched): the two slab tests, the order, the push of
+// the second child -- a ray that would exceed `limit` entries loses both children, counted -- or the pop.
+template <bool COUNT, class Rule, class Stack>
+__device__ __forceinline__ void walk_node(Walk& w, Stack& st, const Rule& rule, Counts& c, f3 o, f3 inv, int limit,
+                                          const ChildPair& ch) {
+    if (COUNT) c.internal++;
+    float tl, tr;
+    const bool lh = rule.box(o, inv, ch.llo, ch.lhi, ch.lz0, ch.lz1, w, tl);
+    const bool rh = rule.box(o, inv, ch.rlo, ch.rhi, ch.rz0, ch.rz1, w, tr);
+    if (!lh && !rh) {
+        walk_pop(w, st);
+        return;
+    }
+    const bool swap = Rule::NEAREST && lh && rh && tr < tl;
+    if (lh && rh) {
+        if (w.sp + 1 >= limit) {
+            c.overflow++;
+            walk_pop(w, st);
+            return;
         }
-        if (COUNT) c.internal++;
+        st.store(w.sp, w.top);   // push the second child
+        w.sp++;
+        w.top = swap ? ch.cl : ch.cr;
+    }
+    w.node = swap ? ch.cr : (lh ? ch.cl : ch.cr);
+}
+
+// The two forms of the tree (a Tree supplies root(T) and children(node)).
+// Node records live in SLOTS (rtbvh_device.h): the walk keeps slots on its stack, and every child-pair test
+// reads ONE 64-B record (words 0..11 the boxes, 12..14 the children's ids and the node's own index).
+__device__ __forceinline__ ChildPair record_children(v4f q0, v4f q1, v4f q2, uint32_t cl, uint32_t cr) {
+    return ChildPair{cl, cr, q0.xy, q0.zw, q1.xy, q1.zw, q2.x, q2.y, q2.z, q2.w};
+}
+struct RecordTree {
+    const Inner* __restrict__ inner;
+    __device__ __forceinline__ uint32_t root(uint32_t T) const { return root_slot(T); }
+    __device__ __forceinline__ ChildPair children(uint32_t node) const {
         const v4f* r = reinterpret_cast<const v4f*>(inner + node);
         const v4f q0 = r[0], q1 = r[1], q2 = r[2];
         const uint4 q3 = reinterpret_cast<const uint4*>(r)[3];
-        const uint32_t cl = child_slot(q3.x, q3.z, 0), cr = child_slot(q3.y, q3.z, 1);
-        float tl, tr;
-        const bool lh = ray_box_xy(o, inv, q0.xy, q0.zw, q2.x, q2.y, hit, best, tl);
-        const bool rh = ray_box_xy(o, inv, q1.xy, q1.zw, q2.z, q2.w, hit, best, tr);
-        if (!lh && !rh) {
-            node = top;                                 // pop
-            if (--sp >= 0) top = LSB > 0 && sp < LSB ? lst[sp * BLOCK] : stack[sp];
-        } else {
-            const bool swap = NEAREST && lh && rh && tr < tl;
-            if (lh && rh) {
-                if (sp + 1 >= limit) {
-                    c.overflow++;
-                    node = top;
-                    if (--sp >= 0) top = LSB > 0 && sp < LSB ? lst[sp * BLOCK] : stack[sp];
-                    continue;
-                }
-                if (LSB > 0 && sp < LSB) lst[sp * BLOCK] = top;   // push the second child
-                else stack[sp] = top;
-                sp++;
-                top = swap ? cl : cr;
-            }
-            node = swap ? cr : (lh ? cl : cr);
-        }
-    } while (sp != -1);
-    return hit;
-}
-
-// traverse<COUNT, false> (findCollision, the reference order) on the topology and the node boxes, for a build that
-// wrote no node records (api.hip: a certified-only context's): at internal node k its children from topo[k], their
-// boxes from nbox (internal) or the leaf record (words 10..15), the same slab test in the same operations -- the same
-// visits, in the same order, and the same hit.  Two dependent fetches a step instead of one: the certified walks'
-// few re-traced rays only.
+        return record_children(q0, q1, q2, child_slot(q3.x, q3.z, 0), child_slot(q3.y, q3.z, 1));
+    }
+};
+// The topology and the node boxes, for a build that wrote no node records (api.hip: a certified-only context's):
+// at internal node k its children from topo[k], their boxes from nbox (internal) or the leaf record (words
+// 10..15), the same slab test in the same operations -- the same visits, in the same order, and the same hit.
+// Two dependent fetches a step instead of one: the certified walks' few re-traced rays only.
 __device__ __forceinline__ void nb_child_box(const float* __restrict__ nbox, const float4* __restrict__ leaf, uint32_t c,
                                              f2v& mnxy, f2v& mxxy, float& mnz, float& mxz) {
     if (c & LEAF_BIT) {
@@ -196,73 +267,62 @@ __device__ __forceinline__ void nb_child_box(const float* __restrict__ nbox, con
         mnxy = f2v{x.x, x.y}; mnz = y.x; mxxy = f2v{y.y, z.x}; mxz = z.y;
     }
 }
-template <bool COUNT>
-__device__ __forceinline__ bool traverse_nb(const uint4* __restrict__ topo, const float* __restrict__ nbox,
-                                            const float4* __restrict__ leaf, uint32_t T, f3 o, f3 d, f3 inv,
-                                            float& best, uint32_t& best_leaf, Counts& c) {
-    bool hit = false;
-    best = 0.f;
-    best_leaf = 0;
+struct NodeBoxTree {
+    const uint4* __restrict__ topo;
+    const float* __restrict__ nbox;
+    const float4* __restrict__ leaf;
+    // the root: internal node 0 (a one-leaf tree: the leaf)
+    __device__ __forceinline__ uint32_t root(uint32_t T) const { return T > 1 ? 0u : LEAF_BIT; }
+    __device__ __forceinline__ ChildPair children(uint32_t node) const {
+        const uint4 q = topo[node];
+        ChildPair ch;
+        ch.cl = q.x;
+        ch.cr = q.y;
+        nb_child_box(nbox, leaf, ch.cl, ch.llo, ch.lhi, ch.lz0, ch.lz1);
+        nb_child_box(nbox, leaf, ch.cr, ch.rlo, ch.rhi, ch.rz0, ch.rz1);
+        return ch;
+    }
+};
+
+// findCollision for one ray per lane: each branch fetches what it needs (a leaf 2 1/4 words of its record, a
+// node its children).  Returns hit; best_leaf = sorted leaf index.  `limit` <= STACK_SIZE entries.
+template <bool COUNT, bool NEAREST, int LSB = 0, class Tree>
+__device__ __forceinline__ bool traverse(const Tree& tree, const float4* __restrict__ leaf, uint32_t T, f3 o, f3 d,
+                                         f3 inv, int limit, float& best, uint32_t& best_leaf, Counts& c,
+                                         uint32_t* lst = nullptr) {
+    const WalkRule<NEAREST> rule;
     uint32_t stack[STACK_SIZE];
-    int sp = 0;
-    uint32_t top = INVALID;
-    uint32_t node = T > 1 ? 0u : LEAF_BIT;   // the root: internal node 0 (a one-leaf tree: the leaf)
-    uint32_t guard = 2 * T + 2;
+    LaneStack<LSB> st{lst, (__attribute__((address_space(5))) uint32_t*)stack};
+    Walk w = walk_start(tree.root(T), T);
     do {
-        if (--guard == 0) { c.overflow++; break; }
-        if (node & LEAF_BIT) {
-            const uint32_t j = node & ~LEAF_BIT;
+        if (--w.guard == 0) { c.overflow++; break; }
+        if (w.node & LEAF_BIT) {
+            const uint32_t j = w.node & ~LEAF_BIT;
             const float4* r = leaf + 4 * (size_t)j;
             float4 a = r[0], b = r[1];
             float e2z = r[2].x;
             pin(a); pin(b); pin(e2z);
-            if (COUNT) c.leaf++;
-            const float t = ray_triangle(o, d, mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), mk(b.z, b.w, e2z));
-            if (t != -1.f && (!hit || t < best)) {
-                best = t;
-                best_leaf = j;
-                hit = true;
-            }
-            node = top;
-            if (--sp >= 0) top = stack[sp];
-            continue;
-        }
-        if (COUNT) c.internal++;
-        const uint4 q = topo[node];
-        const uint32_t cl = q.x, cr = q.y;
-        f2v lmn, lmx, rmn, rmx;
-        float lz0, lz1, rz0, rz1;
-        nb_child_box(nbox, leaf, cl, lmn, lmx, lz0, lz1);
-        nb_child_box(nbox, leaf, cr, rmn, rmx, rz0, rz1);
-        float tl, tr;
-        const bool lh = ray_box_xy(o, inv, lmn, lmx, lz0, lz1, hit, best, tl);
-        const bool rh = ray_box_xy(o, inv, rmn, rmx, rz0, rz1, hit, best, tr);
-        if (!lh && !rh) {
-            node = top;
-            if (--sp >= 0) top = stack[sp];
+            walk_leaf<COUNT>(w, st, rule, c, o, d, j, mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), mk(b.z, b.w, e2z));
         } else {
-            if (lh && rh) {
-                if (sp + 1 >= STACK_SIZE) {
-                    c.overflow++;
-                    node = top;
-                    if (--sp >= 0) top = stack[sp];
-                    continue;
-                }
-                stack[sp] = top;
-                sp++;
-                top = cr;
-            }
-            node = lh ? cl : cr;
+            walk_node<COUNT>(w, st, rule, c, o, inv, limit, tree.children(w.node));
         }
-    } while (sp != -1);
-    return hit;
+    } while (w.sp != -1);
+    best = w.best;
+    best_leaf = w.bl;
+    return w.hit;
 }
-// the reference-order walk of a re-traced ray: on the records, or (a.nb) the topology and node boxes
+// the reference-order walk of a re-traced ray: on the records, or (nb) the topology and node boxes
+template <bool COUNT>
+__device__ __forceinline__ bool traverse_ref(bool nb, const Inner* __restrict__ inner, const uint4* __restrict__ topo,
+                                             const float* __restrict__ nbox, const float4* __restrict__ leaf,
+                                             uint32_t T, f3 o, f3 d, f3 inv, float& best, uint32_t& bl, Counts& c) {
+    return nb ? traverse<COUNT, false>(NodeBoxTree{topo, nbox, leaf}, leaf, T, o, d, inv, STACK_SIZE, best, bl, c)
+              : traverse<COUNT, false>(RecordTree{inner}, leaf, T, o, d, inv, STACK_SIZE, best, bl, c);
+}
 template <bool COUNT>
 __device__ __forceinline__ bool traverse_ref(const TraceArgs& a, f3 o, f3 d, f3 inv, float& best, uint32_t& bl,
                                              Counts& c) {
-    return a.nb ? traverse_nb<COUNT>(a.topo, a.nbox, a.leaf, a.T, o, d, inv, best, bl, c)
-                : traverse<COUNT, false>(a.inner, a.leaf, a.T, o, d, inv, STACK_SIZE, best, bl, c);
+    return traverse_ref<COUNT>(a.nb, a.inner, a.topo, a.nbox, a.leaf, a.T, o, d, inv, best, bl, c);
 }
 
 // ---- wave-packet traversal (primary rays) -------------------------------------
@@ -606,7 +666,7 @@ __device__ __forceinline__ bool traverse_packet4(const Inner* __restrict__ inner
 // 2 packet reference order, 3 packet nearest-first, 4 4-wide packet (axis-parallel test),
 // 5 the same without the walk-length guard (a clz64 tree has no cycles; ~6 SALU per step)
 // 6: the reference order per lane on the topology and the node boxes (a certified trace's overflowed tiles and
-// frames past the binned pass's size, on a build without node records: traverse_nb)
+// frames past the binned pass's size, on a build without node records: traverse on a NodeBoxTree)
 template <int K> struct PrimaryWalk {
     static constexpr bool NEAREST = (K == 1 || K == 3);
     static constexpr bool PACKET = (K >= 2 && K <= 5);
@@ -760,6 +820,23 @@ __device__ __forceinline__ uint32_t wave_append(bool active, uint32_t* counter) 
     base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
     return base + lane_rank(mask);
 }
+// the sum of v over the wave's 64 lanes, in every lane; and of each element of an array
+template <class V> __device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+template <class V, int N> __device__ __forceinline__ void wave_sum(V (&v)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = wave_sum(v[k]);
+}
+// the ray of a queue entry (o = words 2..4, d = words 5..7, as two 16-B loads) and its reciprocal direction
+__device__ __forceinline__ void load_ray(const RayQ* e, f3& o, f3& d, f3& inv) {
+    const float4 q0 = reinterpret_cast<const float4*>(e)[0], q1 = reinterpret_cast<const float4*>(e)[1];
+    o = mk(q0.z, q0.w, q1.x);
+    d = mk(q1.y, q1.z, q1.w);
+    inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+}
 
 // counters: [base] internal visits, [base+1] leaf visits, [base+2] hits (base 2 primary,
 // 5 bounce), [8] stack overflows / guard trips (also added to *overflow), [9] textured hits,
@@ -769,10 +846,7 @@ template <bool COUNT, bool BINS = false>
 __device__ __forceinline__ void flush_counts(const TraceArgs& a, const Counts& c, uint32_t hits, uint32_t tex,
                                              int base) {
     unsigned long long v[7] = {c.internal, c.leaf, hits, c.overflow, tex, c.wint, c.wleaf};
-#pragma unroll
-    for (int k = 0; k < 7; k++)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    wave_sum(v);
     if (lane_id() == 0) {
         if (COUNT) {
             atomicAdd(&a.counters[base], v[0]);
@@ -881,10 +955,13 @@ __global__ __launch_bounds__(BLOCK, 8) void k_primary(TraceArgs a, RayQ* __restr
         phit = traverse_packet<COUNT, PW::NEAREST>(a.inner, a.leaf, a.T, o, d, inv, valid, lim, best, bl, c,
                                                    s_pst + w * PST);
     if (valid) {
-        const bool h = PW::PACKET ? phit
-                       : PW::NB   ? traverse_nb<COUNT>(a.topo, a.nbox, a.leaf, a.T, o, d, inv, best, bl, c)
-                                  : traverse<COUNT, PW::NEAREST, PW::PACKET ? 0 : LANE_LSB>(a.inner, a.leaf, a.T, o, d, inv, lim,
-                                                                                           best, bl, c, s_lst + threadIdx.x);
+        bool h = phit;
+        if (PW::NB) {   // (all in scratch, the compiled capacity: the few rays of a certified trace)
+            h = traverse_ref<COUNT>(true, a.inner, a.topo, a.nbox, a.leaf, a.T, o, d, inv, best, bl, c);
+        } else if (!PW::PACKET) {
+            h = traverse<COUNT, PW::NEAREST, LANE_LSB>(RecordTree{a.inner}, a.leaf, a.T, o, d, inv, lim, best, bl, c,
+                                                       s_lst + threadIdx.x);
+        }
         live = primary_pixel(a, out, o, d, h, best, bl, hits, tex, e);
     }
     const uint32_t slot = wave_append(emit && live, qcount);
@@ -938,8 +1015,7 @@ __global__ __launch_bounds__(BLOCK) void k_pb_bin(TraceArgs a, uint32_t* __restr
 constexpr uint32_t PB_SCAN = 1024;
 __device__ __forceinline__ uint32_t block_sum_1024(uint32_t v, uint32_t* s_w) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    v = wave_sum(v);
     if (lane == 0) s_w[w] = v;
     __syncthreads();
     uint32_t t = 0;
@@ -1014,10 +1090,120 @@ constexpr uint32_t PB_RASTER_BLOCK_SMALL = 512;   // ... for a small pass one fr
 #ifndef RTBVH_PB_PROBE
 #define RTBVH_PB_PROBE 0
 #endif
+// CERT (the certified pass, DESIGN.md 3): the binned pass tested every leaf whose triangle could be
+// accepted below a pixel's bound (its depth key, margin.h); a pixel's (t, leaf) is the reference's when
+// the leaf's own box passes the reference slab test with the bound t (k_bounce_shade's leaf_certified,
+// here from the leaf record's box).  Pixels that fail it go to the re-trace list (redo: compact pixel
+// index) and are left to k_primary_redo, outside the block's bounce-queue claim.
+// One tile of k_pb_shade's work over NT threads, the pixels' keys from key_at(compact row, x).  s_cnt: 16
+// words of LDS, s_mask: 2 x 16 words, s_base: one.  The 16 sub-tiles of 8 x 8 pixels go to the waves in
+// turn; a first pass counts each one's live rays (and certificates) into LDS, the tile claims its queue
+// range, then a second pass shades them (no per-sub-tile registers held across the claim).
+// (Inlined: out of line, A/B round 5, the fused binned pass took 1.07 ms against 0.86.)
+// The kernel's TraceArgs (its first argument) read again from the kernel-argument segment where they are used:
+// scalar loads the compiler cannot hoist out of a loop (held in SGPRs across the shading loop's iterations they
+// spilled into VGPR lanes, and the shading's VGPRs to scratch)
+__device__ __forceinline__ const TraceArgs& kernel_trace_args() {
+    auto p = (const __attribute__((address_space(4))) TraceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const TraceArgs*)p;
+}
 template <bool COUNT, bool CERT, uint32_t NT, bool REC, class KeyAt>
-__device__ void pb_shade_tile(const TraceArgs& a, uint32_t rows, KeyAt&& key_at, RayQ* __restrict__ q,
-                              uint32_t* __restrict__ qcount, int emit, uint32_t* __restrict__ redo,
-                              uint32_t* __restrict__ redo_count, uint32_t* s_cnt, uint64_t* s_mask, uint32_t& s_base);
+__device__ __forceinline__ void pb_shade_tile(const TraceArgs& a, uint32_t rows, KeyAt&& key_at, RayQ* __restrict__ q,
+                                              uint32_t* __restrict__ qcount, int emit, uint32_t* __restrict__ redo,
+                                              uint32_t* __restrict__ redo_count, uint32_t* s_cnt, uint64_t* s_mask,
+                                              uint32_t& s_base) {
+    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
+    const uint32_t X0 = blockIdx.x * PB_TILE, C0 = blockIdx.y * PB_TILE;
+    constexpr uint32_t NST = (PB_TILE / 8) * (PB_TILE / 8) / (NT / 64);   // sub-tiles per wave
+    constexpr uint32_t NSUB = (PB_TILE / 8) * (PB_TILE / 8);
+    const float hw = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(a.W >> 1))));
+    const float hh = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(a.H >> 1))));
+    const auto pixel = [&](uint32_t i, uint32_t& x, uint32_t& crow) {
+        const uint32_t st = w + i * (NT / 64);
+        x = X0 + (st % (PB_TILE / 8)) * 8 + (lane & 7u);
+        crow = C0 + (st / (PB_TILE / 8)) * 8 + (lane >> 3);
+        return x < a.W && crow < rows;
+    };
+    // the live reflection rays: hit, and the hit material's shininess > 0
+#pragma unroll 1
+    for (uint32_t i = 0; i < NST; i++) {
+        uint32_t x, crow;
+        const bool valid = pixel(i, x, crow);
+        const uint64_t key = valid ? key_at(crow, x) : NO_HIT;
+        bool live = false, flag = false;
+        if (CERT && key != NO_HIT) {   // the certificate: the leaf's box, the reference slab test at t
+            const float4 b2 = a.leaf[4 * (size_t)(uint32_t)key + 2], b3 = a.leaf[4 * (size_t)(uint32_t)key + 3];
+            const f3 o = mk(((float)x - hw) / 4.f, ((float)pb_image_row(a, crow) - hh) / 4.f, 0.f);
+            const f3 d = mk(0.f, 0.f, 1.f);
+            float tm;
+            flag = !ray_box(o, mk(1.f / d.x, 1.f / d.y, 1.f / d.z), b2.z, b2.w, b3.x, b3.y, b3.z, b3.w, true,
+                            key_t(key), tm);
+        }
+        if (emit && key != NO_HIT && !flag) {
+            const uint32_t tri = __float_as_uint(a.leaf[4 * (size_t)(uint32_t)key + 2].y) & ~LEAF_BIT;
+            const uint32_t mi = TCS == 4 ? __float_as_uint(a.tclip[TCS * (size_t)tri + 3].w) : a.matidx[tri];
+            live = 0 < a.mats[mi].shininess / 1000.f * 1;
+        }
+        const uint64_t livem = __ballot(live), flagm = CERT ? __ballot(flag) : 0ull;
+        const uint32_t st = w + i * (NT / 64);
+        if (lane == 0) {
+            s_cnt[st] = (uint32_t)__popcll(livem);
+            s_mask[st] = livem;
+            s_mask[NSUB + st] = flagm;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t k = 0; k < NSUB; k++) {
+            const uint32_t v = s_cnt[k];
+            s_cnt[k] = run;
+            run += v;
+        }
+        s_base = run && emit ? atomicAdd(qcount, run) : 0u;
+    }
+    __syncthreads();
+    const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(s_base);
+    uint32_t hits = 0, tex = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < NST; i++) {
+        uint32_t x, crow;
+        const bool valid = pixel(i, x, crow);
+        const uint32_t st = w + i * (NT / 64);
+        // (wave-uniform: into SGPRs, so the shading below keeps its VGPRs)
+        const auto uni64 = [](uint64_t v) {
+            return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
+                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32;
+        };
+        const uint64_t livem = uni64(s_mask[st]), flagm = CERT ? uni64(s_mask[NSUB + st]) : 0ull;
+        const uint32_t qb = sbase + (uint32_t)__builtin_amdgcn_readfirstlane(s_cnt[st]);
+        const bool flag = CERT && ((flagm >> lane) & 1u);
+        if (CERT && flagm) {   // (rare) the re-trace list, one atomic per wave
+            const uint32_t slot = wave_append(flag, redo_count);
+            if (flag) redo[slot] = crow * a.W + x;
+        }
+        if (valid && !flag) {
+            const TraceArgs& a = kernel_trace_args();   // (a is the kernel's first argument: k_primary_binned, k_pb_shade)
+            const uint64_t key = key_at(crow, x);
+            const f3 o = mk(((float)x - hw) / 4.f, ((float)pb_image_row(a, crow) - hh) / 4.f, 0.f);
+            const bool phit = key != NO_HIT;
+            uint32_t h1 = 0, t1 = 0;
+            RayQ e;
+            // (the live rays were counted above: this lane's queue entry is known before the shading)
+            RayQ* dst = emit && ((livem >> lane) & 1u) ? q + qb + lane_rank(livem)
+                                                        : nullptr;
+            (void)primary_pixel<REC>(a, (size_t)crow * a.W + x, o, mk(0.f, 0.f, 1.f), phit, phit ? key_t(key) : 0.f,
+                                     phit ? (uint32_t)key : 0u, h1, t1, e, dst);
+            hits += h1;
+            tex += t1;
+        }
+    }
+    if (COUNT) {
+        Counts c = {0, 0, 0, 0, 0};
+        flush_counts<COUNT>(a, c, hits, tex, 2);
+    }
+}
 // FUSE (the default; RTBVH_PB_FUSE=0 builds the separate k_pb_shade launch, A/B): the tile's shading (k_pb_shade's work, pb_shade_tile) at the end of the
 // same workgroup, from the keys in LDS -- no keys round trip through HBM, one launch fewer, and a tile's
 // dependent shading gathers run beside other tiles' rasterisation on the CU
@@ -1224,120 +1410,6 @@ __global__ __launch_bounds__(RB, RTBVH_PB_WAVES) void k_primary_binned(TraceArgs
 #define RTBVH_PB_SHADE_BLOCK 1024
 #endif
 constexpr uint32_t PB_SHADE_BLOCK = RTBVH_PB_SHADE_BLOCK;
-// CERT (the certified pass, DESIGN.md 3): the binned pass tested every leaf whose triangle could be
-// accepted below a pixel's bound (its depth key, margin.h); a pixel's (t, leaf) is the reference's when
-// the leaf's own box passes the reference slab test with the bound t (k_bounce_shade's leaf_certified,
-// here from the leaf record's box).  Pixels that fail it go to the re-trace list (redo: compact pixel
-// index) and are left to k_primary_redo, outside the block's bounce-queue claim.
-// One tile of k_pb_shade's work over NT threads, the pixels' keys from key_at(compact row, x).  s_cnt: 16
-// words of LDS, s_mask: 2 x 16 words, s_base: one.  The 16 sub-tiles of 8 x 8 pixels go to the waves in
-// turn; a first pass counts each one's live rays (and certificates) into LDS, the tile claims its queue
-// range, then a second pass shades them (no per-sub-tile registers held across the claim).
-// (Inlined: out of line, A/B round 5, the fused binned pass took 1.07 ms against 0.86.)
-// The kernel's TraceArgs (its first argument) read again from the kernel-argument segment where they are used:
-// scalar loads the compiler cannot hoist out of a loop (held in SGPRs across the shading loop's iterations they
-// spilled into VGPR lanes, and the shading's VGPRs to scratch)
-__device__ __forceinline__ const TraceArgs& kernel_trace_args() {
-    auto p = (const __attribute__((address_space(4))) TraceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return *(const TraceArgs*)p;
-}
-template <bool COUNT, bool CERT, uint32_t NT, bool REC, class KeyAt>
-__device__ __forceinline__ void pb_shade_tile(const TraceArgs& a, uint32_t rows, KeyAt&& key_at, RayQ* __restrict__ q,
-                                              uint32_t* __restrict__ qcount, int emit, uint32_t* __restrict__ redo,
-                                              uint32_t* __restrict__ redo_count, uint32_t* s_cnt, uint64_t* s_mask,
-                                              uint32_t& s_base) {
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-    const uint32_t X0 = blockIdx.x * PB_TILE, C0 = blockIdx.y * PB_TILE;
-    constexpr uint32_t NST = (PB_TILE / 8) * (PB_TILE / 8) / (NT / 64);   // sub-tiles per wave
-    constexpr uint32_t NSUB = (PB_TILE / 8) * (PB_TILE / 8);
-    const float hw = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(a.W >> 1))));
-    const float hh = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(a.H >> 1))));
-    const auto pixel = [&](uint32_t i, uint32_t& x, uint32_t& crow) {
-        const uint32_t st = w + i * (NT / 64);
-        x = X0 + (st % (PB_TILE / 8)) * 8 + (lane & 7u);
-        crow = C0 + (st / (PB_TILE / 8)) * 8 + (lane >> 3);
-        return x < a.W && crow < rows;
-    };
-    // the live reflection rays: hit, and the hit material's shininess > 0
-#pragma unroll 1
-    for (uint32_t i = 0; i < NST; i++) {
-        uint32_t x, crow;
-        const bool valid = pixel(i, x, crow);
-        const uint64_t key = valid ? key_at(crow, x) : NO_HIT;
-        bool live = false, flag = false;
-        if (CERT && key != NO_HIT) {   // the certificate: the leaf's box, the reference slab test at t
-            const float4 b2 = a.leaf[4 * (size_t)(uint32_t)key + 2], b3 = a.leaf[4 * (size_t)(uint32_t)key + 3];
-            const f3 o = mk(((float)x - hw) / 4.f, ((float)pb_image_row(a, crow) - hh) / 4.f, 0.f);
-            const f3 d = mk(0.f, 0.f, 1.f);
-            float tm;
-            flag = !ray_box(o, mk(1.f / d.x, 1.f / d.y, 1.f / d.z), b2.z, b2.w, b3.x, b3.y, b3.z, b3.w, true,
-                            key_t(key), tm);
-        }
-        if (emit && key != NO_HIT && !flag) {
-            const uint32_t tri = __float_as_uint(a.leaf[4 * (size_t)(uint32_t)key + 2].y) & ~LEAF_BIT;
-            const uint32_t mi = TCS == 4 ? __float_as_uint(a.tclip[TCS * (size_t)tri + 3].w) : a.matidx[tri];
-            live = 0 < a.mats[mi].shininess / 1000.f * 1;
-        }
-        const uint64_t livem = __ballot(live), flagm = CERT ? __ballot(flag) : 0ull;
-        const uint32_t st = w + i * (NT / 64);
-        if (lane == 0) {
-            s_cnt[st] = (uint32_t)__popcll(livem);
-            s_mask[st] = livem;
-            s_mask[NSUB + st] = flagm;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (uint32_t k = 0; k < NSUB; k++) {
-            const uint32_t v = s_cnt[k];
-            s_cnt[k] = run;
-            run += v;
-        }
-        s_base = run && emit ? atomicAdd(qcount, run) : 0u;
-    }
-    __syncthreads();
-    const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(s_base);
-    uint32_t hits = 0, tex = 0;
-#pragma unroll 1
-    for (uint32_t i = 0; i < NST; i++) {
-        uint32_t x, crow;
-        const bool valid = pixel(i, x, crow);
-        const uint32_t st = w + i * (NT / 64);
-        // (wave-uniform: into SGPRs, so the shading below keeps its VGPRs)
-        const auto uni64 = [](uint64_t v) {
-            return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
-                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32;
-        };
-        const uint64_t livem = uni64(s_mask[st]), flagm = CERT ? uni64(s_mask[NSUB + st]) : 0ull;
-        const uint32_t qb = sbase + (uint32_t)__builtin_amdgcn_readfirstlane(s_cnt[st]);
-        const bool flag = CERT && ((flagm >> lane) & 1u);
-        if (CERT && flagm) {   // (rare) the re-trace list, one atomic per wave
-            const uint32_t slot = wave_append(flag, redo_count);
-            if (flag) redo[slot] = crow * a.W + x;
-        }
-        if (valid && !flag) {
-            const TraceArgs& a = kernel_trace_args();   // (a is the kernel's first argument: k_primary_binned, k_pb_shade)
-            const uint64_t key = key_at(crow, x);
-            const f3 o = mk(((float)x - hw) / 4.f, ((float)pb_image_row(a, crow) - hh) / 4.f, 0.f);
-            const bool phit = key != NO_HIT;
-            uint32_t h1 = 0, t1 = 0;
-            RayQ e;
-            // (the live rays were counted above: this lane's queue entry is known before the shading)
-            RayQ* dst = emit && ((livem >> lane) & 1u) ? q + qb + lane_rank(livem)
-                                                        : nullptr;
-            (void)primary_pixel<REC>(a, (size_t)crow * a.W + x, o, mk(0.f, 0.f, 1.f), phit, phit ? key_t(key) : 0.f,
-                                     phit ? (uint32_t)key : 0u, h1, t1, e, dst);
-            hits += h1;
-            tex += t1;
-        }
-    }
-    if (COUNT) {
-        Counts c = {0, 0, 0, 0, 0};
-        flush_counts<COUNT>(a, c, hits, tex, 2);
-    }
-}
 template <bool COUNT, bool CERT>
 __global__ __launch_bounds__(PB_SHADE_BLOCK, 8) void k_pb_shade(TraceArgs a, const uint32_t* __restrict__ off, uint32_t cap,
                                                     uint32_t ntx, uint32_t rows,
@@ -1404,23 +1476,24 @@ __global__ __launch_bounds__(BLOCK, 8) void k_bounce(TraceArgs a, const RayQ* __
         RayQ e;
         if (i < n) {
             e = qin[perm ? perm[i] : i];
-            const f3 o = mk(e.ox, e.oy, e.oz), d = mk(e.dx, e.dy, e.dz);
-            const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            f3 o, d, inv;
+            load_ray(&e, o, d, inv);
             float best;
             uint32_t bl;
             float4 col = a.color[e.idx];
             float intensity = e.intensity;
+            const int lim = LIM ? a.stack_limit : STACK_SIZE;
 #ifdef RTBVH_BOUNCE_PROBE   // cost probes (A/B builds, wrong frames): 1 no walk (every ray misses), 2 no shading
             const bool th = RTBVH_BOUNCE_PROBE == 1 ? false
-                                                    : traverse<COUNT, NEAREST, LANE_LSB>(a.inner, a.leaf, a.T, o, d, inv,
-                                                          LIM ? a.stack_limit : STACK_SIZE, best, bl, c, s_lst + threadIdx.x);
+                                                    : traverse<COUNT, NEAREST, LANE_LSB>(RecordTree{a.inner}, a.leaf, a.T, o,
+                                                          d, inv, lim, best, bl, c, s_lst + threadIdx.x);
             if (RTBVH_BOUNCE_PROBE == 2 && th) {
                 hits++;
                 col = make_float4(best, (float)bl, 0.f, 1.f);
             } else if (th) {
 #else
-            if (traverse<COUNT, NEAREST, LANE_LSB>(a.inner, a.leaf, a.T, o, d, inv, LIM ? a.stack_limit : STACK_SIZE,
-                                                   best, bl, c, s_lst + threadIdx.x)) {
+            if (traverse<COUNT, NEAREST, LANE_LSB>(RecordTree{a.inner}, a.leaf, a.T, o, d, inv, lim, best, bl, c,
+                                                   s_lst + threadIdx.x)) {
 #endif
                 hits++;
                 const HitInfo h = shade_hit(a, bl, o, d, best);
@@ -1478,6 +1551,38 @@ __device__ __forceinline__ uint32_t claim_segment(uint32_t k) {   // the wave's 
     const uint32_t g = (xcd + k / SEGS_PER_XCD) % XCDS;
     return g * SEGS_PER_XCD + (sub + k) % SEGS_PER_XCD;
 }
+// segment seg of a queue of n rays: positions [s0, s0 + len)
+__device__ __forceinline__ void segment_bounds(uint32_t n, uint32_t seg, uint32_t& s0, uint32_t& len) {
+    s0 = (uint32_t)((uint64_t)n * seg / NEXT_SEGS);
+    len = (uint32_t)((uint64_t)n * (seg + 1) / NEXT_SEGS) - s0;
+}
+// The refill of a persistent walk (all lanes converged; has: this lane holds a ray).  Once REFILL_MIN lanes are
+// idle the wave claims that many positions of its current segment with one atomic, and start(p) hands queue
+// position p to each idle lane that got one.  Every refill either hands out rays or moves on to the next segment
+// (the last one sets `drained`), so a wave with no ray left comes back here until the queue is drained.
+struct Refill {
+    bool drained = false;
+    uint32_t kseg = 0;   // segments claimed from so far (wave-uniform)
+};
+template <class Start>
+__device__ __forceinline__ void refill_claim(Refill& rf, uint32_t* __restrict__ next, uint32_t n, bool has,
+                                             Start&& start) {
+    const uint64_t idle = __ballot(!has);
+    const uint32_t nidle = (uint32_t)__popcll(idle);
+    if (!rf.drained && (nidle >= REFILL_MIN || nidle == 64)) {
+        const uint32_t seg = claim_segment(rf.kseg);
+        uint32_t s0, len;
+        segment_bounds(n, seg, s0, len);
+        uint32_t base = 0;
+        if (lane_id() == 0) base = atomicAdd(next + NEXT_STRIDE * seg, nidle);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base + nidle >= len && ++rf.kseg == NEXT_SEGS) rf.drained = true;   // segment (and the last) used up
+        if (!has) {
+            const uint32_t p = base + lane_rank(idle);
+            if (p < len) start(s0 + p);
+        }
+    }
+}
 
 __device__ __forceinline__ void sort2(float& ta, uint32_t& ia, float& tb, uint32_t& ib) {
     const bool sw = tb < ta;
@@ -1508,6 +1613,16 @@ __device__ __forceinline__ float bf16_up(uint16_t h) { return __uint_as_float((u
 // rounded toward -inf (6 B each; the pop's prune test on the rounded-down distance keeps
 // every entry the exact test keeps), deeper entries as full pairs in scratch.
 constexpr int SB = 16;   // 16 x 4 B x 256 lanes = 16 KB per block
+// the binary modes' stack (a Stack of the shared step): `col`: this lane's LDS column, entry k at col[k * BLOCK];
+// `deep`: the kernel's scratch array of the entries [SB, STACK_SIZE)
+struct BlockStack {
+    uint32_t *col, *deep;
+    __device__ __forceinline__ void store(int k, uint32_t v) {
+        if (k < SB) col[k * BLOCK] = v;
+        else deep[k - SB] = v;
+    }
+    __device__ __forceinline__ uint32_t load(int k) const { return k < SB ? col[k * BLOCK] : deep[k - SB]; }
+};
 // 13 x 6 B x 256 lanes = 19.5 KB per block: 8 blocks per CU in 160 KB.  A/B (C5 bounce stage):
 // 8 entries 2.75-2.77 ms (deeper entries go to scratch), 12 2.50-2.55, 13 2.47-2.52, 14 2.51-2.53
 // (7 blocks per CU)
@@ -1611,13 +1726,11 @@ template <bool COUNT>
 __device__ __forceinline__ float2 defer_walk(const Inner* __restrict__ inner, const uint4* __restrict__ topo,
                                              const float* __restrict__ nbox, const float4* __restrict__ leaf,
                                              uint32_t T, const RayQ* e, Counts& c) {
-    const float4 q0 = reinterpret_cast<const float4*>(e)[0], q1 = reinterpret_cast<const float4*>(e)[1];
-    const f3 o = mk(q0.z, q0.w, q1.x), d = mk(q1.y, q1.z, q1.w);
-    const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+    f3 o, d, inv;
+    load_ray(e, o, d, inv);
     float best;
     uint32_t bl;
-    const bool h = nbox ? traverse_nb<COUNT>(topo, nbox, leaf, T, o, d, inv, best, bl, c)
-                        : traverse<COUNT, false>(inner, leaf, T, o, d, inv, STACK_SIZE, best, bl, c);
+    const bool h = traverse_ref<COUNT>(nbox != nullptr, inner, topo, nbox, leaf, T, o, d, inv, best, bl, c);
     const uint32_t tri = h ? __float_as_uint(leaf[4 * (size_t)bl + 2].y) & ~LEAF_BIT : INVALID;
     return make_float2(h ? -best : -__builtin_inff(), __uint_as_float(tri));
 }
@@ -1685,14 +1798,110 @@ constexpr uint32_t DEFER_WORKERS = RTBVH_DEFER_WORKERS;
 constexpr uint32_t ESHADE_RAYS = RTBVH_ESHADE_RAYS;   // queue positions per shading workgroup
 // hit-record words of a certified pass with early shading (RTBVH_EARLY_SHADE): not written yet, and shaded already
 constexpr uint32_t HIT_NOT_READY = 0xFFFFFFFFu, HIT_SHADED = 0xFFFFFFFEu;   // (x words: NaN patterns no walk writes)
+// RayTraceReflection.hlsl:19-60 for one queued ray e from its closest hit (tri at t; tri INVALID: a
+// miss): colour, intensity, the reflectRay record, and the next ray in e (returns whether it is live)
+__device__ __forceinline__ bool bounce_apply(const TraceArgs& a, RayQ& e, uint32_t tri, float t, uint32_t& hits,
+                                             uint32_t& tex) {
+    f3 o, d, inv;
+    load_ray(&e, o, d, inv);
+    float4 col = a.color[e.idx];
+    float intensity = e.intensity;
+    bool live = false;
+    if (tri != INVALID) {
+        hits = 1;
+        const HitInfo h = shade_hit_tri(a, tri, o, d, t);
+        tex = h.textured;
+        col = make_float4(lerpf(col.x, h.color.x, intensity), lerpf(col.y, h.color.y, intensity),
+                          lerpf(col.z, h.color.z, intensity), lerpf(col.w, h.color.w, intensity));
+        intensity *= h.shininess / 1000.f * 1;
+        const f3 ro = add(h.hitp, mul(h.nrm, .0001f));   // RAY_OFFSET .0001
+        const f3 rd = normalize(reflect(d, h.nrm));
+        e.intensity = intensity;
+        e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
+        e.dx = rd.x; e.dy = rd.y; e.dz = rd.z;
+        live = 0 < intensity;
+        if (a.refl_rec) put_record(a.refl_rec, e.idx, intensity, true, ro, rd, col);   // :42-46
+    } else {
+        col = make_float4(lerpf(col.x, .5f, intensity), lerpf(col.y, .5f, intensity),
+                          lerpf(col.z, .5f, intensity), lerpf(col.w, 1.f, intensity));
+        intensity = 0.f;
+        if (a.refl_rec) {   // :50-55: the ray stays, intensity 0, colour blended
+            float* r = a.refl_rec + 14 * (size_t)e.idx;
+            r[0] = 0.f;
+            r[10] = col.x; r[11] = col.y; r[12] = col.z; r[13] = col.w;
+        }
+    }
+    a.color[e.idx] = col;
+    if (a.intensity) a.intensity[e.idx] = intensity;
+    return live;
+}
+
+// The certificate of a certified walk's hit (DESIGN.md 3): the reference's findCollision
+// (RayTraceTraversal.hlsl:106-193) reaches leaf x -- and, the walk having seen every triangle that could
+// be accepted at t <= its best, returns x -- when x's own box passes the reference slab test with the
+// bound t (every box above contains it: the slab test is monotone in the box, so they pass too, at every
+// bound the reference holds, all >= t).  The box is the leaf's: min / max of its clip-space vertices
+// (build.hip leaf_record_words, MortonCodes.hlsl:87-96), from the triangle's record.
+__device__ __forceinline__ bool leaf_certified(const TraceArgs& a, uint32_t tri, f3 o, f3 inv, float t) {
+    const float4* P = a.tclip + TCS * (size_t)tri;
+    const float4 a0 = P[0], a1 = P[1], a2 = P[2];
+    const f3 v0 = mk(a0.x, a0.y, a0.z), v1 = mk(a1.x, a1.y, a1.z), v2 = mk(a2.x, a2.y, a2.z);
+    const f3 lo = vmin(vmin(v0, v1), v2), hi = vmax(vmax(v0, v1), v2);
+    float tm;
+    return ray_box(o, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, true, t, tm);
+}
+
+// RayTraceReflection.hlsl:19-60 for queued ray i from its hit record h2 (valid: i is a ray to shade now).  CERT: a ray
+// whose walk flagged it or whose hit fails the certificate is flagged (the caller lists it for the re-trace) instead
 template <bool CERT>
 __device__ __forceinline__ void bounce_shade_ray(const TraceArgs& a, const RayQ* __restrict__ qin, uint32_t i, float2 h2,
                                                  bool valid, RayQ& e, bool& live, bool& flagged, uint32_t& hits,
-                                                 uint32_t& tex);
+                                                 uint32_t& tex) {
+    live = false;
+    flagged = false;
+    if (!valid) return;
+    e = qin[i];
+    uint32_t tri = __float_as_uint(h2.y);
+    bool skip = false;
+    if (CERT) {
+        flagged = hit_flagged(tri);
+        tri = (tri & LEAF_BIT) ? INVALID : tri & ~HIT_FLAG;
+        if (signbit(h2.x)) {   // the walk's deferred rays (trace.hip DEFER_*): walked in the reference order
+            skip = flagged;    //   by the walk's drained waves (exact: shaded as is), or by k_bounce_redo
+            flagged = false;
+            h2.x = -h2.x;
+        } else if (!flagged && tri != INVALID) {
+            f3 o, d, inv;
+            load_ray(&e, o, d, inv);
+            flagged = !leaf_certified(a, tri, o, inv, h2.x);
+        }
+    }
+    if (!flagged && !skip) live = bounce_apply(a, e, tri, h2.x, hits, tex);
+}
+// ... and its outputs (all lanes of the wave call this): a flagged ray appended to the re-trace list, a live next
+// ray to the next queue; hits, tex: the caller's running counts.  k_bounce_shade's work per ray, and the walk's
+// early-shading workgroups'.  Inlined: the early-shading role's shading spills 13 VGPRs in its own blocks (the
+// walk's loop has none: its scratch accesses are the deep stack's, as in the plain instance); as an out-of-line
+// call it made the one-frame walk 2.70 -> 3.16 ms (r06_hab3)
+template <bool CERT>
+__device__ __forceinline__ void bounce_shade_emit(const TraceArgs& a, const RayQ* qin, uint32_t i, float2 h2, bool valid,
+                                                  RayQ* qout, uint32_t* qout_count, int emit, uint32_t* redo,
+                                                  uint32_t* redo_count, uint32_t& hits, uint32_t& tex) {
+    RayQ e;
+    bool live, flagged;
+    uint32_t h1 = 0, t1 = 0;   // (bounce_apply sets them: one ray's)
+    bounce_shade_ray<CERT>(a, qin, i, h2, valid, e, live, flagged, h1, t1);
+    hits += h1;
+    tex += t1;
+    if (CERT) {
+        const uint32_t rs = wave_append(flagged, redo_count);
+        if (flagged) redo[rs] = i;
+    }
+    const uint32_t qs = wave_append(emit && live, qout_count);
+    if (emit && live) qout[qs] = e;
+}
 // ES: the instance with early shading (a frame traced one at a time); the walk without it (frames in flight) is its
-// own instance without the shading role's code.  The role's shading spills 13 VGPRs in its own blocks (the walk's
-// loop has none: its scratch accesses are the deep stack's, as in the plain instance); as an out-of-line call it
-// made the one-frame walk 2.70 -> 3.16 ms (r06_hab3)
+// own instance without the shading role's code (bounce_shade_emit, inlined: see there).
 template <bool COUNT, int MODE, bool LIM, bool GUARD, bool CERT = false, bool ES = false>
 __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner* __restrict__ inner,
                                                           const QNode* __restrict__ qn,
@@ -1739,16 +1948,7 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
                 }
                 h2 = make_float2(__uint_as_float(xb), __uint_as_float(yb));
             }
-            RayQ e;
-            bool live, flagged;
-            uint32_t h1 = 0, t1 = 0;   // (bounce_apply sets them: one ray's)
-            bounce_shade_ray<true>(ta, qin, i, h2, valid, e, live, flagged, h1, t1);
-            hits += h1;
-            tex += t1;
-            const uint32_t rs = wave_append(flagged, redo_count);
-            if (flagged) redo[rs] = i;
-            const uint32_t qs = wave_append(emit && live, qout_count);
-            if (emit && live) qout[qs] = e;
+            bounce_shade_emit<true>(ta, qin, i, h2, valid, qout, qout_count, emit, redo, redo_count, hits, tex);
         }
         if (COUNT) flush_counts<COUNT>(ta, c, hits, tex, 5);
         return;
@@ -1763,8 +1963,8 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
             // those being claimed right now
             bool used = true;
             for (uint32_t seg = lane; seg < NEXT_SEGS; seg += 64) {
-                const uint32_t s0 = (uint32_t)((uint64_t)n * seg / NEXT_SEGS);
-                const uint32_t len = (uint32_t)((uint64_t)n * (seg + 1) / NEXT_SEGS) - s0;
+                uint32_t s0, len;
+                segment_bounds(n, seg, s0, len);
                 used = used && __hip_atomic_load(next + NEXT_STRIDE * seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= len;
             }
             if (__ballot(!used) == 0) break;
@@ -1773,10 +1973,7 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
         defer_walk_all<COUNT>(next, defer, inner, topo, nbox, leaf, T, qin, hitrec, c, wt);
         if (COUNT) {
             unsigned long long v[2] = {c.internal, c.leaf};
-#pragma unroll
-            for (int k = 0; k < 2; k++)
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+            wave_sum(v);
             if (lane == 0) {
                 atomicAdd(&counters[5], v[0]);
                 atomicAdd(&counters[6], v[1]);
@@ -1784,12 +1981,14 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
         }
         return;
     }
-    bool has = false, hit = false, qfast = false;
-    uint32_t r = 0, node = 0, top = INVALID, bl = 0, guard = 0;
+    bool has = false, qfast = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // the ray's walk; the 4-wide walk uses its node, sp and guard
+    uint32_t& node = w.node;
+    int& sp = w.sp;
+    uint32_t& guard = w.guard;
     uint32_t btri = 0;       // triangle of the best hit (leaf record word 9): the hit record's id
     uint64_t key = NO_HIT;   // WIDE: the lexicographic (t, leaf) minimum (hit / best / bl of the binary walks)
-    int sp = 0;
-    float best = 0.f;
     f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
     // CERT: the per-node margin's coefficients (margin.h rho_n; each QNode carries its node's edge bound
     // and margin range) and the ray's flag
@@ -1797,18 +1996,11 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
     bool flg = false;
     __shared__ uint32_t s_stk[WIDE ? 1 : SB][WIDE ? 1 : BLOCK];   // (none for WIDE: its LDS is the 6-B stack)
     uint32_t stack[WIDE ? 1 : STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    const uint32_t tid = threadIdx.x;
+    BlockStack st{&s_stk[0][0] + (WIDE ? 0u : tid), stack};
     __shared__ uint32_t s_wid[WIDE ? SW : 1][BLOCK];
     __shared__ uint16_t s_wt[WIDE ? SW : 1][BLOCK];
     uint2 wstack[WIDE ? STACK4B - SW : 1];       // entries [SW, STACK4B)
-    const uint32_t tid = threadIdx.x;
-    auto spush = [&](uint32_t v) {
-        if (sp < SB) s_stk[sp][tid] = v;
-        else stack[sp - SB] = v;
-        ++sp;
-    };
-    auto spop_top = [&]() {   // --sp; refill the cached top from entry sp
-        if (--sp >= 0) top = sp < SB ? s_stk[sp][tid] : stack[sp - SB];
-    };
     auto wpush = [&](uint32_t id, float t) {
         if (sp < SW) {
             s_wid[sp][tid] = id;
@@ -1906,59 +2098,32 @@ ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, 
         sort2(k1, i1, k3, i3);
         sort2(k1, i1, k2, i2);
     };
-    bool drained = false;
-    uint32_t kseg = 0;   // segments claimed from so far (wave-uniform)
+    Refill rf;
     unsigned long long wsteps = 0, mixed = 0, active_lanes = 0;
     while (true) {
-        const uint64_t idle = __ballot(!has);
-        const uint32_t nidle = (uint32_t)__popcll(idle);
-        if (!drained && (nidle >= REFILL_MIN || nidle == 64)) {
-            const uint32_t seg = claim_segment(kseg);
-            const uint32_t s0 = (uint32_t)((uint64_t)n * seg / NEXT_SEGS);
-            const uint32_t len = (uint32_t)((uint64_t)n * (seg + 1) / NEXT_SEGS) - s0;
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(next + NEXT_STRIDE * seg, nidle);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + nidle >= len && ++kseg == NEXT_SEGS) drained = true;   // segment (and the last) used up
-            if (!has) {
-                const uint32_t p = base + lane_rank(idle);
-                if (p < len) {
-                    r = perm ? perm[s0 + p] : s0 + p;
-                    const float4 q0 = reinterpret_cast<const float4*>(qin + r)[0];
-                    const float4 q1 = reinterpret_cast<const float4*>(qin + r)[1];
-                    o = mk(q0.z, q0.w, q1.x);
-                    d = mk(q1.y, q1.z, q1.w);
-                    inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
-                    qfast = WIDE && qnode_fast_ray(o, inv);
-                    has = true;
-                    hit = false;
-                    best = 0.f;
-                    bl = 0;
-                    key = NO_HIT;
-                    sp = 0;
-                    top = INVALID;
-                    node = root_slot(T);
-                    guard = 2 * T + 2;
-                    if (CERT) {   // a ray the margin does not cover is deferred (DEFER_* below)
-                        flg = !(qfast && dot(d, d) <= MT_DD);
-                        if (flg) {
-                            // the "deferred" record first, then the entry with release order: a wave that takes
-                            // the entry (acquire) writes the walk's record after this one, never under it
-                            const float2 mk_def = make_float2(-__builtin_inff(), __uint_as_float(INVALID ^ HIT_FLAG));
-                            if (wt) st_hitrec(hitrec + r, mk_def);
-                            else hitrec[r] = mk_def;
-                            const uint32_t k = atomicAdd(next + DEFER_COUNT, 1u);
-                            __hip_atomic_store(defer + k, r | DEFER_VALID, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                            has = false;
-                            flg = false;
-                        }
-                    }
+        refill_claim(rf, next, n, has, [&](uint32_t p) {   // this lane takes the p-th ray of the queue
+            r = perm ? perm[p] : p;
+            load_ray(qin + r, o, d, inv);
+            qfast = WIDE && qnode_fast_ray(o, inv);
+            has = true;
+            w = walk_start(root_slot(T), T);
+            key = NO_HIT;
+            if (CERT) {   // a ray the margin does not cover is deferred (DEFER_* below)
+                flg = !(qfast && dot(d, d) <= MT_DD);
+                if (flg) {
+                    // the "deferred" record first, then the entry with release order: a wave that takes
+                    // the entry (acquire) writes the walk's record after this one, never under it
+                    const float2 mk_def = make_float2(-__builtin_inff(), __uint_as_float(INVALID ^ HIT_FLAG));
+                    if (wt) st_hitrec(hitrec + r, mk_def);
+                    else hitrec[r] = mk_def;
+                    const uint32_t k = atomicAdd(next + DEFER_COUNT, 1u);
+                    __hip_atomic_store(defer + k, r | DEFER_VALID, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                    has = false;
+                    flg = false;
                 }
             }
-        }
-        // every refill either hands out rays or moves on to the next segment (the last one
-        // sets `drained`), so a wave with no ray left loops back to refill until the queue is drained
-        if (__ballot(has) == 0 && drained) break;
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
         if (COUNT) {   // wave-level divergence census (stats trav_*; all lanes converged here)
             const uint64_t act = __ballot(has);
             const uint64_t lf = __ballot(has && (node & LEAF_BIT) != 0);
@@ -2056,58 +2221,29 @@ ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, 
             if (GUARD && --guard == 0) {
                 c.overflow++;
                 done = true;
-            } else if (isleaf) {
-                const uint32_t j = node & ~LEAF_BIT;
-                if (COUNT) c.leaf++;
-                const float t = ray_triangle(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x));
-                if (t != -1.f && (!hit || t < best || (NEAREST && t == best && j < bl))) {
-                    best = t;
-                    bl = j;
-                    btri = __float_as_uint(q2.y) & ~LEAF_BIT;
-                    hit = true;
-                }
-                node = top;                             // pop
-                spop_top();
-                done = sp == -1;
             } else {
-                if (COUNT) c.internal++;
-                const uint32_t own = __float_as_uint(q3.z);
-                const uint32_t cl = child_slot(__float_as_uint(q3.x), own, 0), cr = child_slot(__float_as_uint(q3.y), own, 1);
-                float tl, tr;
-                const bool lh = ray_box_xy(o, inv, q0.xy, q0.zw, q2.x, q2.y, hit, best, tl);
-                const bool rh = ray_box_xy(o, inv, q1.xy, q1.zw, q2.z, q2.w, hit, best, tr);
-                if (!lh && !rh) {
-                    node = top;                             // pop
-                    spop_top();
-                    done = sp == -1;
+                if (isleaf) {
+                    if (walk_leaf<COUNT>(w, st, WalkRule<NEAREST>{}, c, o, d, node & ~LEAF_BIT, mk(q0.x, q0.y, q0.z),
+                                         mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x)))
+                        btri = __float_as_uint(q2.y) & ~LEAF_BIT;
                 } else {
-                    const bool swap = NEAREST && lh && rh && tr < tl;
-                    if (lh && rh) {
-                        if (sp + 1 >= limit) {
-                            c.overflow++;
-                            node = top;
-                            spop_top();
-                            done = sp == -1;
-                        } else {
-                            spush(top);                     // push the second child
-                            top = swap ? cl : cr;
-                            node = swap ? cr : cl;
-                        }
-                    } else {
-                        node = lh ? cl : cr;
-                    }
+                    const uint32_t own = __float_as_uint(q3.z);
+                    walk_node<COUNT>(w, st, WalkRule<NEAREST>{}, c, o, inv, limit,
+                                     record_children(q0, q1, q2, child_slot(__float_as_uint(q3.x), own, 0),
+                                                     child_slot(__float_as_uint(q3.y), own, 1)));
                 }
+                done = sp == -1;
             }
         }
         if (done) {
             // (t, triangle) of the hit, INVALID for a miss: the shading reads no leaf record
             if (WIDE) {
-                uint32_t w = key != NO_HIT ? btri : INVALID;
-                if (CERT && flg) w ^= HIT_FLAG;   // (a hit: bit 30 set; a miss: bit 30 cleared)
-                if (CERT && wt) st_hitrec(hitrec + r, make_float2(key_t(key), __uint_as_float(w)));
-                else hitrec[r] = make_float2(key_t(key), __uint_as_float(w));
+                uint32_t id = key != NO_HIT ? btri : INVALID;
+                if (CERT && flg) id ^= HIT_FLAG;   // (a hit: bit 30 set; a miss: bit 30 cleared)
+                if (CERT && wt) st_hitrec(hitrec + r, make_float2(key_t(key), __uint_as_float(id)));
+                else hitrec[r] = make_float2(key_t(key), __uint_as_float(id));
             }
-            else hitrec[r] = make_float2(best, __uint_as_float(hit ? btri : INVALID));
+            else hitrec[r] = make_float2(w.best, __uint_as_float(w.hit ? btri : INVALID));
             has = false;
             if (COUNT && GUARD) {   // walk length census (stats trav_max_steps / trav_steps_log2)
                 const uint32_t steps = 2 * T + 2 - guard;
@@ -2132,10 +2268,7 @@ ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, 
     }
     if (COUNT || __ballot(c.overflow != 0)) {
         unsigned long long v[3] = {c.internal, c.leaf, c.overflow};
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+        wave_sum(v);
         if (lane == 0) {
             if (COUNT) {
                 atomicAdd(&counters[5], v[0]);
@@ -2152,84 +2285,6 @@ ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, 
     }
 }
 
-// RayTraceReflection.hlsl:19-60 for one queued ray e from its closest hit (tri at t; tri INVALID: a
-// miss): colour, intensity, the reflectRay record, and the next ray in e (returns whether it is live)
-__device__ __forceinline__ bool bounce_apply(const TraceArgs& a, RayQ& e, uint32_t tri, float t, uint32_t& hits,
-                                             uint32_t& tex) {
-    const f3 o = mk(e.ox, e.oy, e.oz), d = mk(e.dx, e.dy, e.dz);
-    float4 col = a.color[e.idx];
-    float intensity = e.intensity;
-    bool live = false;
-    if (tri != INVALID) {
-        hits = 1;
-        const HitInfo h = shade_hit_tri(a, tri, o, d, t);
-        tex = h.textured;
-        col = make_float4(lerpf(col.x, h.color.x, intensity), lerpf(col.y, h.color.y, intensity),
-                          lerpf(col.z, h.color.z, intensity), lerpf(col.w, h.color.w, intensity));
-        intensity *= h.shininess / 1000.f * 1;
-        const f3 ro = add(h.hitp, mul(h.nrm, .0001f));   // RAY_OFFSET .0001
-        const f3 rd = normalize(reflect(d, h.nrm));
-        e.intensity = intensity;
-        e.ox = ro.x; e.oy = ro.y; e.oz = ro.z;
-        e.dx = rd.x; e.dy = rd.y; e.dz = rd.z;
-        live = 0 < intensity;
-        if (a.refl_rec) put_record(a.refl_rec, e.idx, intensity, true, ro, rd, col);   // :42-46
-    } else {
-        col = make_float4(lerpf(col.x, .5f, intensity), lerpf(col.y, .5f, intensity),
-                          lerpf(col.z, .5f, intensity), lerpf(col.w, 1.f, intensity));
-        intensity = 0.f;
-        if (a.refl_rec) {   // :50-55: the ray stays, intensity 0, colour blended
-            float* r = a.refl_rec + 14 * (size_t)e.idx;
-            r[0] = 0.f;
-            r[10] = col.x; r[11] = col.y; r[12] = col.z; r[13] = col.w;
-        }
-    }
-    a.color[e.idx] = col;
-    if (a.intensity) a.intensity[e.idx] = intensity;
-    return live;
-}
-
-// The certificate of a certified walk's hit (DESIGN.md 3): the reference's findCollision
-// (RayTraceTraversal.hlsl:106-193) reaches leaf x -- and, the walk having seen every triangle that could
-// be accepted at t <= its best, returns x -- when x's own box passes the reference slab test with the
-// bound t (every box above contains it: the slab test is monotone in the box, so they pass too, at every
-// bound the reference holds, all >= t).  The box is the leaf's: min / max of its clip-space vertices
-// (build.hip leaf_record_words, MortonCodes.hlsl:87-96), from the triangle's record.
-__device__ __forceinline__ bool leaf_certified(const TraceArgs& a, uint32_t tri, f3 o, f3 inv, float t) {
-    const float4* P = a.tclip + TCS * (size_t)tri;
-    const float4 a0 = P[0], a1 = P[1], a2 = P[2];
-    const f3 v0 = mk(a0.x, a0.y, a0.z), v1 = mk(a1.x, a1.y, a1.z), v2 = mk(a2.x, a2.y, a2.z);
-    const f3 lo = vmin(vmin(v0, v1), v2), hi = vmax(vmax(v0, v1), v2);
-    float tm;
-    return ray_box(o, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, true, t, tm);
-}
-
-// RayTraceReflection.hlsl:19-60 for queued ray i from its hit record h2 (valid: i is a ray to shade now).  CERT: a ray
-// whose walk flagged it or whose hit fails the certificate is flagged (the caller lists it for the re-trace) instead
-template <bool CERT>
-__device__ __forceinline__ void bounce_shade_ray(const TraceArgs& a, const RayQ* __restrict__ qin, uint32_t i, float2 h2,
-                                                 bool valid, RayQ& e, bool& live, bool& flagged, uint32_t& hits,
-                                                 uint32_t& tex) {
-    live = false;
-    flagged = false;
-    if (!valid) return;
-    e = qin[i];
-    uint32_t tri = __float_as_uint(h2.y);
-    bool skip = false;
-    if (CERT) {
-        flagged = hit_flagged(tri);
-        tri = (tri & LEAF_BIT) ? INVALID : tri & ~HIT_FLAG;
-        if (signbit(h2.x)) {   // the walk's deferred rays (trace.hip DEFER_*): walked in the reference order
-            skip = flagged;    //   by the walk's drained waves (exact: shaded as is), or by k_bounce_redo
-            flagged = false;
-            h2.x = -h2.x;
-        } else if (!flagged && tri != INVALID) {
-            const f3 d = mk(e.dx, e.dy, e.dz);
-            flagged = !leaf_certified(a, tri, mk(e.ox, e.oy, e.oz), mk(1.f / d.x, 1.f / d.y, 1.f / d.z), h2.x);
-        }
-    }
-    if (!flagged && !skip) live = bounce_apply(a, e, tri, h2.x, hits, tex);
-}
 template <bool COUNT, bool CERT>
 __global__ __launch_bounds__(BLOCK) void k_bounce_shade(TraceArgs a, const RayQ* __restrict__ qin,
                                                         const uint32_t* __restrict__ qin_count,
@@ -2239,20 +2294,12 @@ __global__ __launch_bounds__(BLOCK) void k_bounce_shade(TraceArgs a, const RayQ*
     const uint32_t n = *qin_count;
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (blockIdx.x * BLOCK >= n) return;   // whole block past the queue (wave_append below needs all lanes)
-    bool live = false, flagged = false;
     uint32_t hits = 0, tex = 0;
-    RayQ e;
     float2 h2 = make_float2(0.f, 0.f);
     if (i < n) h2 = hitrec[i];
     // (a ray the walk's early shading took is done: RTBVH_EARLY_SHADE)
-    bounce_shade_ray<CERT>(a, qin, i, h2, i < n && !(CERT && __float_as_uint(h2.x) == HIT_SHADED), e, live, flagged, hits,
-                           tex);
-    if (CERT) {
-        const uint32_t slot = wave_append(flagged, redo_count);
-        if (flagged) redo[slot] = i;
-    }
-    const uint32_t slot = wave_append(emit && live, qout_count);
-    if (emit && live) qout[slot] = e;
+    bounce_shade_emit<CERT>(a, qin, i, h2, i < n && !(CERT && __float_as_uint(h2.x) == HIT_SHADED), qout, qout_count, emit,
+                            redo, redo_count, hits, tex);
     if (COUNT) {
         Counts c = {0, 0, 0, 0, 0};
         flush_counts<COUNT>(a, c, hits, tex, 5);
@@ -2295,8 +2342,8 @@ __global__ __launch_bounds__(BLOCK) void k_bounce_redo(TraceArgs a, const RayQ* 
                 r = redo[i - nd];
             }
             e = qin[r];
-            const f3 o = mk(e.ox, e.oy, e.oz), d = mk(e.dx, e.dy, e.dz);
-            const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            f3 o, d, inv;
+            load_ray(&e, o, d, inv);
             float best;
             uint32_t bl;
             const bool h = traverse_ref<COUNT>(a, o, d, inv, best, bl, c);
@@ -2380,8 +2427,7 @@ __global__ __launch_bounds__(BLOCK) void k_count_diff(const uint4* __restrict__ 
         const uint4 x = a[i], y = b[i];
         cnt += (x.x != y.x) | (x.y != y.y) | (x.z != y.z) | (x.w != y.w);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     if (lane_id() == 0 && cnt) atomicAdd(diff, cnt);
 }
 
@@ -2390,64 +2436,30 @@ __global__ __launch_bounds__(BLOCK) void k_count_diff32(const uint32_t* __restri
                                                         size_t n, unsigned long long* __restrict__ diff) {
     unsigned long long cnt = 0;
     for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) cnt += a[i] != b[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     if (lane_id() == 0 && cnt) atomicAdd(diff, cnt);
 }
 
-template <bool COUNT, int K>
-void launch_primary_t(const TraceArgs& a, RayQ* q, uint32_t* qcount, bool emit, dim3 grid, hipStream_t s) {
-    if (a.limited) hipLaunchKernelGGL((k_primary<COUNT, K, true>), grid, dim3(BLOCK), 0, s, a, q, qcount, (int)emit);
-    else hipLaunchKernelGGL((k_primary<COUNT, K, false>), grid, dim3(BLOCK), 0, s, a, q, qcount, (int)emit);
-}
-template <int K>
-void launch_primary_c(const TraceArgs& a, RayQ* q, uint32_t* qcount, bool count, bool emit, dim3 grid, hipStream_t s) {
-    if (count) launch_primary_t<true, K>(a, q, qcount, emit, grid, s);
-    else launch_primary_t<false, K>(a, q, qcount, emit, grid, s);
-}
-
-template <bool COUNT, int MODE>
-void launch_bounce_trav_t(const TraceArgs& a, const RayQ* qin, const uint32_t* qin_count, const uint32_t* perm,
-                          float2* hitrec, uint32_t* next, uint32_t blocks, bool cert, uint32_t* defer, hipStream_t s,
-                          const BounceShade* es) {
-    const int lim = MODE == 2 ? a.stack_limit4b : a.stack_limit;
-    // early shading (certified passes, es): the hit records start "not written yet", shading workgroups follow the walk's
-    const bool early = RTBVH_EARLY_SHADE && MODE == 2 && cert && es;
-    const uint32_t nshade = early ? (es->P + ESHADE_RAYS - 1) / ESHADE_RAYS : 0u;
-    if (early) hipLaunchKernelGGL(k_hit_init, dim3(1024), dim3(BLOCK), 0, s, hitrec, qin_count);
-#define RTBVH_BTE(L, G, C, E)                                                                                          \
-    hipLaunchKernelGGL((k_bounce_trav<COUNT, MODE, L, G, C, E>), dim3(blocks + nshade), dim3(BLOCK), 0, s, a.inner,         \
-                       a.qnode,                                                                                        \
-                       a.leaf, a.T, qin, qin_count, perm, hitrec, next, a.counters, a.overflow, lim, defer, a.topo,    \
-                       a.nb ? a.nbox : nullptr, blocks, a, early ? es->qout : nullptr, early ? es->qout_count : nullptr, \
-                       early ? (int)es->emit : 0, early ? es->redo : nullptr, early ? es->redo_count : nullptr)
-#define RTBVH_BT(L, G, C) RTBVH_BTE(L, G, C, false)
-    // the guard only for a tree that may have cycles (CPUTests delta), or for COUNT's census
-    const bool guard = COUNT || !a.acyclic;
-    if (MODE == 2 && cert && early) {
-        if (guard) RTBVH_BTE(false, true, MODE == 2, MODE == 2);
-        else RTBVH_BTE(false, false, MODE == 2, MODE == 2);
-    } else if (MODE == 2 && cert) {   // (the certified walk: no stack limit, a clz64 tree -- api.hip enqueue_trace)
-        if (guard) RTBVH_BT(false, true, MODE == 2);
-        else RTBVH_BT(false, false, MODE == 2);
-    } else if (a.limited) { if (guard) RTBVH_BT(true, true, false); else RTBVH_BT(true, false, false); }
-    else { if (guard) RTBVH_BT(false, true, false); else RTBVH_BT(false, false, false); }
-#undef RTBVH_BT
-#undef RTBVH_BTE
+// ---- instance selection on the host ------------------------------------------------------------
+// Run-time bools as compile-time constants: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{},
+// std::bool_constant<b1>{}, ...), so a generic lambda names the kernel instance `k<B0, B1>` of its arguments.
+// Only the instances such a lambda names exist: a combination no context asks for is excluded by the
+// constants written beside the arguments.
+template <class F> void with_bools(F&& f) { f(); }
+template <class F, class... Bs> void with_bools(F&& f, bool b, Bs... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 // ---- ray queries (rtbvh_query_async): caller rays in, (t, u, v, triangle) out ------------------------
-// findCollision for rays the caller chose, in the space the BVH was built in.  One ray per lane on the per-lane
-// walk state of k_bounce_trav's reference-order mode (the stack top cached in a register, entries [0, SB) in LDS
-// columns, deeper ones in scratch; one 64-B fetch a step, leaf or node), the same claims (per-wave segment claims
+// findCollision for rays the caller chose, in the space the BVH was built in.  One ray per lane on the shared
+// per-lane step (Walk, walk_leaf, walk_node) with k_bounce_trav's binary modes' stack (BlockStack) and fetch
+// placement (one 64-B fetch a step, leaf or node), the same claims (refill_claim: per-wave segment claims
 // on per-XCD counters, a refill once REFILL_MIN lanes are idle): caller rays are incoherent, and any-hit walks
 // end at very different lengths.  A ray is two float4 loads, a hit one 16-B store at the ray's own index.
-// t_max enters in two places only: a triangle's t is accepted iff the reference accepts it and t <= t_max; a
-// box passes iff the reference's first two conditions hold and (hit ? mn <= dist : !(mn > t_max)) -- with
-// t_max = +inf the reference, bit for bit.  A zero or non-finite direction or origin needs no special case:
-// the arithmetic makes the ray a miss.
-// ANY: the box test without the `hit` branch, the walk ends at the first accepted triangle.
-// NB: on the topology and the node boxes (traverse_nb's fetches), for a build that wrote no records.
+// t_max and ANY enter through the walk's rule alone (QueryRule).  A zero or non-finite direction or origin needs
+// no special case: the arithmetic makes the ray a miss.
+// NB: on the topology and the node boxes (NodeBoxTree's fetches), for a build that wrote no records.
 // Every instance keeps the walk-length guard and reads the stack limit at run time (compiling them out where no
 // context needs them, as k_bounce_trav's GUARD and LIM do, measured 12.13 -> 12.06 ms at C5: less than the
 // figure moves between runs, so not worth twice the instances).
@@ -2459,82 +2471,47 @@ __device__ __forceinline__ void ray_triangle_uv(f3 o, f3 d, f3 p0, f3 e1, f3 e2,
     u = dot(rt, tmp) * idx;
     v = dot(d, cross(rt, e1)) * idx;
 }
-template <bool ANY>
-__device__ __forceinline__ bool query_box(f3 o, f3 inv, f2v lo, f2v hi, float lz, float hz, bool hit, float best,
-                                          float tmax) {
-    float mn;
-    const bool base = ray_box_xy(o, inv, lo, hi, lz, hz, false, 0.f, mn);
-    return base && (!ANY && hit ? mn <= best : !(mn > tmax));
-}
 template <bool ANY, bool COUNT, bool NB>
 __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query(QueryArgs a) {
     const uint32_t n = a.n, T = a.T;
-    const uint32_t lane = lane_id(), tid = threadIdx.x;
+    const uint32_t lane = lane_id();
     const int limit = a.stack_limit;
     const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
     Counts c = {0, 0, 0, 0, 0};
     uint32_t nrays = 0, nhits = 0;
-    bool has = false, hit = false;
-    uint32_t r = 0, node = 0, top = INVALID, bl = 0, guard = 0;
-    int sp = 0;
-    float best = 0.f, tmax = 0.f;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};
+    QueryRule<ANY> rule{0.f};
     f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
     __shared__ uint32_t s_stk[SB][BLOCK];
     uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
-    auto spush = [&](uint32_t v) {
-        if (sp < SB) s_stk[sp][tid] = v;
-        else stack[sp - SB] = v;
-        ++sp;
-    };
-    auto spop = [&]() {   // the next node from the cached top; refill the top from entry --sp
-        node = top;
-        if (--sp >= 0) top = sp < SB ? s_stk[sp][tid] : stack[sp - SB];
-    };
-    auto start = [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
-        r = a.perm ? a.perm[p] : p;
-        const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
-        o = mk(q0.x, q0.y, q0.z);
-        tmax = q0.w;
-        d = mk(q1.x, q1.y, q1.z);
-        inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
-        has = true;
-        hit = false;
-        best = 0.f;
-        bl = 0;
-        sp = 0;
-        top = INVALID;
-        node = NB ? (T > 1 ? 0u : LEAF_BIT) : root_slot(T);
-        guard = 2 * T + 2;
-    };
-    bool drained = false;
-    uint32_t kseg = 0;   // segments claimed from so far (wave-uniform)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
     while (true) {
-        const uint64_t idle = __ballot(!has);
-        const uint32_t nidle = (uint32_t)__popcll(idle);
-        if (!drained && (nidle >= REFILL_MIN || nidle == 64)) {
-            const uint32_t seg = claim_segment(kseg);
-            const uint32_t s0 = (uint32_t)((uint64_t)n * seg / NEXT_SEGS);
-            const uint32_t len = (uint32_t)((uint64_t)n * (seg + 1) / NEXT_SEGS) - s0;
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(a.next + NEXT_STRIDE * seg, nidle);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + nidle >= len && ++kseg == NEXT_SEGS) drained = true;   // segment (and the last) used up
-            if (!has) {
-                const uint32_t p = base + lane_rank(idle);
-                if (p < len) start(s0 + p);
-            }
-        }
-        if (__ballot(has) == 0 && drained) break;
+        refill_claim(rf, a.next, n, has, [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
+            r = a.perm ? a.perm[p] : p;
+            const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
+            o = mk(q0.x, q0.y, q0.z);
+            rule.tmax = q0.w;
+            d = mk(q1.x, q1.y, q1.z);
+            inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            has = true;
+            w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
         if (!has) continue;
         bool done = false;
-        const bool isleaf = (node & LEAF_BIT) != 0;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
         // one fetch for every active lane, leaf or node, before the branch (k_bounce_trav); NB: a node's
         // children from the topology, then their boxes
         v4f q0, q1, q2;
         uint32_t cl = 0, cr = 0;
         if (!NB || isleaf) {
-            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(node & ~LEAF_BIT))
-                                   : reinterpret_cast<const v4f*>(a.inner + node);
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
             q0 = rr[0]; q1 = rr[1]; q2 = rr[2];
             v4f q3 = rr[3];
             pin(q0); pin(q1); pin(q2); pin(q3);
@@ -2544,81 +2521,47 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query(QueryArgs a) {
                 cr = child_slot(__float_as_uint(q3.y), own, 1);
             }
         } else {
-            const uint4 tp = a.topo[node];
-            cl = tp.x;
-            cr = tp.y;
-            f2v lmn, lmx, rmn, rmx;
-            float lz0, lz1, rz0, rz1;
-            nb_child_box(a.nbox, leaf, cl, lmn, lmx, lz0, lz1);
-            nb_child_box(a.nbox, leaf, cr, rmn, rmx, rz0, rz1);
-            q0 = v4f{lmn.x, lmn.y, lmx.x, lmx.y};   // the record's layout
-            q1 = v4f{rmn.x, rmn.y, rmx.x, rmx.y};
-            q2 = v4f{lz0, lz1, rz0, rz1};
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
         }
-        if (--guard == 0) {
+        if (--w.guard == 0) {
             c.overflow++;
             done = true;
         } else if (isleaf) {
-            const uint32_t j = node & ~LEAF_BIT;
-            if (COUNT) c.leaf++;
-            const float t = ray_triangle(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x));
-            if (t != -1.f && t <= tmax && (ANY || !hit || t < best)) {
-                best = t;
-                bl = j;
-                hit = true;
-                if (ANY) done = true;
-            }
-            if (!done) {
-                spop();
-                done = sp == -1;
-            }
+            const bool acc = walk_leaf<COUNT>(w, st, rule, c, o, d, w.node & ~LEAF_BIT, mk(q0.x, q0.y, q0.z),
+                                              mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x));
+            done = (ANY && acc) || w.sp == -1;
         } else {
-            if (COUNT) c.internal++;
-            const bool lh = query_box<ANY>(o, inv, q0.xy, q0.zw, q2.x, q2.y, hit, best, tmax);
-            const bool rh = query_box<ANY>(o, inv, q1.xy, q1.zw, q2.z, q2.w, hit, best, tmax);
-            if (!lh && !rh) {
-                spop();
-                done = sp == -1;
-            } else if (lh && rh) {
-                if (sp + 1 >= limit) {
-                    c.overflow++;
-                    spop();
-                    done = sp == -1;
-                } else {
-                    spush(top);   // push the second child
-                    top = cr;
-                    node = cl;
-                }
-            } else {
-                node = lh ? cl : cr;
-            }
+            walk_node<COUNT>(w, st, rule, c, o, inv, limit, record_children(q0, q1, q2, cl, cr));
+            done = w.sp == -1;
         }
         if (done) {
             // (u, v) of the winning triangle, recomputed once from its leaf record.  (Fetching the record with the
             // wave's next common fetch instead -- the ray taking one more step at its leaf -- gained nothing: C5,
             // closest-hit 12.06 -> 12.32 ms)
             float4 h = make_float4(-1.f, 0.f, 0.f, __uint_as_float(INVALID));
-            if (hit) {
-                const float4* lr = leaf + 4 * (size_t)bl;
+            if (w.hit) {
+                const float4* lr = leaf + 4 * (size_t)w.bl;
                 const float4 la = lr[0], lb = lr[1], lc = lr[2];
                 float u, v;
                 ray_triangle_uv(o, d, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y), mk(lb.z, lb.w, lc.x), u, v);
-                h = make_float4(best, u, v, __uint_as_float(__float_as_uint(lc.y) & ~LEAF_BIT));
+                h = make_float4(w.best, u, v, __uint_as_float(__float_as_uint(lc.y) & ~LEAF_BIT));
             }
             a.hits[r] = h;
             has = false;
             if (COUNT) {
                 nrays++;
-                nhits += hit;
+                nhits += w.hit;
             }
         }
     }
     if (COUNT || __ballot(c.overflow != 0)) {
         unsigned long long v[5] = {nrays, nhits, c.internal, c.leaf, c.overflow};
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+        wave_sum(v);
         if (lane == 0) {
             if (COUNT)
                 for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
@@ -2647,12 +2590,9 @@ void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s) {
     if (a.n == 0) return;
     // the persistent grid of the bounce walk (8 waves per SIMD), or a workgroup per 256 rays when that is fewer
     const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
-#define RTBVH_Q(A, C, N) hipLaunchKernelGGL((k_query<A, C, N>), dim3(blocks), dim3(BLOCK), 0, s, a)
-#define RTBVH_QC(A, C) do { if (a.nb) RTBVH_Q(A, C, true); else RTBVH_Q(A, C, false); } while (0)
-    if (any) { if (count) RTBVH_QC(true, true); else RTBVH_QC(true, false); }
-    else { if (count) RTBVH_QC(false, true); else RTBVH_QC(false, false); }
-#undef RTBVH_QC
-#undef RTBVH_Q
+    with_bools([&](auto ANY, auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_query<ANY, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, any, count, a.nb);
 }
 
 void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
@@ -2667,17 +2607,23 @@ void launch_primary(const TraceArgs& a, RayQ* q, uint32_t* qcount, bool count, b
     const uint32_t launch_bands = my_bands > a.band0 ? (my_bands - a.band0 + a.bstep - 1) / a.bstep : 0;
     if (launch_bands == 0 || a.W == 0) return;
     dim3 grid((a.W + 31) / 32, launch_bands);
+    const auto walk = [&](auto K) {   // k_primary's walk K (PrimaryWalk)
+        with_bools([&](auto COUNT, auto LIM) {
+            hipLaunchKernelGGL((k_primary<COUNT, K, LIM>), grid, dim3(BLOCK), 0, s, a, q, qcount, (int)emit);
+        }, count, a.limited);
+    };
+    using std::integral_constant;
     switch (kind) {
-        case PrimaryKind::LANE_NEAREST: launch_primary_c<1>(a, q, qcount, count, emit, grid, s); break;
-        case PrimaryKind::PACKET_REFERENCE: launch_primary_c<2>(a, q, qcount, count, emit, grid, s); break;
-        case PrimaryKind::PACKET_NEAREST: launch_primary_c<3>(a, q, qcount, count, emit, grid, s); break;
+        case PrimaryKind::LANE_NEAREST: walk(integral_constant<int, 1>{}); break;
+        case PrimaryKind::PACKET_REFERENCE: walk(integral_constant<int, 2>{}); break;
+        case PrimaryKind::PACKET_NEAREST: walk(integral_constant<int, 3>{}); break;
         case PrimaryKind::PACKET_WIDE:
-            if (a.acyclic) launch_primary_c<5>(a, q, qcount, count, emit, grid, s);
-            else launch_primary_c<4>(a, q, qcount, count, emit, grid, s);
+            if (a.acyclic) walk(integral_constant<int, 5>{});
+            else walk(integral_constant<int, 4>{});
             break;
         default:   // LANE_REFERENCE: on the topology and node boxes when the trace says so (a certified one)
-            if (a.nb) launch_primary_c<6>(a, q, qcount, count, emit, grid, s);
-            else launch_primary_c<0>(a, q, qcount, count, emit, grid, s);
+            if (a.nb) walk(integral_constant<int, 6>{});
+            else walk(integral_constant<int, 0>{});
             break;
     }
 }
@@ -2708,36 +2654,30 @@ void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ*
     uint32_t* rl = redo ? redo->list : nullptr;
     uint32_t* rc = redo ? redo->count : nullptr;
     const bool rec = a.refl_rec || a.refr_rec;
-#define RTBVH_PBR(C, R, F)                                                                                          \
-    do {                                                                                                            \
-        if (rec || !(F))                                                                                            \
-            hipLaunchKernelGGL((k_primary_binned<C, R, F, true>), grid, dim3(PB_RASTER_BLOCK), 0, s, a, pb.off,     \
-                               pb.bins, pb.cap, pb.ntx, rows, pb.keys, q, qcount, (int)emit, rl, rc);               \
-        else if (small_tiles)                                                                                       \
-            hipLaunchKernelGGL((k_primary_binned<C, R, F, false, PB_RASTER_BLOCK_SMALL>), grid,                      \
-                               dim3(PB_RASTER_BLOCK_SMALL), 0, s, a, pb.off, pb.bins, pb.cap, pb.ntx, rows, pb.keys, q, \
-                               qcount, (int)emit, rl, rc);                                                          \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_primary_binned<C, R, F, false>), grid, dim3(PB_RASTER_BLOCK), 0, s, a, pb.off,    \
-                               pb.bins, pb.cap, pb.ntx, rows, pb.keys, q, qcount, (int)emit, rl, rc);               \
-    } while (0)
-#define RTBVH_PBS(C, R)                                                                                              \
-    hipLaunchKernelGGL((k_pb_shade<C, R>), grid, dim3(PB_SHADE_BLOCK), 0, s, a, pb.off, pb.cap, pb.ntx, rows, pb.keys, q, \
-                       qcount, (int)emit, rl, rc)
+    const auto raster = [&](auto* kernel, uint32_t rb) {
+        hipLaunchKernelGGL(kernel, grid, dim3(rb), 0, s, a, pb.off, pb.bins, pb.cap, pb.ntx, rows, pb.keys, q, qcount,
+                           (int)emit, rl, rc);
+    };
 #if RTBVH_PB_FUSE
-    if (count) { if (redo) RTBVH_PBR(true, true, true); else RTBVH_PBR(true, false, true); }
-    else { if (redo) RTBVH_PBR(false, true, true); else RTBVH_PBR(false, false, true); }
+    with_bools([&](auto COUNT, auto CERT) {
+        if (rec) raster(k_primary_binned<COUNT, CERT, true, true>, PB_RASTER_BLOCK);
+        else if (small_tiles)
+            raster(k_primary_binned<COUNT, CERT, true, false, PB_RASTER_BLOCK_SMALL>, PB_RASTER_BLOCK_SMALL);
+        else raster(k_primary_binned<COUNT, CERT, true, false>, PB_RASTER_BLOCK);
+    }, count, redo != nullptr);
 #else
-    if (count) RTBVH_PBR(true, false, false); else RTBVH_PBR(false, false, false);
-    if (count) { if (redo) RTBVH_PBS(true, true); else RTBVH_PBS(true, false); }
-    else { if (redo) RTBVH_PBS(false, true); else RTBVH_PBS(false, false); }
+    (void)rec;
+    (void)small_tiles;
+    with_bools([&](auto COUNT) { raster(k_primary_binned<COUNT, false, false, true>, PB_RASTER_BLOCK); }, count);
+    with_bools([&](auto COUNT, auto CERT) {
+        hipLaunchKernelGGL((k_pb_shade<COUNT, CERT>), grid, dim3(PB_SHADE_BLOCK), 0, s, a, pb.off, pb.cap, pb.ntx, rows,
+                           pb.keys, q, qcount, (int)emit, rl, rc);
+    }, count, redo != nullptr);
 #endif
-#undef RTBVH_PBR
-#undef RTBVH_PBS
     if (redo) {   // the flagged pixels, in the reference order
-        const dim3 rg(REDO_BLOCKS);
-        if (count) hipLaunchKernelGGL((k_primary_redo<true>), rg, dim3(BLOCK), 0, s, a, rl, rc, q, qcount, (int)emit);
-        else hipLaunchKernelGGL((k_primary_redo<false>), rg, dim3(BLOCK), 0, s, a, rl, rc, q, qcount, (int)emit);
+        with_bools([&](auto COUNT) {
+            hipLaunchKernelGGL((k_primary_redo<COUNT>), dim3(REDO_BLOCKS), dim3(BLOCK), 0, s, a, rl, rc, q, qcount, (int)emit);
+        }, count);
     }
 }
 
@@ -2764,18 +2704,10 @@ void launch_primary_binned(const TraceArgs& a, const PrimBins& pb, uint32_t rows
 void launch_bounce(const TraceArgs& a, const RayQ* qin, const uint32_t* qin_count, const uint32_t* perm, RayQ* qout,
                    uint32_t* qout_count, bool count, bool emit, bool nearest, hipStream_t s) {
     const uint32_t blocks = 2048;   // 8 waves/SIMD x 1024 SIMDs / 4 waves per block; grid-stride over the queue
-#define RTBVH_BNC(C, N)                                                                                          \
-    do {                                                                                                           \
-        if (a.limited)                                                                                             \
-            hipLaunchKernelGGL((k_bounce<C, N, true>), dim3(blocks), dim3(BLOCK), 0, s, a, qin, qin_count, perm, qout, \
-                               qout_count, (int)emit);                                                           \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_bounce<C, N, false>), dim3(blocks), dim3(BLOCK), 0, s, a, qin, qin_count, perm,     \
-                               qout, qout_count, (int)emit);                                                     \
-    } while (0)
-    if (count) { if (nearest) RTBVH_BNC(true, true); else RTBVH_BNC(true, false); }
-    else { if (nearest) RTBVH_BNC(false, true); else RTBVH_BNC(false, false); }
-#undef RTBVH_BNC
+    with_bools([&](auto COUNT, auto NEAREST, auto LIM) {
+        hipLaunchKernelGGL((k_bounce<COUNT, NEAREST, LIM>), dim3(blocks), dim3(BLOCK), 0, s, a, qin, qin_count, perm, qout,
+                           qout_count, (int)emit);
+    }, count, nearest, a.limited);
 }
 
 void launch_bounce_keys(const RayQ* q, const uint32_t* count, const float* box, uint32_t P, uint32_t* keys,
@@ -2787,13 +2719,32 @@ void launch_bounce_traverse(const TraceArgs& a, const RayQ* qin, const uint32_t*
                             bool count, BounceWalk walk, float2* hitrec, uint32_t* next, uint32_t blocks,
                             hipStream_t s, bool cert, uint32_t* defer, const BounceShade* es) {
     if (blocks == 0) blocks = 2048;
-#define RTBVH_TRAV(C, M) launch_bounce_trav_t<C, M>(a, qin, qin_count, perm, hitrec, next, blocks, cert, defer, s, es)
-    switch (walk) {
-        case BounceWalk::NEAREST: if (count) RTBVH_TRAV(true, 1); else RTBVH_TRAV(false, 1); break;
-        case BounceWalk::WIDE_QUANTIZED: if (count) RTBVH_TRAV(true, 2); else RTBVH_TRAV(false, 2); break;
-        default: if (count) RTBVH_TRAV(true, 0); else RTBVH_TRAV(false, 0); break;
-    }
-#undef RTBVH_TRAV
+    const bool wide = walk == BounceWalk::WIDE_QUANTIZED;
+    // the certified walk: the 4-wide one, no stack limit, a clz64 tree (api.hip enqueue_trace)
+    const bool certified = wide && cert;
+    // early shading (certified passes, es): the hit records start "not written yet", shading workgroups follow the walk's
+    const bool early = RTBVH_EARLY_SHADE && certified && es;
+    const uint32_t nshade = early ? (es->P + ESHADE_RAYS - 1) / ESHADE_RAYS : 0u;
+    if (early) hipLaunchKernelGGL(k_hit_init, dim3(1024), dim3(BLOCK), 0, s, hitrec, qin_count);
+    const auto launch = [&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks + nshade), dim3(BLOCK), 0, s, a.inner, a.qnode, a.leaf, a.T, qin, qin_count,
+                           perm, hitrec, next, a.counters, a.overflow, wide ? a.stack_limit4b : a.stack_limit, defer,
+                           a.topo, a.nb ? a.nbox : nullptr, blocks, a, early ? es->qout : nullptr,
+                           early ? es->qout_count : nullptr, early ? (int)es->emit : 0, early ? es->redo : nullptr,
+                           early ? es->redo_count : nullptr);
+    };
+    // the guard only for a tree that may have cycles (CPUTests delta), or for COUNT's census
+    const bool guard = count || !a.acyclic;
+    if (certified)
+        with_bools([&](auto COUNT, auto GUARD, auto ES) { launch(k_bounce_trav<COUNT, 2, false, GUARD, true, ES>); }, count,
+                   guard, early);
+    else if (wide)
+        with_bools([&](auto COUNT, auto LIM, auto GUARD) { launch(k_bounce_trav<COUNT, 2, LIM, GUARD>); }, count, a.limited,
+                   guard);
+    else
+        with_bools([&](auto COUNT, auto NEAREST, auto LIM, auto GUARD) {
+            launch(k_bounce_trav<COUNT, NEAREST ? 1 : 0, LIM, GUARD>);
+        }, count, walk == BounceWalk::NEAREST, a.limited, guard);
 }
 
 void launch_bounce_shade(const TraceArgs& a, const RayQ* qin, const uint32_t* qin_count, const float2* hitrec,
@@ -2803,18 +2754,15 @@ void launch_bounce_shade(const TraceArgs& a, const RayQ* qin, const uint32_t* qi
     uint32_t* rl = redo ? redo->list : nullptr;
     uint32_t* rc = redo ? redo->count : nullptr;
     const dim3 g((P + BLOCK - 1) / BLOCK);
-#define RTBVH_BS(C, R)                                                                                             \
-    hipLaunchKernelGGL((k_bounce_shade<C, R>), g, dim3(BLOCK), 0, s, a, qin, qin_count, hitrec, qout, qout_count, \
-                       (int)emit, rl, rc)
-    if (count) { if (redo) RTBVH_BS(true, true); else RTBVH_BS(true, false); }
-    else { if (redo) RTBVH_BS(false, true); else RTBVH_BS(false, false); }
-#undef RTBVH_BS
-    if (redo) {   // the flagged rays (and the walk's deferred rays left over), in the reference order
-        if (count) hipLaunchKernelGGL((k_bounce_redo<true>), dim3(REDO_BLOCKS), dim3(BLOCK), 0, s, a, qin, rl, rc, qout,
-                                      qout_count, (int)emit, redo->defer, redo->dnext);
-        else hipLaunchKernelGGL((k_bounce_redo<false>), dim3(REDO_BLOCKS), dim3(BLOCK), 0, s, a, qin, rl, rc, qout,
-                                qout_count, (int)emit, redo->defer, redo->dnext);
-    }
+    with_bools([&](auto COUNT, auto CERT) {
+        hipLaunchKernelGGL((k_bounce_shade<COUNT, CERT>), g, dim3(BLOCK), 0, s, a, qin, qin_count, hitrec, qout, qout_count,
+                           (int)emit, rl, rc);
+    }, count, redo != nullptr);
+    if (redo)   // the flagged rays (and the walk's deferred rays left over), in the reference order
+        with_bools([&](auto COUNT) {
+            hipLaunchKernelGGL((k_bounce_redo<COUNT>), dim3(REDO_BLOCKS), dim3(BLOCK), 0, s, a, qin, rl, rc, qout,
+                               qout_count, (int)emit, redo->defer, redo->dnext);
+        }, count);
 }
 
 void launch_assemble(const float4* bands, const uint32_t* slots, uint32_t stride_rows, uint32_t W, uint32_t H,
