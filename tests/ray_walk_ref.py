@@ -70,9 +70,16 @@ def _box(bmin, bmax, o, inv):
         return (0 <= mx) & (mn <= mx), mn
 
 
-def walk(nodes, tris, origins, directions, t_max=None, any_hit=False):
+def walk(nodes, tris, origins, directions, t_max=None, any_hit=False, order="reference"):
     """Walks every ray; returns a dict of per-ray arrays: hit (bool), t, u, v (float32; a miss has
-    t = -1, u = v = 0), tri (uint32; a miss 0xFFFFFFFF), internal and leaf (visit counts, int64)."""
+    t = -1, u = v = 0), tri (uint32; a miss 0xFFFFFFFF), internal and leaf (visit counts, int64), max_stack (the
+    ray's largest stack index, int64: find_collision's max_depth, 0 for a ray that never pushed).
+
+    order="nearest" (closest hits only) restates the binary nearest-first walk of trace.hip (WalkRule<true>,
+    walk_node): where both children pass, the right one first if its slab entry is the smaller (the left one is
+    pushed), and a triangle at the best distance replaces the best hit if its sorted leaf index is smaller."""
+    nearest = order == "nearest"
+    assert order in ("reference", "nearest") and not (nearest and any_hit)
     o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
     d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
     R = len(o)
@@ -90,11 +97,13 @@ def walk(nodes, tris, origins, directions, t_max=None, any_hit=False):
     hit = np.zeros(R, bool)
     best = np.zeros(R, np.float32)
     btri = np.zeros(R, np.int64)
+    bleaf = np.zeros(R, np.int64)
     node = np.full(R, n if n > 1 else 0, np.int64)
     stack = np.full((R, STACK), -1, np.int64)
     sp = np.zeros(R, np.int64)
     n_int = np.zeros(R, np.int64)
     n_leaf = np.zeros(R, np.int64)
+    max_sp = np.zeros(R, np.int64)
     act = np.arange(R)
     while len(act):
         nd = node[act]
@@ -107,10 +116,14 @@ def walk(nodes, tris, origins, directions, t_max=None, any_hit=False):
             t, _, _ = tri_test(tris, tr, o[a], d[a])
             acc = (t != -1) & (t <= tm[a])
             if not any_hit:
-                acc &= ~hit[a] | (t < best[a])
+                better = ~hit[a] | (t < best[a])
+                if nearest:
+                    better |= (t == best[a]) & (nd[lf] < bleaf[a])
+                acc &= better
             w = a[acc]
             best[w] = t[acc]
             btri[w] = tr[acc]
+            bleaf[w] = nd[lf][acc]
             hit[w] = True
             node[a] = stack[a, sp[a]]
             sp[a] -= 1
@@ -140,9 +153,12 @@ def walk(nodes, tris, origins, directions, t_max=None, any_hit=False):
             sp[pop] -= 1
             psh = b[both & ~full]
             sp[psh] += 1
-            stack[psh, sp[psh]] = Rr[both & ~full]
+            with np.errstate(all="ignore"):
+                swap = both & (rmn < lmn) if nearest else np.zeros(len(b), bool)
+            stack[psh, sp[psh]] = np.where(swap, L, Rr)[both & ~full]
+            max_sp[psh] = np.maximum(max_sp[psh], sp[psh])
             go = (lh | rh) & ~full
-            node[b[go]] = np.where(lh[go], L[go], Rr[go])
+            node[b[go]] = np.where(swap, Rr, np.where(lh, L, Rr))[go]
         act = act[sp[act] != -1]
 
     out_t = np.where(hit, best, np.float32(-1)).astype(np.float32)
@@ -153,7 +169,8 @@ def walk(nodes, tris, origins, directions, t_max=None, any_hit=False):
         _, uu, vv = tri_test(tris, btri[w], o[w], d[w])
         u[w], v[w] = uu, vv
     return {"hit": hit, "t": out_t, "u": u, "v": v,
-            "tri": np.where(hit, btri, NONE).astype(np.uint32), "internal": n_int, "leaf": n_leaf}
+            "tri": np.where(hit, btri, NONE).astype(np.uint32), "internal": n_int, "leaf": n_leaf,
+            "max_stack": max_sp}
 
 
 def bits(x):

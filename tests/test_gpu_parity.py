@@ -583,7 +583,13 @@ def test_qnodes_contain_the_exact_boxes(scene):
         s = rt.Scene(d["vertices"], d["indices"], d["mat_indices"], d["material_blob"])
     cam = (np.eye(4, dtype=np.float32), np.eye(4, dtype=np.float32)) if scene == "tiny triangles" \
         else rt.camera_reference(320, 240)
-    with rt.Context(device=0) as c:
+    check_qnodes(s, cam, tiny=scene == "tiny triangles")
+
+
+def check_qnodes(s, cam, tiny=False, flags=0):
+    """test_qnodes_contain_the_exact_boxes' checks on scene s under camera cam = (wvp, wv), built by a context with
+    `flags` (tests/test_deep_trees_gpu.py runs them on its own scene)."""
+    with rt.Context(device=0, flags=flags) as c:
         c.set_scene(s)
         c.set_camera(*cam)
         c.build()
@@ -660,14 +666,14 @@ def test_qnodes_contain_the_exact_boxes(scene):
     assert ((reach < top) | (half < np.float32(2.0 ** -120)))[read].all(), "grid step not minimal"
     # the margin codes: E_k = max over node k's leaves of margin.h mt_edge_bound on the clip-space
     # triangle (rtbvh_device.h xform_point's operation order, no FMA: numpy float32), rounded up
-    wvp = cam[0].reshape(4, 4)
+    wvp = np.asarray(cam[0], np.float32).reshape(4, 4)
     P = s.vertices[:, :3].astype(np.float32)
     with np.errstate(under="ignore"):
         clip = ((P[:, 0:1] * wvp[0] + P[:, 1:2] * wvp[1]) + P[:, 2:3] * wvp[2]) + wvp[3]
     tri = clip[s.indices.reshape(-1, 3), :3]
     e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
     eb = _edge_bound_np(e1, e2)
-    if scene == "tiny triangles":   # the bound is >= the exact 2-norm at every scale
+    if tiny:   # the bound is >= the exact 2-norm at every scale
         n64 = lambda e: np.sqrt((e.astype(np.float64) ** 2).sum(1))
         assert (eb.astype(np.float64) >= np.maximum(n64(e1), n64(e2))).all()
         assert (eb < 2.0 ** -100).sum() > 500

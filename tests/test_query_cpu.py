@@ -47,6 +47,20 @@ def test_restatement_primary_rays_match_oracle(pinned):
     assert int(r["leaf"].sum()) == st["leaf_visits"]
     np.testing.assert_array_equal(r["hit"].reshape(H, W), (pinned["fb0"] != BACKGROUND).any(-1))
     assert (r["tri"][~r["hit"]] == 0xFFFFFFFF).all() and (r["t"][~r["hit"]] == -1).all()
+    assert int(r["max_stack"].max()) == st["max_stack"]
+
+
+def test_restatement_nearest_order_returns_the_reference_hits(pinned):
+    """order="nearest" (trace.hip's binary nearest-first rule) answers as the reference order on the OBJ scenes."""
+    rec = pinned["refl"]
+    live = rec[:, 0] > 0
+    for o, d in (primary_rays(W, H), (rec[live, 1:4], rec[live, 4:7])):
+        r = rw.walk(pinned["nodes"], pinned["tris"], o, d)
+        q = rw.walk(pinned["nodes"], pinned["tris"], o, d, order="nearest")
+        for f in ("t", "u", "v"):
+            np.testing.assert_array_equal(rw.bits(q[f]), rw.bits(r[f]), err_msg=f)
+        np.testing.assert_array_equal(q["tri"], r["tri"])
+        assert int(q["internal"].sum()) <= int(r["internal"].sum())
 
 
 def test_restatement_reflect_records_match_oracle(pinned):
