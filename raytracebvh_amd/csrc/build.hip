@@ -72,7 +72,26 @@ __device__ __forceinline__ uint32_t quantise_hlsl(float p) {
 // reduces the partials.  bounds layout: [0..5] = min xyz, max xyz; [8..] partials.
 constexpr uint32_t BOUNDS_BLOCKS = 1024;
 
-__device__ __forceinline__ void reduce_box_block(f3& mn, f3& mx, float* s_red /*4*6*/) {
+// A box as six floats (min xyz, max xyz): LDS rows, inner[p].lmin / rmin, the bounds, the root box
+__device__ __forceinline__ void ld_box(const float* p, f3& lo, f3& hi) {
+    lo = mk(p[0], p[1], p[2]);
+    hi = mk(p[3], p[4], p[5]);
+}
+__device__ __forceinline__ void st_box(float* p, f3 lo, f3 hi) {
+    p[0] = lo.x; p[1] = lo.y; p[2] = lo.z;
+    p[3] = hi.x; p[4] = hi.y; p[5] = hi.z;
+}
+__device__ __forceinline__ void st_rootbox(const BuildArgs& a, f3 lo, f3 hi) { st_box(a.rootbox, lo, hi); }
+// a climber on `side` of a node takes in its sibling's box: the union in (childL, childR)
+// order, as the reference's min(L.bbMin, R.bbMin)
+__device__ __forceinline__ void unite(uint32_t side, f3& lo, f3& hi, f3 smin, f3 smax) {
+    if (side) { lo = vmin(smin, lo); hi = vmax(smax, hi); }
+    else      { lo = vmin(lo, smin); hi = vmax(hi, smax); }
+}
+
+// the box of a block of WAVES waves (wave shuffles, then s_red: 6 floats a wave): thread 0's mn, mx
+template <uint32_t WAVES>
+__device__ __forceinline__ void reduce_box_block(f3& mn, f3& mx, float* s_red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         mn.x = fminf(mn.x, __shfl_xor(mn.x, off, 64));
@@ -82,18 +101,50 @@ __device__ __forceinline__ void reduce_box_block(f3& mn, f3& mx, float* s_red /*
         mx.y = fmaxf(mx.y, __shfl_xor(mx.y, off, 64));
         mx.z = fmaxf(mx.z, __shfl_xor(mx.z, off, 64));
     }
-    const uint32_t w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_red[6 * w + 0] = mn.x; s_red[6 * w + 1] = mn.y; s_red[6 * w + 2] = mn.z;
-        s_red[6 * w + 3] = mx.x; s_red[6 * w + 4] = mx.y; s_red[6 * w + 5] = mx.z;
+    if ((threadIdx.x & 63) == 0) st_box(s_red + 6 * (threadIdx.x >> 6), mn, mx);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t k = 1; k < WAVES; k++) {
+            f3 wn, wx;
+            ld_box(s_red + 6 * k, wn, wx);
+            mn = vmin(mn, wn);
+            mx = vmax(mx, wx);
+        }
+    }
+}
+// (min z, max z, largest edge bound) of a block of WAVES waves, through s_z (3 floats a wave):
+// thread 0's zl, zh, em (folded from the neutral values, so a wave of NaN depths drops out)
+template <uint32_t WAVES>
+__device__ __forceinline__ void reduce_zrange_block(float& zl, float& zh, float& em, float* s_z) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        zl = fminf(zl, __shfl_xor(zl, off, 64));
+        zh = fmaxf(zh, __shfl_xor(zh, off, 64));
+        em = fmaxf(em, __shfl_xor(em, off, 64));
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        s_z[3 * (threadIdx.x >> 6)] = zl;
+        s_z[3 * (threadIdx.x >> 6) + 1] = zh;
+        s_z[3 * (threadIdx.x >> 6) + 2] = em;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) {
-            mn = vmin(mn, mk(s_red[6 * k + 0], s_red[6 * k + 1], s_red[6 * k + 2]));
-            mx = vmax(mx, mk(s_red[6 * k + 3], s_red[6 * k + 4], s_red[6 * k + 5]));
+        zl = INFINITY, zh = -INFINITY, em = 0.f;
+        for (uint32_t w = 0; w < WAVES; w++) {
+            zl = fminf(zl, s_z[3 * w]);
+            zh = fmaxf(zh, s_z[3 * w + 1]);
+            em = fmaxf(em, s_z[3 * w + 2]);
         }
     }
+}
+// inclusive scan over the wave's lanes
+__device__ __forceinline__ uint32_t wave_scan(uint32_t x) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if ((int)(threadIdx.x & 63u) >= d) x += y;
+    }
+    return x;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bounds(const float4* __restrict__ opos, uint32_t V, float* __restrict__ bounds) {
@@ -104,26 +155,21 @@ __global__ __launch_bounds__(BLOCK) void k_bounds(const float4* __restrict__ opo
         mn = vmin(mn, mk(p.x, p.y, p.z));
         mx = vmax(mx, mk(p.x, p.y, p.z));
     }
-    reduce_box_block(mn, mx, s_red);
-    if (threadIdx.x == 0) {
-        float* o = bounds + 8 + 6 * (size_t)blockIdx.x;
-        o[0] = mn.x; o[1] = mn.y; o[2] = mn.z; o[3] = mx.x; o[4] = mx.y; o[5] = mx.z;
-    }
+    reduce_box_block<BLOCK / 64>(mn, mx, s_red);
+    if (threadIdx.x == 0) st_box(bounds + 8 + 6 * (size_t)blockIdx.x, mn, mx);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bounds_final(float* __restrict__ bounds, uint32_t nparts) {
     __shared__ float s_red[24];
     f3 mn = mk(INFINITY, INFINITY, INFINITY), mx = mk(-INFINITY, -INFINITY, -INFINITY);
     for (uint32_t i = threadIdx.x; i < nparts; i += BLOCK) {
-        const float* p = bounds + 8 + 6 * (size_t)i;
-        mn = vmin(mn, mk(p[0], p[1], p[2]));
-        mx = vmax(mx, mk(p[3], p[4], p[5]));
+        f3 pn, px;
+        ld_box(bounds + 8 + 6 * (size_t)i, pn, px);
+        mn = vmin(mn, pn);
+        mx = vmax(mx, px);
     }
-    reduce_box_block(mn, mx, s_red);
-    if (threadIdx.x == 0) {
-        bounds[0] = mn.x; bounds[1] = mn.y; bounds[2] = mn.z;
-        bounds[3] = mx.x; bounds[4] = mx.y; bounds[5] = mx.z;
-    }
+    reduce_box_block<BLOCK / 64>(mn, mx, s_red);
+    if (threadIdx.x == 0) st_box(bounds, mn, mx);
 }
 
 // MortonCodes.hlsl:54-125 (HLSL mode) / ShaderSim/main.cpp:292-301 (CPUTests mode):
@@ -135,8 +181,8 @@ __device__ __forceinline__ uint32_t morton_code(const BuildArgs& a, uint32_t t, 
     const f3 c0 = xform_point(a.cam, p0), c1 = xform_point(a.cam, p1), c2 = xform_point(a.cam, p2);
     uint32_t code;
     if (a.morton_mode == 0) {
-        const f3 mn = mk(a.bounds[0], a.bounds[1], a.bounds[2]);
-        const f3 mx = mk(a.bounds[3], a.bounds[4], a.bounds[5]);
+        f3 mn, mx;
+        ld_box(a.bounds, mn, mx);
         const float xv = p0.x + p1.x + p2.x, yv = p0.y + p1.y + p2.y, zv = p0.z + p1.z + p2.z;
         const uint32_t qx = quantise_cputests((xv / 3.f - mn.x) / (mx.x - mn.x));
         const uint32_t qy = quantise_cputests((yv / 3.f - mn.y) / (mx.y - mn.y));
@@ -482,10 +528,7 @@ __device__ __forceinline__ void complete_node(const BuildArgs& a, uint32_t p, ui
     lo = vmin(l0, r0);
     hi = vmax(l1, r1);
     if (a.nbox) st_nbox(a.nbox, p, lo, hi);
-    if (e == INVALID) {
-        a.rootbox[0] = lo.x; a.rootbox[1] = lo.y; a.rootbox[2] = lo.z;
-        a.rootbox[3] = hi.x; a.rootbox[4] = hi.y; a.rootbox[5] = hi.z;
-    }
+    if (e == INVALID) st_rootbox(a, lo, hi);
 }
 
 // The largest leaf edge bound below a node (margin.h: its QNode's margin codes).  Where a QNode is
@@ -507,6 +550,24 @@ __device__ __forceinline__ float ld_edge_sc1(const float* src) {
         __hip_atomic_load(reinterpret_cast<const uint32_t*>(src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
+// One arrival at node p's global ticket by the climber of its child `side`, whose box (lo, hi) and bound
+// em are in inner[p] already (refit_climb's sc1 stores, or an earlier launch's).  The first arriver
+// leaves (false).  The second -- told by the value its add returned -- reads the sibling's box and bound
+// with sc1 loads only, completes p, and goes on with p's box, bound and parent link e.
+__device__ __forceinline__ bool global_arrive(const BuildArgs& a, uint32_t p, uint32_t side, f3& lo, f3& hi, float& em,
+                                              uint32_t& e) {
+    const uint32_t old = __hip_atomic_fetch_add(&a.refit_cnt[p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == 0) return false;
+    asm volatile("" ::: "memory");
+    f3 smin, smax;
+    ld_box_sc1(side ? a.inner[p].lmin : a.inner[p].rmin, smin, smax);
+    em = fmaxf(em, ld_edge_sc1(hand_edge(a, p, side ^ 1u)));
+    *node_edge(a, p) = em;   // (read by k_qnodes_late / k_qnodes, later launches)
+    e = a.pint[p];
+    if (side) complete_node(a, p, e, smin, smax, lo, hi, lo, hi);
+    else      complete_node(a, p, e, lo, hi, smin, smax, lo, hi);
+    return true;
+}
 // The global climb, for the nodes whose leaf range crosses a refit workgroup: from a complete
 // node (box lo, hi, edge bound em; e = its parent link) upward, the child box and bound handed
 // over through inner[p] (sc1) and a per-node ticket; the second arriver completes p and goes on.
@@ -519,16 +580,7 @@ __device__ __forceinline__ void refit_climb(f3 lo, f3 hi, float em, uint32_t e, 
         st_box_sc1(side ? a.inner[p].rmin : a.inner[p].lmin, lo, hi);
         st_edge_sc1(hand_edge(a, p, side), em);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the box stores before the ticket
-        const uint32_t old = __hip_atomic_fetch_add(&a.refit_cnt[p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) return;
-        asm volatile("" ::: "memory");
-        f3 smin, smax;
-        ld_box_sc1(side ? a.inner[p].lmin : a.inner[p].rmin, smin, smax);
-        em = fmaxf(em, ld_edge_sc1(hand_edge(a, p, side ^ 1u)));
-        *node_edge(a, p) = em;   // (read by k_qnodes_late / k_qnodes, later launches)
-        e = a.pint[p];
-        if (side) complete_node(a, p, e, smin, smax, lo, hi, lo, hi);
-        else      complete_node(a, p, e, lo, hi, smin, smax, lo, hi);
+        if (!global_arrive(a, p, side, lo, hi, em, e)) return;
     }
 }
 
@@ -536,6 +588,30 @@ __device__ __forceinline__ void refit_climb(f3 lo, f3 hi, float em, uint32_t e, 
 __device__ __forceinline__ bool crossing(uint4 topo_k, uint32_t k) {
     const uint32_t base = k & ~(RBLOCK - 1);
     return !(topo_k.z >= base && topo_k.w < base + RBLOCK);
+}
+
+// One arrival at a node's LDS ticket (k_refit's in-block climb, k_build_small) by the climber of its
+// child `side`, in two steps with the caller's exit between them: `if (!(tk = lds_arrive(..))) break;
+// lds_second(.., tk, ..)`.  (As one function returning whether the lane goes on, the compiler kept the
+// returned flag's join inside the loop: 12 more instructions per level in k_refit.)  `row` holds the
+// node's two child boxes.  The ticket carries the edge bound: atomicMax of (bound | bit 31) -- nonzero,
+// ordered as the bounds (non-negative floats order as their bits) -- so the first arriver sees 0 and
+// stops, the second sees the sibling's bound, and the word ends as the node's own.
+__device__ __forceinline__ uint32_t lds_arrive(float (*row)[6], uint32_t* ticket, uint32_t side, f3 lo, f3 hi, float em) {
+    st_box(row[side], lo, hi);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS box lands before the ticket
+    return atomicMax(ticket, __float_as_uint(em) | 0x80000000u);
+}
+// ... the second arriver (tk != 0) goes on with the node's box and bound in lo, hi, em and its parent
+// link *link in e
+__device__ __forceinline__ void lds_second(float (*row)[6], uint32_t tk, const uint32_t* link, uint32_t side, f3& lo,
+                                           f3& hi, float& em, uint32_t& e) {
+    em = fmaxf(em, __uint_as_float(tk & 0x7FFFFFFFu));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    f3 smin, smax;
+    ld_box(row[side ^ 1u], smin, smax);
+    e = *link;
+    unite(side, lo, hi, smin, smax);
 }
 
 // ---- quantized 4-wide nodes (rtbvh_device.h QNode) ---------------------------------
@@ -724,10 +800,9 @@ __device__ __forceinline__ void qnode_from_records(Inner* __restrict__ rec, uint
                        ent);
     store4(dst, w);
     if (PSEUDO_NOGRID && w[0].w == 0.f) {
-        if (e0.id & LEAF_BIT)
-            store_pseudo_record(rec + e0.slot, e0.id, mk(e0.b[0], e0.b[1], e0.b[2]), mk(e0.b[3], e0.b[4], e0.b[5]));
-        if (e1.id & LEAF_BIT)
-            store_pseudo_record(rec + e1.slot, e1.id, mk(e1.b[0], e1.b[1], e1.b[2]), mk(e1.b[3], e1.b[4], e1.b[5]));
+        f3 lo, hi;
+        if (e0.id & LEAF_BIT) { ld_box(e0.b, lo, hi); store_pseudo_record(rec + e0.slot, e0.id, lo, hi); }
+        if (e1.id & LEAF_BIT) { ld_box(e1.b, lo, hi); store_pseudo_record(rec + e1.slot, e1.id, lo, hi); }
     }
 }
 
@@ -774,7 +849,9 @@ __global__ __launch_bounds__(BLOCK) void k_records(BuildArgs a) {
     float l[6], r[6];
     child_box(a, t.x, l);
     child_box(a, t.y, r);
-    const f3 l0 = mk(l[0], l[1], l[2]), l1 = mk(l[3], l[4], l[5]), r0 = mk(r[0], r[1], r[2]), r1 = mk(r[3], r[4], r[5]);
+    f3 l0, l1, r0, r1;
+    ld_box(l, l0, l1);
+    ld_box(r, r0, r1);
     const uint32_t slot = slot_of(a.pint[k], a.T);
     store_record(a.rec + slot, l0, l1, r0, r1, t.x, t.y, k);
     if (a.qnode && reinterpret_cast<const float4*>(a.qnode + slot)[0].w == 0.f) {
@@ -790,7 +867,10 @@ __global__ __launch_bounds__(BLOCK) void k_nbox(BuildArgs a) {
     float l[6], q[6];
     record_box(r, 0, l);
     record_box(r, 1, q);
-    st_nbox(a.nbox, k, vmin(mk(l[0], l[1], l[2]), mk(q[0], q[1], q[2])), vmax(mk(l[3], l[4], l[5]), mk(q[3], q[4], q[5])));
+    f3 l0, l1, r0, r1;
+    ld_box(l, l0, l1);
+    ld_box(q, r0, r1);
+    st_nbox(a.nbox, k, vmin(l0, r0), vmax(l1, r1));
 }
 
 // Refit (BVHConstructP2.hlsl:8-37) fused with the leaf records and the node outputs.  One
@@ -852,12 +932,8 @@ __global__ __launch_bounds__(RBLOCK) void k_refit(BuildArgs a) {
                        reinterpret_cast<float4*>(&s_box[0][0][0]) + 128 * (tid >> 6));
     }
     if (i < T) {
-        if (T == 1) {
-            a.rootbox[0] = lo.x; a.rootbox[1] = lo.y; a.rootbox[2] = lo.z;
-            a.rootbox[3] = hi.x; a.rootbox[4] = hi.y; a.rootbox[5] = hi.z;
-        } else {
-            e = a.pleaf[i];
-        }
+        if (T == 1) st_rootbox(a, lo, hi);
+        else e = a.pleaf[i];
     }
     {   // the block's depth range (min lo.z, max hi.z of its leaves) for k_zrange: the binned primary
         // pass buckets by depth as soon as the leaves are written, before the climb above the blocks
@@ -866,29 +942,12 @@ __global__ __launch_bounds__(RBLOCK) void k_refit(BuildArgs a) {
         // bounds only: a subtree holding a non-finite triangle is never pruned by distance, its QNodes'
         // tcap being -1)
         float zl = i < T ? lo.z : INFINITY, zh = i < T ? hi.z : -INFINITY, em = emax < INFINITY ? emax : 0.f;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            zl = fminf(zl, __shfl_xor(zl, off, 64));
-            zh = fmaxf(zh, __shfl_xor(zh, off, 64));
-            em = fmaxf(em, __shfl_xor(em, off, 64));
+        reduce_zrange_block<RBLOCK / 64>(zl, zh, em, s_topo_z);   // (its barrier: s_cnt, s_topo, s_pint are set)
+        if (tid == 0) {
+            a.zpart[ZPART * blockIdx.x] = zl;
+            a.zpart[ZPART * blockIdx.x + 1] = zh;
+            a.zpart[ZPART * blockIdx.x + 2] = em;
         }
-        if ((tid & 63u) == 0) {
-            s_topo_z[3 * (tid >> 6)] = zl;
-            s_topo_z[3 * (tid >> 6) + 1] = zh;
-            s_topo_z[3 * (tid >> 6) + 2] = em;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float zl = INFINITY, zh = -INFINITY, em = 0.f;
-        for (uint32_t w = 0; w < RBLOCK / 64; w++) {
-            zl = fminf(zl, s_topo_z[3 * w]);
-            zh = fmaxf(zh, s_topo_z[3 * w + 1]);
-            em = fmaxf(em, s_topo_z[3 * w + 2]);
-        }
-        a.zpart[ZPART * blockIdx.x] = zl;
-        a.zpart[ZPART * blockIdx.x + 1] = zh;
-        a.zpart[ZPART * blockIdx.x + 2] = em;
     }
     for (int level = 0; e != INVALID && level < 2 * STACK_SIZE; level++) {
         const uint32_t p = e >> 1, side = e & 1u;
@@ -899,31 +958,15 @@ __global__ __launch_bounds__(RBLOCK) void k_refit(BuildArgs a) {
             cross = !(q3.z >= base && q3.w < end);
         }
         if (cross) {   // k_refit_group takes it from here (kernel boundary: plain stores)
-            float* hb = side ? a.inner[p].rmin : a.inner[p].lmin;
-            hb[0] = lo.x; hb[1] = lo.y; hb[2] = lo.z; hb[3] = hi.x; hb[4] = hi.y; hb[5] = hi.z;
+            st_box(side ? a.inner[p].rmin : a.inner[p].lmin, lo, hi);
             *hand_edge(a, p, side) = emax;
             break;
         }
-        float* sb = s_box[p - base][side];
-        sb[0] = lo.x; sb[1] = lo.y; sb[2] = lo.z; sb[3] = hi.x; sb[4] = hi.y; sb[5] = hi.z;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS box lands before the ticket
-        // the ticket carries the edge bound: atomicMax of (bound | bit 31) -- nonzero, ordered as the
-        // bounds (non-negative floats order as their bits) -- so the first arriver sees 0, the second
-        // the sibling's bound, and the word ends as the node's own (phase 3 reads it)
-        const uint32_t tk = atomicMax(&s_cnt[p - base], __float_as_uint(emax) | 0x80000000u);
+        // (the ticket word ends as the node's edge bound: phase 3 reads it)
+        const uint32_t tk = lds_arrive(s_box[p - base], &s_cnt[p - base], side, lo, hi, emax);
         if (tk == 0) break;
-        emax = fmaxf(emax, __uint_as_float(tk & 0x7FFFFFFFu));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const float* ob = s_box[p - base][side ^ 1u];
-        const f3 smin = mk(ob[0], ob[1], ob[2]), smax = mk(ob[3], ob[4], ob[5]);
-        // union in (childL, childR) order, as the reference
-        if (side) { lo = vmin(smin, lo); hi = vmax(smax, hi); }
-        else      { lo = vmin(lo, smin); hi = vmax(hi, smax); }
-        e = s_pint[p - base];
-        if (e == INVALID) {
-            a.rootbox[0] = lo.x; a.rootbox[1] = lo.y; a.rootbox[2] = lo.z;
-            a.rootbox[3] = hi.x; a.rootbox[4] = hi.y; a.rootbox[5] = hi.z;
-        }
+        lds_second(s_box[p - base], tk, &s_pint[p - base], side, lo, hi, emax, e);
+        if (e == INVALID) st_rootbox(a, lo, hi);
     }
     __syncthreads();
     // the block's crossing nodes (k_refit_group completes them, k_qnodes_late quantizes them):
@@ -951,10 +994,8 @@ __global__ __launch_bounds__(RBLOCK) void k_refit(BuildArgs a) {
     uint32_t ent[4] = {INVALID, INVALID, INVALID, INVALID};
     float E = 0.f;   // the node's edge bound: its QNode's margin codes, added once the QNode is known to be read
     if (mine) {
-    const float* L = s_box[tid][0];
-    const float* R = s_box[tid][1];
-    l0 = mk(L[0], L[1], L[2]); l1 = mk(L[3], L[4], L[5]);
-    r0 = mk(R[0], R[1], R[2]); r1 = mk(R[3], R[4], R[5]);
+    ld_box(s_box[tid][0], l0, l1);
+    ld_box(s_box[tid][1], r0, r1);
     slot = slot_of(s_pint[tid], T);
     record_words(l0, l1, r0, r1, q.x, q.y, i, rw);
     if (a.nbox) st_nbox(a.nbox, i, vmin(l0, r0), vmax(l1, r1));   // (its own box; node-indexed: coalesced)
@@ -1099,30 +1140,22 @@ __device__ __forceinline__ void refit_top_node(const BuildArgs& a, uint32_t k) {
     const bool ncl = (q.x & LEAF_BIT) || !crossing(a.topo[q.x], q.x);
     const bool ncr = (q.y & LEAF_BIT) || !crossing(a.topo[q.y], q.y);
     if (!ncl && !ncr) return;
-    const float* L = a.inner[k].lmin;
-    const float* R = a.inner[k].rmin;
     f3 lo, hi;
     float em;
-    uint32_t e = a.pint[k];
+    uint32_t e;
     if (ncl && ncr) {
+        f3 r0, r1;
+        ld_box(a.inner[k].lmin, lo, hi);
+        ld_box(a.inner[k].rmin, r0, r1);
         em = fmaxf(*hand_edge(a, k, 0), *hand_edge(a, k, 1));
         *node_edge(a, k) = em;
-        complete_node(a, k, e, mk(L[0], L[1], L[2]), mk(L[3], L[4], L[5]), mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]),
-                      lo, hi);
-    } else {   // one child here: its arrival at k's ticket (the other side's box and bound come sc1)
+        e = a.pint[k];
+        complete_node(a, k, e, lo, hi, r0, r1, lo, hi);
+    } else {   // one child here (read plainly: an earlier launch wrote it): its arrival at k's ticket
         const uint32_t side = ncl ? 0u : 1u;
-        const float* B = side ? R : L;
-        const f3 blo = mk(B[0], B[1], B[2]), bhi = mk(B[3], B[4], B[5]);
+        ld_box(side ? a.inner[k].rmin : a.inner[k].lmin, lo, hi);
         em = *hand_edge(a, k, side);
-        const uint32_t old = __hip_atomic_fetch_add(&a.refit_cnt[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) return;
-        asm volatile("" ::: "memory");
-        f3 smin, smax;
-        ld_box_sc1(side ? a.inner[k].lmin : a.inner[k].rmin, smin, smax);
-        em = fmaxf(em, ld_edge_sc1(hand_edge(a, k, side ^ 1u)));
-        *node_edge(a, k) = em;
-        if (side) complete_node(a, k, e, smin, smax, blo, bhi, lo, hi);
-        else      complete_node(a, k, e, blo, bhi, smin, smax, lo, hi);
+        if (!global_arrive(a, k, side, lo, hi, em, e)) return;
     }
     refit_climb(lo, hi, em, e, a);
 }
@@ -1163,12 +1196,7 @@ __global__ __launch_bounds__(GBLOCK) void k_refit_group(BuildArgs a) {
     if (tid < 64) {   // the lists' offsets (RGROUP <= 64: one wave)
         static_assert(RGROUP <= 64, "one wave scans the group's list counts");
         const uint32_t v = tid < nbg ? a.xcnt[b0 + tid] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if ((int)lane >= d) x += y;
-        }
+        const uint32_t x = wave_scan(v);
         if (tid < nbg) s_off[tid] = x - v;
         if (tid == nbg - 1) s_off[nbg] = x;
     }
@@ -1205,12 +1233,7 @@ __global__ __launch_bounds__(GBLOCK) void k_refit_group(BuildArgs a) {
     {   // the word ranks: an exclusive scan of the words' popcounts (GSPAN / 32 = GBLOCK words, one a thread)
         static_assert(GSPAN / 32 == GBLOCK, "one bitmap word per thread");
         const uint32_t v = (uint32_t)__popc(s_bits[tid]);
-        uint32_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if ((int)lane >= d) x += y;
-        }
+        const uint32_t x = wave_scan(v);
         if (lane == 63) s_wsum[wv] = x;
         __syncthreads();
         uint32_t before = 0;
@@ -1262,20 +1285,20 @@ __global__ __launch_bounds__(GBLOCK) void k_refit_group(BuildArgs a) {
         uint32_t sl = tid;
         for (int level = 0; level < 2 * STACK_SIZE; level++) {   // (bounded: a CPUTests-delta tree may cycle)
             const uint32_t k = s_sid[sl];
-            const float* L = s_gbox[sl][0];
-            const float* R = s_gbox[sl][1];
             const float em = fmaxf(s_ge[sl][0], s_ge[sl][1]);
             *node_edge(a, k) = em;   // (read by k_qnodes_late, a later launch)
             const uint32_t e = s_par[sl];
-            f3 lo, hi;
-            complete_node(a, k, e, mk(L[0], L[1], L[2]), mk(L[3], L[4], L[5]), mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]),
-                          lo, hi);
+            f3 lo, hi, r0, r1;
+            ld_box(s_gbox[sl][0], lo, hi);
+            ld_box(s_gbox[sl][1], r0, r1);
+            complete_node(a, k, e, lo, hi, r0, r1, lo, hi);
             if (e == INVALID) break;   // the root
             const uint32_t p = e >> 1, side = e & 1u;
             const uint32_t sp = listed(p) ? slot_of_k(p) : GCAP;
-            if (sp < GCAP && s_tk[sp] != 3) {   // a group-internal parent: its ticket in LDS
-                float* d = s_gbox[sp][side];
-                d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = hi.x; d[4] = hi.y; d[5] = hi.z;
+            // a group-internal parent: its ticket in LDS (a counting one, not lds_arrive's: it starts at the
+            // children k_refit handed over, and the second arriver takes both boxes and bounds at the loop's top)
+            if (sp < GCAP && s_tk[sp] != 3) {
+                st_box(s_gbox[sp][side], lo, hi);
                 s_ge[sp][side] = em;
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the box lands before the ticket
                 const uint32_t old = atomicAdd(&s_tk[sp], 1u);
@@ -1311,10 +1334,10 @@ __global__ __launch_bounds__(BLOCK, 8) void k_pb_count_late(BuildArgs b, TraceAr
 __global__ __launch_bounds__(BLOCK) void k_refit_boxes(BuildArgs a, const float* __restrict__ boxes) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= a.T) return;
-    const float* b = boxes + 6 * (size_t)i;
-    const f3 lo = mk(b[0], b[1], b[2]), hi = mk(b[3], b[4], b[5]);
+    f3 lo, hi;
+    ld_box(boxes + 6 * (size_t)i, lo, hi);
     if (a.T == 1) {
-        for (int k = 0; k < 6; k++) a.rootbox[k] = b[k];
+        st_rootbox(a, lo, hi);
         return;
     }
     refit_climb(lo, hi, INFINITY, a.pleaf[i], a);   // (no triangles: no margin; the walk never prunes by distance)
@@ -1340,6 +1363,65 @@ struct LdsCodes {   // sorted code j = the high word of the sorted 64-bit key
     const uint64_t* kv;
     __device__ uint32_t operator[](int32_t j) const { return (uint32_t)(kv[j] >> 32); }
 };
+
+// The bitonic network over the N = KPT * SMALL_BLOCK 64-bit keys of a 1024-thread workgroup, ascending:
+// thread tid holds keys KPT tid + b in e[b].  The compare-exchanges at distance j < KPT are in the thread
+// (constant indices: e stays in registers), those at j < 64 KPT across lanes (tid ^ j / KPT), and only the
+// longer ones go through LDS (s_kv: N keys) with a barrier per step (KPT = 2: 10 of the 66 steps; all
+// through LDS: 26 us of k_build_small's 79).  No barrier follows the last reads of s_kv: before one, a
+// thread may rewrite only its own places KPT tid + b.
+template <uint32_t KPT>
+__device__ __forceinline__ void bitonic_sort(uint64_t (&e)[KPT], uint64_t* s_kv, uint32_t tid) {
+    constexpr uint32_t N = KPT * SMALL_BLOCK;
+    for (uint32_t k = 2; k <= N; k <<= 1) {
+        uint32_t j = k >> 1;
+        if (j >= 64 * KPT) {
+#pragma unroll
+            for (uint32_t b = 0; b < KPT; b++) s_kv[KPT * tid + b] = e[b];
+            __syncthreads();
+            for (; j >= 64 * KPT; j >>= 1) {
+#pragma unroll
+                for (uint32_t h = 0; h < KPT / 2; h++) {
+                    const uint32_t p = tid + h * SMALL_BLOCK;   // pair p: index i with bit j clear, and i | j
+                    const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+                    const uint64_t x = s_kv[i], y = s_kv[l];
+                    const bool up = (i & k) == 0, lt = x < y;
+                    s_kv[i] = up == lt ? x : y;
+                    s_kv[l] = up == lt ? y : x;
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (uint32_t b = 0; b < KPT; b++) e[b] = s_kv[KPT * tid + b];
+        }
+        for (; j >= KPT; j >>= 1) {   // partner lane tid ^ (j / KPT)
+            const uint32_t m = j / KPT;
+#pragma unroll
+            for (uint32_t b = 0; b < KPT; b++) {
+                const uint32_t i = KPT * tid + b;
+                const uint64_t x = e[b];
+                const uint32_t ylo = (uint32_t)__shfl_xor((int)(uint32_t)x, (int)m, 64);
+                const uint32_t yhi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), (int)m, 64);
+                const uint64_t y = (uint64_t)yhi << 32 | ylo;
+                const bool keep_min = ((i & j) == 0) == ((i & k) == 0);
+                e[b] = keep_min == (x < y) ? x : y;
+            }
+        }
+#pragma unroll
+        for (uint32_t jj = KPT / 2; jj >= 1; jj >>= 1) {   // in the thread (jj a constant: e stays in registers)
+            if (jj > j) continue;   // (stages k < KPT start below KPT / 2)
+#pragma unroll
+            for (uint32_t b = 0; b < KPT; b++) {
+                if (b & jj) continue;
+                const uint32_t i = KPT * tid + b;
+                const uint64_t x = e[b], y = e[b | jj];
+                const bool sw = ((i & k) == 0) != (x < y);
+                e[b] = sw ? y : x;
+                e[b | jj] = sw ? x : y;
+            }
+        }
+    }
+}
 
 // RTBVH_SMALL_PROBE (A/B builds only): thread 0 prints the constant-rate clock at the phase ends
 #ifdef RTBVH_SMALL_PROBE
@@ -1371,36 +1453,12 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_build_small(BuildArgs a, uint32
             mn = vmin(mn, mk(p.x, p.y, p.z));
             mx = vmax(mx, mk(p.x, p.y, p.z));
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn.x = fminf(mn.x, __shfl_xor(mn.x, off, 64));
-            mn.y = fminf(mn.y, __shfl_xor(mn.y, off, 64));
-            mn.z = fminf(mn.z, __shfl_xor(mn.z, off, 64));
-            mx.x = fmaxf(mx.x, __shfl_xor(mx.x, off, 64));
-            mx.y = fmaxf(mx.y, __shfl_xor(mx.y, off, 64));
-            mx.z = fmaxf(mx.z, __shfl_xor(mx.z, off, 64));
-        }
-        const uint32_t w = tid >> 6;
-        if ((tid & 63) == 0) {
-            s_red[6 * w + 0] = mn.x; s_red[6 * w + 1] = mn.y; s_red[6 * w + 2] = mn.z;
-            s_red[6 * w + 3] = mx.x; s_red[6 * w + 4] = mx.y; s_red[6 * w + 5] = mx.z;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int k = 1; k < 16; k++) {
-                mn = vmin(mn, mk(s_red[6 * k + 0], s_red[6 * k + 1], s_red[6 * k + 2]));
-                mx = vmax(mx, mk(s_red[6 * k + 3], s_red[6 * k + 4], s_red[6 * k + 5]));
-            }
-            a.bounds[0] = mn.x; a.bounds[1] = mn.y; a.bounds[2] = mn.z;
-            a.bounds[3] = mx.x; a.bounds[4] = mx.y; a.bounds[5] = mx.z;
-        }
+        reduce_box_block<SMALL_BLOCK / 64>(mn, mx, s_red);
+        if (tid == 0) st_box(a.bounds, mn, mx);
         __syncthreads();   // morton_tri reads the box back (same workgroup: visible)
     }
     SMALL_MARK(1);
-    // the bitonic network over all SMALL_T keys (padding ~0: above every key), thread tid holding
-    // keys 2 tid and 2 tid + 1 in registers: the compare-exchanges at distance j < 128 are within
-    // the wave (j = 1 in the thread, 2..64 across lanes tid ^ j/2), only j >= 128 goes through LDS
-    // with a barrier per step (10 of the 66 steps; all through LDS: 26 us of the 79)
+    // all SMALL_T keys (padding ~0: above every key), thread tid holding keys 2 tid and 2 tid + 1
     uint64_t e[2];
 #pragma unroll
     for (uint32_t b = 0; b < 2; b++) {
@@ -1408,43 +1466,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_build_small(BuildArgs a, uint32
         e[b] = t < T ? ((uint64_t)morton_tri(a, t) << 32 | t) : ~0ull;
     }
     SMALL_MARK(2);
-    for (uint32_t k = 2; k <= SMALL_T; k <<= 1) {
-        uint32_t j = k >> 1;
-        if (j >= 128) {
-            s_kv[2 * tid] = e[0];
-            s_kv[2 * tid + 1] = e[1];
-            __syncthreads();
-            for (; j >= 128; j >>= 1) {
-                // pair tid: index i with bit j clear (tid with a 0 inserted at bit j) and i | j
-                const uint32_t i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
-                const uint64_t x = s_kv[i], y = s_kv[l];
-                const bool up = (i & k) == 0, lt = x < y;
-                s_kv[i] = up == lt ? x : y;
-                s_kv[l] = up == lt ? y : x;
-                __syncthreads();
-            }
-            e[0] = s_kv[2 * tid];
-            e[1] = s_kv[2 * tid + 1];
-        }
-        for (; j >= 2; j >>= 1) {
-            const uint32_t m = j >> 1;   // partner lane distance
-#pragma unroll
-            for (uint32_t b = 0; b < 2; b++) {
-                const uint32_t i = 2 * tid + b;
-                const uint64_t x = e[b];
-                const uint32_t ylo = (uint32_t)__shfl_xor((int)(uint32_t)x, (int)m, 64);
-                const uint32_t yhi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), (int)m, 64);
-                const uint64_t y = (uint64_t)yhi << 32 | ylo;
-                const bool keep_min = ((i & j) == 0) == ((i & k) == 0);
-                e[b] = keep_min == (x < y) ? x : y;
-            }
-        }
-        const bool up = ((2 * tid) & k) == 0;   // j = 1: the thread's own pair
-        const bool sw = up != (e[0] < e[1]);
-        const uint64_t x0 = e[0];
-        e[0] = sw ? e[1] : x0;
-        e[1] = sw ? x0 : e[1];
-    }
+    bitonic_sort(e, s_kv, tid);
     s_kv[2 * tid] = e[0];
     s_kv[2 * tid + 1] = e[1];
     SMALL_MARK(3);
@@ -1509,44 +1531,26 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_build_small(BuildArgs a, uint32
         if (i >= T) continue;
         f3 lo = llo[b], hi = lhi[b];
         float em = lem[b];
-        if (T == 1) {
-            a.rootbox[0] = lo.x; a.rootbox[1] = lo.y; a.rootbox[2] = lo.z;
-            a.rootbox[3] = hi.x; a.rootbox[4] = hi.y; a.rootbox[5] = hi.z;
-            a.rootbox[6] = lo.z; a.rootbox[7] = hi.z;   // (k_zrange's: the root box's depth range)
-            continue;
-        }
-        uint32_t e = s_pleaf[i];
-        store_pseudo_record(a.rec + e, LEAF_BIT | i, lo, hi);
-        for (int level = 0; level < 2 * STACK_SIZE; level++) {
+        uint32_t e = T == 1 ? INVALID : s_pleaf[i];
+        if (e != INVALID) store_pseudo_record(a.rec + e, LEAF_BIT | i, lo, hi);
+        for (int level = 0; e != INVALID && level < 2 * STACK_SIZE; level++) {
             const uint32_t p = e >> 1, side = e & 1u;
-            float* sb = s_box[p][side];
-            sb[0] = lo.x; sb[1] = lo.y; sb[2] = lo.z; sb[3] = hi.x; sb[4] = hi.y; sb[5] = hi.z;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS box lands before the ticket
-            // the ticket carries the edge bound as k_refit's (the word ends as the node's bound)
-            const uint32_t tk = atomicMax(&s_cnt[p], __float_as_uint(em) | 0x80000000u);
+            const uint32_t tk = lds_arrive(s_box[p], &s_cnt[p], side, lo, hi, em);   // (the ticket ends as p's bound)
             if (tk == 0) break;
-            em = fmaxf(em, __uint_as_float(tk & 0x7FFFFFFFu));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const float* ob = s_box[p][side ^ 1u];
-            const f3 smin = mk(ob[0], ob[1], ob[2]), smax = mk(ob[3], ob[4], ob[5]);
-            e = s_pint[p];
-            if (side) { lo = vmin(smin, lo); hi = vmax(smax, hi); }
-            else      { lo = vmin(lo, smin); hi = vmax(hi, smax); }
-            if (e == INVALID) {
-                a.rootbox[0] = lo.x; a.rootbox[1] = lo.y; a.rootbox[2] = lo.z;
-                a.rootbox[3] = hi.x; a.rootbox[4] = hi.y; a.rootbox[5] = hi.z;
-                a.rootbox[6] = lo.z; a.rootbox[7] = hi.z;
-                break;
-            }
+            lds_second(s_box[p], tk, &s_pint[p], side, lo, hi, em, e);
+        }
+        if (e == INVALID) {   // this thread reached the root
+            st_rootbox(a, lo, hi);
+            a.rootbox[6] = lo.z; a.rootbox[7] = hi.z;   // (k_zrange's: the root box's depth range)
         }
     }
     __syncthreads();   // every node's two child boxes in LDS
     for (uint32_t p = tid; p + 1 < T; p += SMALL_BLOCK) {
-        const float* l = s_box[p][0];
-        const float* r = s_box[p][1];
+        f3 l0, l1, r0, r1;
+        ld_box(s_box[p][0], l0, l1);
+        ld_box(s_box[p][1], r0, r1);
         const uint2 ids = s_ids[p];
-        store_record(a.rec + slot_of(s_pint[p], T), mk(l[0], l[1], l[2]), mk(l[3], l[4], l[5]), mk(r[0], r[1], r[2]),
-                     mk(r[3], r[4], r[5]), ids.x, ids.y, p);
+        store_record(a.rec + slot_of(s_pint[p], T), l0, l1, r0, r1, ids.x, ids.y, p);
         *node_edge(a, p) = __uint_as_float(s_cnt[p] & 0x7FFFFFFFu);   // (k_qnodes: the QNode's margin)
     }
 #ifdef RTBVH_SMALL_PROBE
@@ -1560,15 +1564,13 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_build_small(BuildArgs a, uint32
 }
 
 // Scenes above k_build_small's 2048 triangles and up to 8192 (C2's Image_Test: 3072): the Morton pass
-// and the sort in one workgroup -- the same bitonic network over (code << 32 | triangle) keys as
-// k_build_small, KPT keys per thread (steps at distance < KPT in the thread, < 64 KPT across lanes, the
-// longer ones through LDS) -- in place of the Morton launch and the radix sort's twelve; the rest of the
+// and the sort in one workgroup -- bitonic_sort over (code << 32 | triangle) keys as k_build_small, KPT
+// keys per thread -- in place of the Morton launch and the radix sort's twelve; the rest of the
 // multi-kernel build follows.  (k_build_small's node boxes would not fit in LDS at this size.)
 template <uint32_t KPT>
 __global__ __launch_bounds__(SMALL_BLOCK) void k_morton_sort_small(BuildArgs a, uint32_t* __restrict__ sk,
                                                                    uint32_t* __restrict__ sv) {
-    constexpr uint32_t N = KPT * SMALL_BLOCK;
-    __shared__ uint64_t s_kv[N];
+    __shared__ uint64_t s_kv[KPT * SMALL_BLOCK];
     const uint32_t tid = threadIdx.x, T = a.T;
     uint64_t e[KPT];
 #pragma unroll
@@ -1576,54 +1578,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_morton_sort_small(BuildArgs a, 
         const uint32_t t = KPT * tid + b;
         e[b] = t < T ? ((uint64_t)morton_tri(a, t) << 32 | t) : ~0ull;
     }
-    for (uint32_t k = 2; k <= N; k <<= 1) {
-        uint32_t j = k >> 1;
-        if (j >= 64 * KPT) {
-#pragma unroll
-            for (uint32_t b = 0; b < KPT; b++) s_kv[KPT * tid + b] = e[b];
-            __syncthreads();
-            for (; j >= 64 * KPT; j >>= 1) {
-#pragma unroll
-                for (uint32_t h = 0; h < KPT / 2; h++) {
-                    const uint32_t p = tid + h * SMALL_BLOCK;   // pair p: index i with bit j clear, and i | j
-                    const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                    const uint64_t x = s_kv[i], y = s_kv[l];
-                    const bool up = (i & k) == 0, lt = x < y;
-                    s_kv[i] = up == lt ? x : y;
-                    s_kv[l] = up == lt ? y : x;
-                }
-                __syncthreads();
-            }
-#pragma unroll
-            for (uint32_t b = 0; b < KPT; b++) e[b] = s_kv[KPT * tid + b];
-        }
-        for (; j >= KPT; j >>= 1) {   // partner lane tid ^ (j / KPT)
-            const uint32_t m = j / KPT;
-#pragma unroll
-            for (uint32_t b = 0; b < KPT; b++) {
-                const uint32_t i = KPT * tid + b;
-                const uint64_t x = e[b];
-                const uint32_t ylo = (uint32_t)__shfl_xor((int)(uint32_t)x, (int)m, 64);
-                const uint32_t yhi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), (int)m, 64);
-                const uint64_t y = (uint64_t)yhi << 32 | ylo;
-                const bool keep_min = ((i & j) == 0) == ((i & k) == 0);
-                e[b] = keep_min == (x < y) ? x : y;
-            }
-        }
-#pragma unroll
-        for (uint32_t jj = KPT / 2; jj >= 1; jj >>= 1) {   // in the thread (jj a constant: e stays in registers)
-            if (jj > j) continue;   // (stages k < KPT start below KPT / 2)
-#pragma unroll
-            for (uint32_t b = 0; b < KPT; b++) {
-                if (b & jj) continue;
-                const uint32_t i = KPT * tid + b;
-                const uint64_t x = e[b], y = e[b | jj];
-                const bool sw = ((i & k) == 0) != (x < y);
-                e[b] = sw ? y : x;
-                e[b | jj] = sw ? x : y;
-            }
-        }
-    }
+    bitonic_sort(e, s_kv, tid);
 #pragma unroll
     for (uint32_t b = 0; b < KPT; b++) {
         const uint32_t i = KPT * tid + b;
@@ -1693,19 +1648,16 @@ void launch_karras(const BuildArgs& a, hipStream_t s) {
 }
 uint32_t small_build_max() { return SMALL_T; }
 uint32_t small_sort_max() { return 8 * SMALL_BLOCK; }
+// a one-workgroup kernel that sorts: it writes the sorted pairs itself (the sort's A buffers)
+static void launch_one_workgroup(void (*kernel)(BuildArgs, uint32_t*, uint32_t*), const BuildArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(SMALL_BLOCK), 0, s, a, const_cast<uint32_t*>(a.sorted_keys),
+                       const_cast<uint32_t*>(a.sorted_vals));
+}
 void launch_morton_sort_small(const BuildArgs& a, hipStream_t s) {
-    uint32_t* sk = const_cast<uint32_t*>(a.sorted_keys);
-    uint32_t* sv = const_cast<uint32_t*>(a.sorted_vals);
-    if (a.T <= 4 * SMALL_BLOCK)
-        hipLaunchKernelGGL(k_morton_sort_small<4>, dim3(1), dim3(SMALL_BLOCK), 0, s, a, sk, sv);
-    else
-        hipLaunchKernelGGL(k_morton_sort_small<8>, dim3(1), dim3(SMALL_BLOCK), 0, s, a, sk, sv);
+    launch_one_workgroup(a.T <= 4 * SMALL_BLOCK ? k_morton_sort_small<4> : k_morton_sort_small<8>, a, s);
 }
 void launch_build_small(const BuildArgs& a, hipStream_t s) {
-    uint32_t* sk = const_cast<uint32_t*>(a.sorted_keys);
-    uint32_t* sv = const_cast<uint32_t*>(a.sorted_vals);
-    if (a.delta_mode == 0) hipLaunchKernelGGL(k_build_small<0>, dim3(1), dim3(SMALL_BLOCK), 0, s, a, sk, sv);
-    else hipLaunchKernelGGL(k_build_small<1>, dim3(1), dim3(SMALL_BLOCK), 0, s, a, sk, sv);
+    launch_one_workgroup(a.delta_mode == 0 ? k_build_small<0> : k_build_small<1>, a, s);
 }
 void launch_qnodes(const BuildArgs& a, hipStream_t s) {
     if (a.T > 1)
@@ -1723,24 +1675,8 @@ __global__ __launch_bounds__(1024) void k_zrange(const float* __restrict__ zpart
         zh = fmaxf(zh, zpart[ZPART * b + 1]);
         em = fmaxf(em, zpart[ZPART * b + 2]);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        zl = fminf(zl, __shfl_xor(zl, off, 64));
-        zh = fmaxf(zh, __shfl_xor(zh, off, 64));
-        em = fmaxf(em, __shfl_xor(em, off, 64));
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        s_z[3 * (threadIdx.x >> 6)] = zl;
-        s_z[3 * (threadIdx.x >> 6) + 1] = zh;
-        s_z[3 * (threadIdx.x >> 6) + 2] = em;
-    }
-    __syncthreads();
+    reduce_zrange_block<16>(zl, zh, em, s_z);
     if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < 16; w++) {
-            zl = fminf(zl, s_z[3 * w]);
-            zh = fmaxf(zh, s_z[3 * w + 1]);
-            em = fmaxf(em, s_z[3 * w + 2]);
-        }
         rootbox[6] = zl;
         rootbox[7] = zh;
         rootbox[8] = em;
@@ -1752,20 +1688,22 @@ void launch_refit_leaves(const BuildArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL(k_refit<false>, dim3(nb), dim3(RBLOCK), 0, s, a);
     hipLaunchKernelGGL(k_zrange, dim3(1), dim3(1024), 0, s, a.zpart, nb, a.rootbox);
 }
+// The crossing nodes (none when one refit workgroup holds the tree), climbed: in LDS within a group, then
+// across.  Returns the blocks that quantize the nodes it listed (k_qnodes_late's work), 0: nothing to do.
+static uint32_t launch_refit_group(const BuildArgs& a, hipStream_t s) {
+    if (a.T <= RBLOCK) return 0;
+    const uint32_t nb = refit_blocks(a.T);
+    hipLaunchKernelGGL(k_refit_group, dim3((nb + RGROUP - 1) / RGROUP), dim3(GBLOCK), 0, s, a);
+    return min(1024u, (nb + 15) / 16);
+}
 void launch_pb_count_top(const BuildArgs& b, const TraceArgs& a, uint32_t* off, uint32_t* cur, uint4* bins, uint32_t cap,
                          uint32_t ntx, uint32_t leaf_blocks, hipStream_t s) {
-    const uint32_t nb = refit_blocks(b.T);
-    // the grouped climb first, then its list's QNodes beside the count
-    const uint32_t nlate = b.T > RBLOCK ? min(1024u, (nb + 15) / 16) : 0u;
-    if (nlate) hipLaunchKernelGGL(k_refit_group, dim3((nb + RGROUP - 1) / RGROUP), dim3(GBLOCK), 0, s, b);
+    const uint32_t nlate = launch_refit_group(b, s);   // the grouped climb first, then its list's QNodes beside the count
     hipLaunchKernelGGL(k_pb_count_late, dim3(nlate + leaf_blocks), dim3(BLOCK), 0, s, b, a, nlate, off, cur, bins, cap, ntx);
 }
 void launch_refit_tail(const BuildArgs& a, hipStream_t s) {
-    const uint32_t nb = refit_blocks(a.T);
-    if (a.T > RBLOCK) {   // the crossing nodes: climbed (in LDS within a group, then across), then quantized
-        hipLaunchKernelGGL(k_refit_group, dim3((nb + RGROUP - 1) / RGROUP), dim3(GBLOCK), 0, s, a);
-        hipLaunchKernelGGL(k_qnodes_late, dim3(min(1024u, (nb + 15) / 16)), dim3(BLOCK), 0, s, a);
-    }
+    const uint32_t nlate = launch_refit_group(a, s);
+    if (nlate) hipLaunchKernelGGL(k_qnodes_late, dim3(nlate), dim3(BLOCK), 0, s, a);
 }
 // leaf j's pseudo-record from its leaf record's box (the bytes k_refit<true> writes)
 __global__ __launch_bounds__(BLOCK) void k_pseudo(const float4* __restrict__ leaf, const uint32_t* __restrict__ pleaf,
@@ -1792,8 +1730,7 @@ void launch_export(const BuildArgs& a, void* out, hipStream_t s) {
     hipLaunchKernelGGL(k_export, dim3(blocks_for(2 * (size_t)a.T - 1)), dim3(BLOCK), 0, s, a, (RefNode*)out);
 }
 void launch_from_codes(const BuildArgs& a, const float* leaf_boxes, hipStream_t s) {
-    if (a.delta_mode == 0) hipLaunchKernelGGL(k_karras<0>, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(k_karras<1>, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a);
+    launch_karras(a, s);
     if (a.T > 1) (void)hipMemsetAsync(a.refit_cnt, 0, sizeof(uint32_t) * (a.T - 1), s);
     hipLaunchKernelGGL(k_refit_boxes, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a, leaf_boxes);
     launch_qnodes(a, s);

@@ -160,7 +160,7 @@ def test_build_matches_oracle_on_obj(name, morton_mode):
     _assert_nodes_equal(nodes, onodes, s.num_tris)
 
 
-@pytest.mark.parametrize("ntris", [1, 2, 5, 1000, 200_000])
+@pytest.mark.parametrize("ntris", [1, 2, 5, 512, 513, 1000, 32_768, 32_769, 200_000])
 def test_build_matches_oracle_synthetic(ntris):
     s = rt.synthetic(ntris, seed=0x5EED0004, half_extent=(50, 50, 50))
     wvp, wv = rt.camera_reference(1920, 1080)
