@@ -364,7 +364,20 @@ enum {
                                      unspecified).  Whether a ray hits equals the closest-hit answer */
     RTBVH_QUERY_SORT = 1u << 1,   /* walk the rays in (direction octant, origin Morton) order, as
                                      RTBVH_FLAG_SORT_BOUNCE does: same results, each at its ray's own index */
-    RTBVH_QUERY_COUNT = 1u << 2   /* count rays, hits and visits for rtbvh_query_counts (slower) */
+    RTBVH_QUERY_COUNT = 1u << 2,  /* count rays, hits and visits for rtbvh_query_counts (slower) */
+    /* (bits 3-7 are rejected) */
+    RTBVH_QUERY_CERTIFIED = 1u << 8 /* the same answer, faster: the certified 4-wide walk of a certified trace
+                                      on the quantized nodes, t_max as its initial bound; each hit
+                                     is checked against a per-ray certificate, and the rays without one -- and the
+                                     rays the walk's margin does not cover: a direction with |d| above 1 or a
+                                     component below 2^-20, |origin| above 2^90, NaN -- are re-traced in the reference
+                                     order by the plain kernel.  Closest-hit: {t, u, v, tri} bit-identical to
+                                     RTBVH_QUERY_CLOSEST's for every ray and t_max; with ANY: the same hit / miss
+                                     answer, a reported hit a genuine one within t_max.  Composes with ANY, SORT and
+                                     COUNT.  Where a certified trace cannot run -- a tree built with
+                                     RTBVH_DELTA_CPUTESTS, or a stack_limit below the capacity -- the plain kernel
+                                     takes every ray: RTBVH_OK and the same hits.  A build that wrote no quantized
+                                     nodes gets them derived on the first such query */
 };
 /* n rays at dev_rays and n hits at dev_hits (device memory of the context's device, 16-B aligned), hit k for
  * ray k, enqueued on `stream` (hipStream_t, NULL = the context stream).  The walk reads the tree the last build
@@ -375,6 +388,8 @@ enum {
  * The call only enqueues, with one exception: the first RTBVH_QUERY_SORT query of a context, and each one with
  * more rays than any before it, grows the sort's buffers, which waits on the host for the outstanding queries
  * and allocates device memory (size the first SORT query for the largest batch to keep later ones asynchronous).
+ * RTBVH_QUERY_CERTIFIED's re-trace list (one word per ray) grows in the same way: the first certified query of a
+ * context and each larger one wait on the host for the outstanding queries and allocate.
  * n == 0 returns RTBVH_OK and touches nothing; RTBVH_ERR_NOT_READY before a build; RTBVH_ERR_INVALID_ARG for
  * NULL pointers with n > 0, unknown mode bits, and n >= 2^31.  Rays that hit rtbvh_config.stack_limit end early
  * with the best hit found so far, and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW as after a
@@ -387,6 +402,14 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* ctx, const rtbvh_ray* dev_rays, uint64
 rtbvh_status rtbvh_query_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode);
 /* The last RTBVH_QUERY_COUNT query (waits for it): rays, hits, internal-node visits, leaf visits. */
 rtbvh_status rtbvh_query_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+/* ... and how its rays were answered: certified (by the 4-wide walk: a hit whose certificate passed, or an
+ * exhaustive miss), redone (re-traced in the reference order: the certificate failed, or the walk flagged the ray
+ * at a node without a grid or a stack overflow), uncovered (the margin does not cover the ray: the reference order
+ * from the start), fallback (a query that took the plain kernel for every ray: one without RTBVH_QUERY_CERTIFIED, or
+ * on a context where the certified walk cannot run).  The four sum to the query's rays.  For a certified query
+ * rtbvh_query_counts' visit words count what the kernels visited: 4-wide node steps as internal visits, plus the
+ * re-traces' visits; rays and hits stay exact.  RTBVH_ERR_NOT_READY before any counting query. */
+rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

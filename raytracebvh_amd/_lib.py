@@ -45,7 +45,7 @@ EXPORTS = [
     "rtbvh_texture_load", "rtbvh_texture_free", "rtbvh_srgb_table",
     "rtbvh_present", "rtbvh_save_bmp", "rtbvh_assemble_bands", "rtbvh_comm_unique_id", "rtbvh_comm_init",
     "rtbvh_comm_destroy", "rtbvh_trace_tiles",
-    "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts",
+    "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts", "rtbvh_query_walk_counts",
 ]
 COMM_ID_BYTES = 128
 
@@ -60,6 +60,7 @@ RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 QUERY_CLOSEST, QUERY_ANY, QUERY_SORT, QUERY_COUNT = 0, 1, 2, 4   # RTBVH_QUERY_*
+QUERY_CERTIFIED = 1 << 8
 
 
 class Config(ctypes.Structure):
@@ -203,6 +204,7 @@ def lib() -> ctypes.CDLL:
         "rtbvh_query_async": (i32, [vp, vp, u64, vp, u32, vp]),
         "rtbvh_query_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_query_counts": (i32, [vp, vp]),
+        "rtbvh_query_walk_counts": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -246,10 +246,13 @@ struct rtbvh_ctx {
     DevBuf<uint32_t> d_qsort;                // RTBVH_QUERY_SORT: 6 arrays of cap_qsort words (keys and values: in,
     DevBuf<uint32_t> d_qsort_scratch;        //   A, B), and the sort's digit counts; grown on demand
     size_t cap_qsort = 0;
+    DevBuf<uint32_t> d_qredo;                // RTBVH_QUERY_CERTIFIED: the re-trace list, cap_qredo words; grown on demand
+    size_t cap_qredo = 0;
     Event ev_query;
     bool query_busy = false;
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
     bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
+    uint64_t query_fallback = 0;             // ... its rays, when it took the present kernel for all of them; or 0
 };
 
 namespace {
@@ -2029,7 +2032,7 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
 rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, rtbvh_hit* dev_hits,
                                uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_QUERY_ANY | RTBVH_QUERY_SORT | RTBVH_QUERY_COUNT))
+    if (mode & ~(uint32_t)(RTBVH_QUERY_ANY | RTBVH_QUERY_SORT | RTBVH_QUERY_COUNT | RTBVH_QUERY_CERTIFIED))
         return fail(c, RTBVH_ERR_INVALID_ARG, "query: unknown mode bits");
     if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "query: 2^31 rays or more");
     if (n == 0) return RTBVH_OK;
@@ -2041,6 +2044,10 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     const bool any = (mode & RTBVH_QUERY_ANY) != 0, sort = (mode & RTBVH_QUERY_SORT) != 0;
     const bool count = (mode & RTBVH_QUERY_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
+    // RTBVH_QUERY_CERTIFIED: the certified 4-wide walk under a certified trace's conditions (plan_trace: a clz64
+    // tree, the full stack); otherwise the present kernel for every ray -- the same hits either way
+    const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
+    const bool cert = (mode & RTBVH_QUERY_CERTIFIED) != 0 && c->tree.clz64 && !limited;
     if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_SCRATCH_WORDS));
     if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
     if (sort && (n > c->cap_qsort || !c->d_qsort)) {
@@ -2052,11 +2059,25 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
         HIPC(c, c->d_qsort_scratch.alloc(sort_scratch_words(N)));
         c->cap_qsort = n;
     }
+    if (cert && (n > c->cap_qredo || !c->d_qredo)) {   // (earlier queries list in the old buffer: as the sort's)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        c->cap_qredo = 0;
+        HIPC(c, c->d_qredo.alloc((size_t)n));
+        c->cap_qredo = n;
+    }
     if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (cert) {   // the QNodes of a build that wrote none, derived once (behind the earlier queries: none reads them)
+        const rtbvh_status qs = ensure_form(c, QNODES, s);
+        if (qs) return qs;
+    }
     if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    // the work counters, and a counting query's count block behind them
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0,
-                           sizeof(uint32_t) * (count ? QUERY_SCRATCH_WORDS : NEXT_SEGS * NEXT_STRIDE), s));
+    // the work counters; behind them a counting query's count block and walk counts, a certified query's list
+    // length and its re-trace's work counters
+    // (a query that does not count leaves the last counting query's words alone)
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * (count ? QUERY_REDO_N_AT : QUERY_COUNTS_AT), s));
+    if (cert)
+        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REDO_N_AT, 0,
+                               sizeof(uint32_t) * (QUERY_SCRATCH_WORDS - QUERY_REDO_N_AT), s));
     QueryArgs a{};
     a.inner = c->d_rec;
     a.topo = c->d_topo;
@@ -2068,7 +2089,13 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     a.hits = reinterpret_cast<float4*>(dev_hits);
     a.n = N;
     a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + NEXT_SEGS * NEXT_STRIDE);
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_COUNTS_AT);
+    a.walk = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_WALK_AT);
+    a.qnode = c->d_qnode;
+    a.tclip = c->d_tclip;
+    a.redo = c->d_qredo;
+    a.redo_n = c->d_qscratch + QUERY_REDO_N_AT;
+    a.next2 = c->d_qscratch + QUERY_NEXT2_AT;
     a.overflow = c->d_ovf;
     const uint32_t lim = c->cfg.stack_limit;
     a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
@@ -2078,12 +2105,16 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
         launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
         a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
     }
-    launch_query(a, any, count, s);
+    if (cert) launch_query_certified(a, any, count, s);
+    else launch_query(a, any, count, s);
     rtbvh_status st = check_launch(c, "query kernels");
     HIPC(c, hipEventRecord(c->ev_query, s));
     c->query_busy = true;
     c->query_ovf = true;
-    if (count && !st) c->query_counted = true;
+    if (count && !st) {
+        c->query_counted = true;
+        c->query_fallback = cert ? 0 : n;
+    }
     return st;
 }
 
@@ -2112,8 +2143,19 @@ rtbvh_status rtbvh_query_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "count block words");
-    HIPC(c, hipMemcpy(out, c->d_qscratch + NEXT_SEGS * NEXT_STRIDE, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_COUNTS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->query_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_QUERY_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    // certified, redone, uncovered from the walk; a query that took the present kernel wrote none (zeroed)
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WALK_AT, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost));
+    out[3] = c->query_fallback;
     return RTBVH_OK;
 }
 

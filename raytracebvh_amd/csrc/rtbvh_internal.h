@@ -293,11 +293,25 @@ struct QueryArgs {
     unsigned long long* counts;     // RTBVH_QUERY_COUNT: [4] rays, hits, internal visits, leaf visits (zeroed)
     unsigned long long* overflow;   // the context's overflow word (TraceArgs::overflow)
     int stack_limit;          // <= STACK_SIZE
+    // a certified query (RTBVH_QUERY_CERTIFIED, launch_query_certified; null / unused otherwise)
+    const uint32_t* n_dev;    // k_query as the re-trace: the ray count on the device (perm: the list; n: its bound)
+    const QNode* qnode;       // [2T-1] the quantized 4-wide nodes (BuildArgs::qnode)
+    const float4* tclip;      // [TCS * T] the clip-space triangles (the certificate's leaf boxes)
+    uint32_t* redo;           // [n] the rays for the reference-order re-trace, and their count (zeroed)
+    uint32_t* redo_n;
+    uint32_t* next2;          // the re-trace's work counters (as next)
+    unsigned long long* walk; // RTBVH_QUERY_COUNT: [3] rays certified, redone, uncovered (zeroed)
 };
 constexpr uint32_t QUERY_COUNT_WORDS = 4;
-// words of a query's scratch block: the work counters, then the count block (8-byte aligned)
-constexpr uint32_t QUERY_SCRATCH_WORDS = NEXT_SEGS * NEXT_STRIDE + 2 * QUERY_COUNT_WORDS;
+// words of a query's scratch block: the work counters, then the count block and the walk counts (8-byte aligned),
+// the re-trace list's length, and the re-trace's work counters
+constexpr uint32_t QUERY_COUNTS_AT = NEXT_SEGS * NEXT_STRIDE, QUERY_WALK_AT = QUERY_COUNTS_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_REDO_N_AT = QUERY_WALK_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_NEXT2_AT = QUERY_REDO_N_AT + NEXT_STRIDE;
+constexpr uint32_t QUERY_SCRATCH_WORDS = QUERY_NEXT2_AT + NEXT_SEGS * NEXT_STRIDE;
 void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s);
+// the certified 4-wide walk (k_query_wide) and the reference-order re-trace of the rays it lists (k_query)
+void launch_query_certified(const QueryArgs& a, bool any, bool count, hipStream_t s);
 // the coherence keys of caller rays (launch_bounce_keys' scheme over the root box) and vals[i] = i
 void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
                        hipStream_t s);

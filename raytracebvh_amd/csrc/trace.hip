@@ -1842,11 +1842,16 @@ __device__ __forceinline__ bool bounce_apply(const TraceArgs& a, RayQ& e, uint32
 // bound t (every box above contains it: the slab test is monotone in the box, so they pass too, at every
 // bound the reference holds, all >= t).  The box is the leaf's: min / max of its clip-space vertices
 // (build.hip leaf_record_words, MortonCodes.hlsl:87-96), from the triangle's record.
-__device__ __forceinline__ bool leaf_certified(const TraceArgs& a, uint32_t tri, f3 o, f3 inv, float t) {
-    const float4* P = a.tclip + TCS * (size_t)tri;
+__device__ __forceinline__ void leaf_clip_box(const float4* __restrict__ tclip, uint32_t tri, f3& lo, f3& hi) {
+    const float4* P = tclip + TCS * (size_t)tri;
     const float4 a0 = P[0], a1 = P[1], a2 = P[2];
     const f3 v0 = mk(a0.x, a0.y, a0.z), v1 = mk(a1.x, a1.y, a1.z), v2 = mk(a2.x, a2.y, a2.z);
-    const f3 lo = vmin(vmin(v0, v1), v2), hi = vmax(vmax(v0, v1), v2);
+    lo = vmin(vmin(v0, v1), v2);
+    hi = vmax(vmax(v0, v1), v2);
+}
+__device__ __forceinline__ bool leaf_certified(const TraceArgs& a, uint32_t tri, f3 o, f3 inv, float t) {
+    f3 lo, hi;
+    leaf_clip_box(a.tclip, tri, lo, hi);
     float tm;
     return ray_box(o, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, true, t, tm);
 }
@@ -1998,106 +2003,9 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_bounce_trav(const Inner
     uint32_t stack[WIDE ? 1 : STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
     const uint32_t tid = threadIdx.x;
     BlockStack st{&s_stk[0][0] + (WIDE ? 0u : tid), stack};
-    __shared__ uint32_t s_wid[WIDE ? SW : 1][BLOCK];
-    __shared__ uint16_t s_wt[WIDE ? SW : 1][BLOCK];
-    uint2 wstack[WIDE ? STACK4B - SW : 1];       // entries [SW, STACK4B)
-    auto wpush = [&](uint32_t id, float t) {
-        if (sp < SW) {
-            s_wid[sp][tid] = id;
-            s_wt[sp][tid] = bf16_down(t);
-        } else {
-            wstack[sp - SW] = make_uint2(id, __float_as_uint(t));
-        }
-        ++sp;
-    };
-    // WIDE: the QNode at `node` (words q0..q3): its four entries, hit ones first by entry distance
-    // (k: entry distance, i: id; a missing child has INVALID and +inf)
-    auto qchildren = [&](v4f q0, v4f q1, v4f q2, v4f q3, float& k0, float& k1, float& k2, float& k3, uint32_t& i0,
-                         uint32_t& i1, uint32_t& i2, uint32_t& i3) {
-        // the four grandchildren: ids (a3.x, a3.y, b3.x, b3.y), entry distances t0..t3
-        uint4 a3, b3;
-        float t0, t1, t2, t3;
-        bool h0, h1, h2, h3;
-        const float kbb = key_t(key);
-        if (CERT || q0.w != 0.f) {   // quantized node: q0..q3 = QNode words 0..15 (CERT: the step checked)
-            // scl[1], scl[2] carry the node's margin codes in their (otherwise zero) mantissas (margin.h)
-            const uint32_t wy = __float_as_uint(q1.x), wz = __float_as_uint(q1.y);
-            const float ox = q0.x, oy = q0.y, oz = q0.z, sx = q0.w;
-            const float sy = __uint_as_float(wy & 0xFF800000u), sz = __uint_as_float(wz & 0xFF800000u);
-            const uint32_t lx = __float_as_uint(q1.z), ly = __float_as_uint(q1.w), lz = __float_as_uint(q2.x);
-            const uint32_t hx = __float_as_uint(q2.y), hy = __float_as_uint(q2.z), hz = __float_as_uint(q2.w);
-            a3 = make_uint4(__float_as_uint(q3.x), __float_as_uint(q3.y), 0u, 0u);
-            b3 = make_uint4(__float_as_uint(q3.z), __float_as_uint(q3.w), 0u, 0u);
-            // (CERT: a ray the slack test cannot take never steps -- it is flagged at its first step -- so
-            // every stepping ray takes this branch)
-            if (qfast || CERT) {
-                // CERT: the node's margin rho_n(best) (0 before the first bound) and its range
-                float rr = 0.f, tcn = 0.f;
-                MtNodeRho nr{0.f, 0.f};
-                if (CERT) {
-                    nr = mt_node_prep(nk, mt_code_val(wy));
-                    tcn = mt_code_val(wz);
-                    rr = kbb < __builtin_inff() ? mt_node_eval(nr, kbb) : 0.f;
-                }
-                const QAxis X = qaxis<CERT>(ox, sx, lx, hx, o.x, inv.x, rr),
-                            Y = qaxis<CERT>(oy, sy, ly, hy, o.y, inv.y, rr),
-                            Z = qaxis<CERT>(oz, sz, lz, hz, o.z, inv.z, rr);
-                if (CERT) {
-                    const f3 ai = mk(fabsf(inv.x), fabsf(inv.y), fabsf(inv.z));
-                    h0 = qbox_fast_cert(X, Y, Z, 0, kbb, nk, nr, ai, tcn, t0);
-                    h1 = qbox_fast_cert(X, Y, Z, 1, kbb, nk, nr, ai, tcn, t1);
-                    h2 = qbox_fast_cert(X, Y, Z, 2, kbb, nk, nr, ai, tcn, t2);
-                    h3 = qbox_fast_cert(X, Y, Z, 3, kbb, nk, nr, ai, tcn, t3);
-                } else {
-                    h0 = qbox_fast(X, Y, Z, 0, true, kbb, t0);
-                    h1 = qbox_fast(X, Y, Z, 1, true, kbb, t1);
-                    h2 = qbox_fast(X, Y, Z, 2, true, kbb, t2);
-                    h3 = qbox_fast(X, Y, Z, 3, true, kbb, t3);
-                }
-            } else {
-    #define RTBVH_QBOX(c, t)                                                                                      \
-ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, lz, c), qdecode(ox, sx, hx, c), \
-        qdecode(oy, sy, hy, c), qdecode(oz, sz, hz, c), true, kbb, t)
-                h0 = RTBVH_QBOX(0, t0);
-                h1 = RTBVH_QBOX(1, t1);
-                h2 = RTBVH_QBOX(2, t2);
-                h3 = RTBVH_QBOX(3, t3);
-    #undef RTBVH_QBOX
-            }
-            h1 = h1 & (a3.y != INVALID);
-            h3 = h3 & (b3.y != INVALID);
-        } else {
-            // a node without a finite grid: its exact record pair (node = its slot; the
-            // pair of its children's records is at 2 * own, own = word 14 of its record; the
-            // build writes the pseudo-records of such a node's leaf children whatever the flags).
-            // (Not widened by the margin: a certified walk ends the ray there, flagged -- below)
-            const uint32_t own = __float_as_uint(reinterpret_cast<const v4f*>(inner + node)[3].z);
-            const v4f* pr = reinterpret_cast<const v4f*>(inner + 2 * (size_t)own);
-            q0 = pr[0]; q1 = pr[1]; q2 = pr[2]; q3 = pr[3];
-            const v4f q4 = pr[4], q5 = pr[5], q6 = pr[6], q7 = pr[7];
-            a3 = make_uint4(__float_as_uint(q3.x), __float_as_uint(q3.y), 0u, 0u);
-            b3 = make_uint4(__float_as_uint(q7.x), __float_as_uint(q7.y), 0u, 0u);
-            // grandchild ids -> slots (2 * parent + side; parent = word 14)
-            const uint32_t ol = __float_as_uint(q3.z), orr = __float_as_uint(q7.z);
-            if (!(a3.x & LEAF_BIT)) a3.x = 2 * ol;
-            if (a3.y != INVALID && !(a3.y & LEAF_BIT)) a3.y = 2 * ol + 1;
-            if (!(b3.x & LEAF_BIT)) b3.x = 2 * orr;
-            if (b3.y != INVALID && !(b3.y & LEAF_BIT)) b3.y = 2 * orr + 1;
-            h0 = ray_box_xy(o, inv, q0.xy, q0.zw, q2.x, q2.y, true, kbb, t0);
-            h1 = ray_box_xy(o, inv, q1.xy, q1.zw, q2.z, q2.w, true, kbb, t1) & (a3.y != INVALID);
-            h2 = ray_box_xy(o, inv, q4.xy, q4.zw, q6.x, q6.y, true, kbb, t2);
-            h3 = ray_box_xy(o, inv, q5.xy, q5.zw, q6.z, q6.w, true, kbb, t3) & (b3.y != INVALID);
-        }
-        const float INF = __builtin_inff();
-        k0 = h0 ? t0 : INF; k1 = h1 ? t1 : INF; k2 = h2 ? t2 : INF; k3 = h3 ? t3 : INF;
-        i0 = h0 ? a3.x : INVALID; i1 = h1 ? a3.y : INVALID; i2 = h2 ? b3.x : INVALID; i3 = h3 ? b3.y : INVALID;
-        // 4-element sorting network on the entry distance (missing children last)
-        sort2(k0, i0, k1, i1);
-        sort2(k2, i2, k3, i3);
-        sort2(k0, i0, k2, i2);
-        sort2(k1, i1, k3, i3);
-        sort2(k1, i1, k2, i2);
-    };
+    // WIDE: the 4-wide walk's stack and node test (wpush, qchildren), and below its step
+#define RTBVH_WIDE_PART 1
+#include "wide_walk.inc"
     Refill rf;
     unsigned long long wsteps = 0, mixed = 0, active_lanes = 0;
     while (true) {
@@ -2134,81 +2042,11 @@ ray_box(o, inv, qdecode(ox, sx, lx, c), qdecode(oy, sy, ly, c), qdecode(oz, sz, 
         if (!has) continue;
         bool done = false;
         if (WIDE) {
-            // A step: the QNode of an internal `node`, then one leaf test -- the nearest child when it
-            // is a leaf (the next child is visited), or the leaf the step began at -- so a leaf found
-            // by the node test costs no step of its own, and the leaf test is one block of code.
-            uint32_t L = INVALID;
-            if (GUARD && --guard == 0) {
-                c.overflow++;
-                done = true;
-                if (CERT) flg = true;
-            } else {
-                if (node & LEAF_BIT) {
-                    L = node;
-                    node = INVALID;
-                } else {
-                    const v4f* rr = reinterpret_cast<const v4f*>(qn + node);
-                    v4f q0 = rr[0], q1 = rr[1], q2 = rr[2], q3 = rr[3];
-                    pin(q0); pin(q1); pin(q2); pin(q3);
-                    if (COUNT) c.internal++;
-                    float k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f;
-                    uint32_t i0 = INVALID, i1 = INVALID, i2 = INVALID, i3 = INVALID;
-                    // CERT: a node without a finite grid (its corners past 2^100: the margin does not cover
-                    // its exact boxes) ends the walk, the ray flagged for the reference-order re-trace
-                    if (CERT && q0.w == 0.f) {
-                        flg = true;
-                        done = true;
-                    } else {
-                        qchildren(q0, q1, q2, q3, k0, k1, k2, k3, i0, i1, i2, i3);
-                    }
 #ifdef RTBVH_DEBUG_PIXEL   // (scripts/debug_walk.py: one ray's walk, step by step, from the COUNT kernel)
-                    if (COUNT && qin[r].idx == (uint32_t)RTBVH_DEBUG_PIXEL)
-                        printf("DBG %d q %u sp %d kb %.6g key %.6g | %.6g %x %.6g %x %.6g %x %.6g %x\n", (int)CERT, node,
-                               sp, key_t(key), key_t(key), k0, i0, k1, i1, k2, i2, k3, i3);
+            const bool wide_dbg = COUNT && qin[r].idx == (uint32_t)RTBVH_DEBUG_PIXEL;
 #endif
-                    const bool lf0 = i0 != INVALID && (i0 & LEAF_BIT);
-                    L = lf0 ? i0 : INVALID;
-                    node = lf0 ? i1 : i0;   // INVALID when no child is left -> pop below
-                    if (sp + 3 > limit) {
-                        c.overflow++;
-                        done = true;
-                        if (CERT) flg = true;
-                    } else {   // push the others farthest first
-                        if (i3 != INVALID) wpush(i3, k3);
-                        if (i2 != INVALID) wpush(i2, k2);
-                        if (!lf0 && i1 != INVALID) wpush(i1, k1);
-                    }
-                }
-#ifdef RTBVH_DEBUG_PIXEL
-                if (COUNT && L != INVALID && qin[r].idx == (uint32_t)RTBVH_DEBUG_PIXEL)
-                    printf("DBG %d leaf %x sp %d kb %.6g key %.6g\n", (int)CERT, L, sp, key_t(key), key_t(key));
-#endif
-                if (L != INVALID) {   // branch-free test (the same accept predicate), u64 key minimum
-                    const uint32_t j = L & ~LEAF_BIT;
-                    const v4f* lr = reinterpret_cast<const v4f*>(leaf + 4 * (size_t)j);
-                    v4f la = lr[0], lb = lr[1], lc = lr[2];
-                    pin(la); pin(lb); pin(lc);
-                    if (COUNT) c.leaf++;
-                    const float tw = ray_triangle_flat(o, d, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y),
-                                                       mk(lb.z, lb.w, lc.x), true);
-                    const uint64_t k = tw == -1.f ? ~0ull : (uint64_t)__float_as_uint(tw) << 32 | j;
-                    btri = k < key ? __float_as_uint(lc.y) & ~LEAF_BIT : btri;
-                    key = k < key ? k : key;
-                }
-                if (!done && node == INVALID) {   // pop, dropping entries that cannot improve
-                    while (sp > 0) {
-                        --sp;
-                        uint2 e;
-                        if (sp < SW) e = make_uint2(s_wid[sp][tid], __float_as_uint(bf16_up(s_wt[sp][tid])));
-                        else e = wstack[sp - SW];
-                        if (__uint_as_float(e.y) <= key_t(key)) {
-                            node = e.x;
-                            break;
-                        }
-                    }
-                    done = node == INVALID;
-                }
-            }
+#define RTBVH_WIDE_PART 2
+#include "wide_walk.inc"
         } else {
             // binary walks: one fetch for every active lane, leaf or internal, before the branch: a
             // wave holding both kinds would otherwise wait for two dependent round trips (leaf records
@@ -2473,7 +2311,10 @@ __device__ __forceinline__ void ray_triangle_uv(f3 o, f3 d, f3 p0, f3 e1, f3 e2,
 }
 template <bool ANY, bool COUNT, bool NB>
 __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query(QueryArgs a) {
-    const uint32_t n = a.n, T = a.T;
+    // (a certified query's re-trace: the list's length is on the device, the grid sized for a.n rays; the workgroups
+    // past the list leave at once -- any workgroup claims from every segment)
+    const uint32_t n = a.n_dev ? *a.n_dev : a.n, T = a.T;
+    if (a.n_dev && blockIdx.x * BLOCK >= n) return;
     const uint32_t lane = lane_id();
     const int limit = a.stack_limit;
     const float4* __restrict__ leaf = a.leaf;
@@ -2570,6 +2411,134 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query(QueryArgs a) {
     }
 }
 
+// ---- certified ray queries (RTBVH_QUERY_CERTIFIED): the 4-wide certified walk for caller rays ---------------
+// k_bounce_trav's certified walk (wide_walk.inc, CERT: the QNodes, boxes grown by the margin, the u64 (t, leaf)
+// key) with k_query's rays, claims and hits.  DESIGN.md 5b has the argument; in short:
+//  - a ray the margin does not cover -- !(qnode_fast_ray && d.d <= MT_DD), NaN inputs included -- never steps: it is
+//    listed for the re-trace at its claim;
+//  - t_max is the walk's initial bound: the key starts at (t_max, 0xFFFFFFFF), so a triangle at t <= t_max wins
+//    (its leaf index is below the sentinel), one beyond never does, and a final key with the sentinel is a miss;
+//    +inf gives NO_HIT, the bounce walk's start.  !(t_max > EPSILON) (NaN included) accepts no triangle: a miss
+//    without a walk;
+//  - ANY: the walk ends at the first accepted triangle;
+//  - the certificate: the winning triangle's own leaf box (leaf_clip_box, leaf_certified's source) passes the
+//    reference's box test -- with the bound t for a closest hit, the any-hit rule with t_max for ANY;
+//  - a ray without a certificate or flagged by the step (a node without a grid, a stack overflow) is listed too.
+// A wave appends its rays to the list with one atomic, at the top of its next iteration (an all-uncovered batch
+// would otherwise make one same-address atomic a ray).
+// The list (a.redo, its length a.redo_n) is re-traced by k_query over it as its perm (launch_query_certified): the
+// plain mode's answer by construction.  The step's own overflow count is dropped: the re-trace reports the ray's.
+// No walk-length guard (a clz64 tree) and no stack limit: api.hip takes k_query for every ray otherwise.
+// COUNT: the walk counts a.walk[0..2] (certified, redone, uncovered), and a.counts from the rays answered here.
+template <bool ANY, bool COUNT>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_query_wide(QueryArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id(), tid = threadIdx.x;
+    const float4* __restrict__ leaf = a.leaf;
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nhits = 0, ncert = 0, nunc = 0, nlisted = 0;   // per lane; nlisted: the wave's listed rays
+    bool has = false, flg = false;
+    uint32_t r = 0, node = INVALID, guard = 0, btri = 0;
+    int sp = 0;
+    uint64_t key = NO_HIT;
+    float tmax = 0.f;
+    f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+    const MtNodeK nk = mt_node_consts();
+    // the walk's names (wide_walk.inc): the certified walk, no guard (a clz64 tree), the whole stack, covered rays
+    constexpr bool WIDE = true, CERT = true, GUARD = false;
+    const Inner* __restrict__ inner = a.inner;
+    const QNode* __restrict__ qn = a.qnode;
+    const int limit = STACK4B;
+    const bool qfast = true;
+#define RTBVH_WIDE_PART 1
+#include "wide_walk.inc"
+    const float4 miss = make_float4(-1.f, 0.f, 0.f, __uint_as_float(INVALID));
+    Refill rf;
+    bool pend = false;   // this lane's ray r (ended, or claimed uncovered: the lane holds none) goes to the re-trace list
+    while (true) {
+        {   // (all lanes converged) the rays the last iteration found for the list: one atomic a wave
+            const uint32_t slot = wave_append(pend, a.redo_n);
+            if (pend) a.redo[slot] = r;
+            if (COUNT) nlisted += (uint32_t)__popcll(__ballot(pend));   // (wave-uniform)
+            pend = false;
+        }
+        refill_claim(rf, a.next, n, has, [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
+            r = a.perm ? a.perm[p] : p;
+            const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
+            o = mk(q0.x, q0.y, q0.z);
+            tmax = q0.w;
+            d = mk(q1.x, q1.y, q1.z);
+            inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            if (!(qnode_fast_ray(o, inv) && dot(d, d) <= MT_DD)) {   // not covered by the margin (NaN: here too)
+                pend = true;
+                if (COUNT) nunc++;
+            } else if (!(tmax > EPSILON)) {   // no triangle is accepted at t <= t_max (every accepted t > EPSILON)
+                a.hits[r] = miss;
+                if (COUNT) ncert++;
+            } else {
+                has = true;
+                flg = false;
+                node = root_slot(T);
+                sp = 0;
+                key = (uint64_t)__float_as_uint(tmax) << 32 | 0xFFFFFFFFull;
+            }
+        });
+        if (__ballot(has || pend) == 0 && rf.drained) break;   // (a pending ray is listed at the top)
+        if (!has) continue;
+        bool done = false;
+        {
+#ifdef RTBVH_DEBUG_PIXEL
+            const bool wide_dbg = false;
+#endif
+#define RTBVH_WIDE_PART 2
+#include "wide_walk.inc"
+        }
+        const bool hit = (uint32_t)key != 0xFFFFFFFFu;
+        if (ANY && hit) done = true;
+        if (done) {
+            bool redo = flg;
+            float4 h = miss;
+            if (!redo && hit) {
+                const float t = key_t(key);
+                f3 lo, hi;
+                leaf_clip_box(a.tclip, btri, lo, hi);
+                float tm;
+                const bool ok = ANY ? ray_box(o, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, false, 0.f, tm) && !(tm > tmax)
+                                    : ray_box(o, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, true, t, tm);
+                if (ok) {   // (u, v) recomputed from the winning leaf's record, as k_query does
+                    const float4* lr = leaf + 4 * (size_t)(uint32_t)key;
+                    const float4 la = lr[0], lb = lr[1], lc = lr[2];
+                    float u, v;
+                    ray_triangle_uv(o, d, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y), mk(lb.z, lb.w, lc.x), u, v);
+                    h = make_float4(t, u, v, __uint_as_float(btri));
+                } else {
+                    redo = true;
+                }
+            }
+            if (redo) {
+                pend = true;
+            } else {
+                a.hits[r] = h;
+                if (COUNT) {
+                    ncert++;
+                    nhits += hit;
+                }
+            }
+            has = false;
+        }
+    }
+    if (COUNT) {
+        unsigned long long v[5] = {ncert, nhits, c.internal, c.leaf, nunc};
+        wave_sum(v);
+        if (lane == 0) {   // (redone: the listed rays that were not uncovered)
+            for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            atomicAdd(&a.walk[0], v[0]);
+            atomicAdd(&a.walk[1], (unsigned long long)nlisted - v[4]);
+            atomicAdd(&a.walk[2], v[4]);
+        }
+    }
+}
+
 // the coherence key of caller rays: k_bounce_keys' (octant, origin Morton) over the root box
 __global__ __launch_bounds__(BLOCK) void k_query_keys(const float4* __restrict__ rays, uint32_t n,
                                                       const float* __restrict__ box, uint32_t* __restrict__ keys,
@@ -2593,6 +2562,21 @@ void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s) {
     with_bools([&](auto ANY, auto COUNT, auto NB) {
         hipLaunchKernelGGL((k_query<ANY, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
     }, any, count, a.nb);
+}
+
+void launch_query_certified(const QueryArgs& a, bool any, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto ANY, auto COUNT) {
+        hipLaunchKernelGGL((k_query_wide<ANY, COUNT>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, any, count);
+    // the listed rays in the reference order: the plain kernel with the list as its walk order, the list's length
+    // read on the device, its own work counters
+    QueryArgs b = a;
+    b.perm = a.redo;
+    b.n_dev = a.redo_n;
+    b.next = a.next2;
+    launch_query(b, any, count, s);
 }
 
 void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,

@@ -196,7 +196,7 @@ class Context:
     # -- ray queries --
     def query(self, rays, mode: int = 0, out=None, stream=None):
         """rtbvh_query_async / rtbvh_query_host: the closest hit (or with QUERY_ANY any hit) of each ray, in the
-        space the BVH was built in (include/rtbvh.h).
+        space the BVH was built in (include/rtbvh.h).  QUERY_CERTIFIED: the same hits through the certified 4-wide walk.
 
         An (N, 8) float32 contiguous CUDA tensor on the context's device (make_rays) goes to the device entry with
         no host copy, enqueued on `stream` (a torch stream or a hipStream_t handle; default: the current torch
@@ -239,6 +239,14 @@ class Context:
         out = np.zeros(4, np.uint64)
         self._check(_L.lib().rtbvh_query_counts(self._h, _L.ptr(out)))
         return dict(zip(("rays", "hits", "internal_visits", "leaf_visits"), (int(v) for v in out)))
+
+    def query_walk_counts(self) -> dict:
+        """rtbvh_query_walk_counts: how the rays of the last QUERY_COUNT query were answered -- certified by the
+        4-wide walk (QUERY_CERTIFIED), redone or uncovered (re-traced in the reference order), or fallback (a query
+        that took the plain kernel for every ray).  The four sum to the query's rays."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_query_walk_counts(self._h, _L.ptr(out)))
+        return dict(zip(("certified", "redone", "uncovered", "fallback"), (int(v) for v in out)))
 
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
