@@ -463,6 +463,13 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* ctx, rtbvh_stats* out);
 rtbvh_status rtbvh_reset_stats(rtbvh_ctx* ctx);
 /* Replace the RTBVH_FLAG_* bits of the context (takes effect for the next build/trace). */
 rtbvh_status rtbvh_set_flags(rtbvh_ctx* ctx, uint32_t flags);
+/* The binned primary pass lists every leaf in the screen-tile bins it covers.  The bins depend on the built tree
+ * and the frame shape only (size, rank, band deal), so a context fills a bin set once and every later binned trace
+ * of the same tree and shape, on any stream, reads it (environment RTBVH_BINS_REUSE=0 at rtbvh_create: a fill per
+ * trace).  rtbvh_bin_builds: the fills enqueued since rtbvh_create; rtbvh_bin_sets: the bin sets the context
+ * holds in device memory.  Both 0 for a NULL context. */
+uint64_t rtbvh_bin_builds(rtbvh_ctx* ctx);
+uint32_t rtbvh_bin_sets(rtbvh_ctx* ctx);
 
 /* ---- primitives (exposed for tests and callers with their own buffers) ---- */
 /* Stable LSD radix sort of (key, value) pairs, 8-bit digits over bits [0, key_bits).

@@ -36,7 +36,7 @@ EXPORTS = [
     "rtbvh_deal_bands", "rtbvh_deal_rows", "rtbvh_set_band_deal",
     "rtbvh_synchronize", "rtbvh_read_framebuffer", "rtbvh_read_intensity", "rtbvh_framebuffer_device",
     "rtbvh_read_bvh", "rtbvh_read_wide", "rtbvh_read_qnodes", "rtbvh_read_morton", "rtbvh_read_sorted", "rtbvh_read_rays", "rtbvh_get_stats",
-    "rtbvh_reset_stats", "rtbvh_set_flags",
+    "rtbvh_reset_stats", "rtbvh_set_flags", "rtbvh_bin_builds", "rtbvh_bin_sets",
     "rtbvh_sort_pairs_async", "rtbvh_sort_pairs_host", "rtbvh_build_from_codes", "rtbvh_scene_load_obj",
     "rtbvh_scene_synthetic", "rtbvh_scene_free", "rtbvh_scene_num_vertices", "rtbvh_scene_num_indices",
     "rtbvh_scene_num_materials", "rtbvh_scene_num_textures", "rtbvh_scene_vertices", "rtbvh_scene_indices",
@@ -174,6 +174,8 @@ def lib() -> ctypes.CDLL:
         "rtbvh_get_stats": (i32, [vp, ctypes.POINTER(Stats)]),
         "rtbvh_reset_stats": (i32, [vp]),
         "rtbvh_set_flags": (i32, [vp, u32]),
+        "rtbvh_bin_builds": (u64, [vp]),
+        "rtbvh_bin_sets": (u32, [vp]),
         "rtbvh_sort_pairs_async": (i32, [vp, vp, vp, vp, vp, u32, u32]),
         "rtbvh_sort_pairs_host": (i32, [vp, vp, vp, vp, vp, u32, u32]),
         "rtbvh_build_from_codes": (i32, [vp, vp, vp, u32, vp]),

@@ -159,17 +159,41 @@ struct rtbvh_ctx {
     size_t cap_split = 0;                     // rays per pipeline queue
     Event ev_fork, ev_join[MAXSPLIT];
     uint32_t nsplit = 1;                      // pipelines of the last trace
-    // RTBVH_FLAG_BINNED_PRIMARY, per buffer set (chain / frames-in-flight slot): leaf footprints,
-    // tile counts / offsets, fill cursors and the bins (trace.hip k_pb_bin)
+    // RTBVH_FLAG_BINNED_PRIMARY: a bin set -- tile counts / offsets, fill cursors, the bins and the rank's leaf
+    // list (trace.hip k_pb_bin) -- is a product of the built tree and the frame shape, like the leaf footprints it
+    // is made from: the two bin passes and the scan read nothing else (PbKey), and every kernel behind them only
+    // reads the set.  So a set records the key it was filled for, and a later binned trace with the same key, on any
+    // stream, uses it as it is (find_bins) instead of zeroing and filling its own: one fill per build and frame
+    // shape, and one set in memory for all the frames in flight.  A trace that finds none fills the set of its own
+    // buffer slot (enqueue_walks).  RTBVH_BINS_REUSE=0: every trace fills its slot's set (A/B).
+    struct PbKey {
+        uint64_t build = 0;           // bins_epoch of the fill: the tree whose footprints and depth range it read
+        uint32_t W = 0, H = 0, rows = 0, rank = 0, nranks = 0, T = 0, ntx = 0, nty = 0;
+        uint32_t share = 0;           // the band deal (root_share; 16 with one rank: no deal) ...
+        const uint32_t* deal = nullptr;   // ... and its device table (null: round-robin, computed in the kernel)
+        bool operator==(const PbKey& o) const {
+            return build == o.build && W == o.W && H == o.H && rows == o.rows && rank == o.rank &&
+                   nranks == o.nranks && T == o.T && ntx == o.ntx && nty == o.nty && share == o.share &&
+                   deal == o.deal;
+        }
+    };
     struct PbBufs {
         DevBuf<uint32_t> off, cur, sums;
         DevBuf<uint4> bins;
-        DevBuf<unsigned long long> keys;
-        uint32_t cap_T = 0, cap_tiles = 0, cap_bins = 0;
-        size_t cap_px = 0;
+        uint32_t cap_T = 0, cap_tiles = 0, cap_bins = 0;   // (cap_bins is what the fill clipped at: the readers' `cap`)
         DevBuf<uint32_t> list;      // N > 1: the rank's leaves (TraceArgs::pb_list)
         size_t cap_list = 0;
+        PbKey key;                  // what the set holds, when `valid`
+        bool valid = false;
+        Event filled;               // recorded behind the fill pass: a reader on another stream waits for it
+        uint32_t readers = 0;       // buffer slots whose traces have read the set since its fill (bit k: slot k)
     } pb[MAXSPLIT];
+    // the (t, leaf) keys of an RTBVH_PB_FUSE=0 build's separate shading launch: a result, so per buffer slot
+    DevBuf<unsigned long long> d_pbkeys[MAXSPLIT];
+    size_t cap_pbkeys[MAXSPLIT] = {};
+    uint64_t bins_epoch = 1;        // bumped whenever the leaf footprints are (or are about to be) rewritten
+    uint64_t bin_builds = 0;        // count passes launched (rtbvh_bin_builds)
+    bool knob_bins_reuse = true;    // RTBVH_BINS_REUSE
     DevBuf<unsigned long long> d_counters;    // [64]: see rtbvh_get_stats
     bool traced = false;
     bool frame_here = false;                 // d_color holds the last trace's whole frame
@@ -285,6 +309,7 @@ void drop_graph(rtbvh_ctx* c) {
 // No tree: the buffers of the built one are about to be rewritten (set_scene, build_from_codes)
 void reset_tree(rtbvh_ctx* c) {
     c->tree = Tree{};
+    c->bins_epoch++;   // (no bin set is of the next tree)
     c->tail_pending = c->leaf_pending = false;
 }
 
@@ -429,15 +454,12 @@ rtbvh_status ensure_split_capacity(rtbvh_ctx* c, uint32_t nsplit, size_t rays) {
 // BINS_PER_LEAF entries per leaf (C5: 1.37 tiles per leaf); a tile whose bins would pass the end is
 // traced by the 4-wide packet walk instead (trace.hip pb_gate), so the capacity is a speed knob only.
 constexpr uint32_t BINS_PER_LEAF = 3;
-rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t tiles, size_t pixels) {
+rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t tiles) {
     rtbvh_ctx::PbBufs& p = c->pb[b];
     const uint32_t bins = BINS_PER_LEAF * T + 16 * tiles;
-    if (T <= p.cap_T && tiles <= p.cap_tiles && bins <= p.cap_bins && pixels <= p.cap_px && p.off) return RTBVH_OK;
+    if (T <= p.cap_T && tiles <= p.cap_tiles && bins <= p.cap_bins && p.off) return RTBVH_OK;
     drop_graph(c);
-    if (pixels > p.cap_px) {
-        HIPC(c, p.keys.alloc(pixels));
-        p.cap_px = pixels;
-    }
+    p.valid = false;   // (its buffers go; the free waits for the device, so for every reader)
     const uint32_t nT = std::max(T, p.cap_T), nt = std::max(tiles, p.cap_tiles);
     const uint32_t nb = std::max(BINS_PER_LEAF * nT + 16 * nt, p.cap_bins);
     HIPC(c, p.off.alloc((size_t)nt * PB_NZ + 1));
@@ -448,6 +470,20 @@ rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t t
     p.cap_tiles = nt;
     p.cap_bins = nb;
     return RTBVH_OK;
+}
+
+// The bin set filled for `key`, if the context has one (rtbvh_ctx::PbBufs), or -1.  The key holds everything the bin
+// passes and the scan read: the tree (bins_epoch: the leaf footprints and the root box's depth range, both written
+// by the build alone), T, the frame shape, the rank's rows and the band deal.  Not the camera: the passes read it only
+// through the footprints, which a camera upload without a build leaves as they are (the frame then still shows the
+// tree of the last build, whose clip-space triangles the walks read).  Not the walk flags, the counters or the
+// overflow word: no bin kernel reads them.  Never inside a capture: a captured frame holds its own bin passes, so
+// that its replay depends on no host state.
+int find_bins(const rtbvh_ctx* c, const rtbvh_ctx::PbKey& key) {
+    if (!c->knob_bins_reuse || c->capturing) return -1;
+    for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++)
+        if (c->pb[k].valid && c->pb[k].off && c->pb[k].key == key) return (int)k;
+    return -1;
 }
 
 BuildArgs build_args(rtbvh_ctx* c) {
@@ -897,15 +933,50 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         HIPC(c, c->d_redo[slot].alloc(P));
         c->cap_redo[slot] = P;
     }
-    // the binned pass's buffers (one chain: buffer set `slot`)
+    // the binned pass's bin set (one chain): a set already filled for this tree and frame shape, or the buffer
+    // slot's own, filled by this trace (fill_bins)
     const uint32_t ntx = pb_tiles_x(W), nty = pb_tiles_y(rows);
-    if (pkind == PrimaryKind::BINNED) {
-        st = ensure_pb_capacity(c, slot, c->T, ntx * nty, (size_t)W * rows);
-        if (st) return st;
-        if (nranks > 1 && c->pb[slot].cap_list < pb_list_words(c->T)) {
+    uint32_t bset = slot;
+    bool fill_bins = false;
+    if (pkind == PrimaryKind::BINNED && rows > 0) {
+        if (pb_keys_used() && (size_t)W * rows > c->cap_pbkeys[slot]) {   // (the slot's own, whichever the set)
             drop_graph(c);
-            HIPC(c, c->pb[slot].list.alloc(pb_list_words(c->T)));
-            c->pb[slot].cap_list = pb_list_words(c->T);
+            HIPC(c, c->d_pbkeys[slot].alloc((size_t)W * rows));
+            c->cap_pbkeys[slot] = (size_t)W * rows;
+        }
+        const rtbvh_ctx::PbKey key{c->bins_epoch, W, H, rows, rank, nranks, c->T, ntx, nty,
+                                   nranks > 1 ? c->root_share : 16u, deal ? deal->d.h : nullptr};
+        // (a trace that runs the build's crossing nodes in its count pass, or its pass beside them, is the first
+        // of its tree: it finds none)
+        const int found = fuse_tail || leaf_pending ? -1 : find_bins(c, key);
+        if (found >= 0) {
+            bset = (uint32_t)found;
+            rtbvh_ctx::PbBufs& p = c->pb[bset];
+            if (bset != slot) HIPC(c, hipStreamWaitEvent(s, p.filled, 0));   // (its own slot's: stream order)
+            p.readers |= 1u << slot;
+        } else {
+            fill_bins = true;
+            st = ensure_pb_capacity(c, slot, c->T, ntx * nty);
+            if (st) return st;
+            rtbvh_ctx::PbBufs& p = c->pb[slot];
+            if (nranks > 1 && p.cap_list < pb_list_words(c->T)) {
+                drop_graph(c);
+                HIPC(c, p.list.alloc(pb_list_words(c->T)));
+                p.cap_list = pb_list_words(c->T);
+            }
+            // the traces of other buffer slots that read what the set held (the same tree at another frame
+            // shape, rank or deal -- a new tree's build has waited for them all) end before this one overwrites
+            // it: stream-side, on their slot events, or the context stream's work so far for slot 0's.  Not
+            // inside a capture (no frame in flight outlives the wait_slots before every replay)
+            for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT && !c->capturing; k++) {
+                if (k == slot || !(p.readers & 1u << k)) continue;
+                if (k == 0) st = order_after_context(c, s);
+                else if (c->ev_slot[k]) HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
+                if (st) return st;
+            }
+            p.readers = 1u << slot;
+            p.valid = false;   // (until the fill is enqueued, below)
+            p.key = key;
         }
     }
     // the trace's counters, queue counts, bounce work counters and bin counts: one launch
@@ -918,14 +989,13 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         z.ptr[2] = c->d_next + (size_t)NEXT_WORDS * slot;
         z.words[2] = (size_t)NEXT_WORDS * nsplit;
     }
-    if (pkind == PrimaryKind::BINNED) {
+    if (fill_bins) {
         z.ptr[3] = c->pb[slot].off;
         z.words[3] = (size_t)ntx * nty * PB_NZ + 1;
         if (nranks > 1) {   // the list counters
             z.ptr[4] = c->pb[slot].list;
             z.words[4] = (size_t)PB_LISTS * PB_LIST_STRIDE;
         }
-
     }
     // rtbvh_compute_bvh: the binned pass (and the zeroing before it) on the side stream, concurrent
     // with the build's crossing nodes (launch_refit_tail)
@@ -944,7 +1014,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         TraceArgs ag = a;
         ag.band0 = g;
         ag.bstep = nsplit;
-        ag.pb_list = pkind == PrimaryKind::BINNED && nranks > 1 ? c->pb[g + slot].list : nullptr;
+        ag.pb_list = fill_bins && nranks > 1 ? c->pb[slot].list : nullptr;   // (the bin passes': one chain)
         const uint32_t b = g + slot;   // buffer set: chain g of the context stream's trace, or the slot
         RayQ* q[2] = {b ? c->d_qs[b][0] : c->d_q[0], b ? c->d_qs[b][1] : c->d_q[1]};
         float2* hit = b ? c->d_hits[b] : c->d_hit;
@@ -952,8 +1022,8 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         uint32_t* nx = c->d_next + (size_t)NEXT_WORDS * b;
         const bool tg = timing && g == 0;   // stage events: chain 0's kernels
         if (pkind == PrimaryKind::BINNED) {
-            const rtbvh_ctx::PbBufs& pbb = c->pb[b];
-            const PrimBins pb{pbb.off, pbb.cur, pbb.bins, pbb.keys, pbb.sums, pbb.cap_bins, ntx, nty};
+            rtbvh_ctx::PbBufs& pbb = c->pb[bset];
+            const PrimBins pb{pbb.off, pbb.cur, pbb.bins, c->d_pbkeys[b], pbb.sums, pbb.cap_bins, ntx, nty};
             if (rows) {
                 const BuildArgs ba = build_args(c);
                 const Redo rd{c->d_redo[b], &qc[16]};
@@ -961,8 +1031,19 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
                 // with frames in flight 256 is faster, round 5 r05_jj). Round 6 (r06_stl): the N = 8 rank's frame
                 // 1.13-1.15 -> 1.11 ms; N = 4 (2.1M pixels) the same, N = 2 (4.1M) +0.05 ms: below 1.5M pixels only
                 const bool small_tiles = !inflight && !c->knob_no_small_tiles && (size_t)W * rows < (3u << 19);
-                launch_pb_pass(ag, pb, rows, q[0], &qc[0], count, bounces > 0, true, overlap ? sp : sg,
-                               fuse_tail ? &ba : nullptr, cert ? &rd : nullptr, small_tiles);
+                if (fill_bins) {
+                    launch_pb_bins(ag, pb, rows, true, overlap ? sp : sg, fuse_tail ? &ba : nullptr);
+                    c->bin_builds++;
+                    // the set is this key's from here on, for every later trace (they wait for `filled`); a
+                    // captured fill is the graph's own, rewritten by every replay
+                    if (c->knob_bins_reuse && !c->capturing) {
+                        if (!pbb.filled) HIPC(c, hipEventCreateWithFlags(pbb.filled.out(), hipEventDisableTiming));
+                        HIPC(c, hipEventRecord(pbb.filled, overlap ? sp : sg));
+                        pbb.valid = true;
+                    }
+                }
+                launch_pb_raster(ag, pb, rows, q[0], &qc[0], count, bounces > 0, overlap ? sp : sg,
+                                 cert ? &rd : nullptr, small_tiles);
                 if (fuse_tail) tail.pending = false;
                 if (overlap) {
                     HIPC(c, hipEventRecord(c->ev_prim, sp));
@@ -1186,6 +1267,7 @@ rtbvh_status rtbvh_create(const rtbvh_config* cfg, rtbvh_ctx** out) {
     if (const char* e = getenv("RTBVH_KEEP_RECORDS")) c->knob_keep_records = atoi(e) != 0;
     if (const char* e = getenv("RTBVH_EARLY_SHADE")) c->knob_no_early_shade = atoi(e) == 0;   // (A/B: 0 = off)
     if (const char* e = getenv("RTBVH_PB_SMALL_TILES")) c->knob_no_small_tiles = atoi(e) == 0;   // (A/B: 0 = off)
+    if (const char* e = getenv("RTBVH_BINS_REUSE")) c->knob_bins_reuse = atoi(e) != 0;   // (A/B: 0 = a fill per trace)
     *out = c;
     return RTBVH_OK;
 }
@@ -1307,6 +1389,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     if (!cst) cst = wait_queries(c, s);    // ... and so do the outstanding ray queries
     if (!cst) cst = sync_camera(c, s);
     if (cst) return cst;
+    c->bins_epoch++;   // new leaf footprints and depth range from here on: no bin set is of this tree
     const bool clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
     Event* ev = c->evb[c->n_builds % rtbvh_ctx::RING];
     if (timing) HIPC(c, hipEventRecord(ev[0], s));
@@ -1471,6 +1554,7 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
     // the host-side state of the captured frame: its tree (the replayed build rewrote it for this camera, so
     // whatever was derived since belongs to the old one) and its trace (one in between may have changed it)
     c->tree = c->graph_tree;
+    c->bins_epoch++;   // (the replayed build rewrote the footprints, the replayed trace the context stream's bin set)
     const rtbvh_ctx::TraceState& g = c->graph_state;
     c->W = g.W;
     c->H = g.H;
@@ -1933,6 +2017,14 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
     }
     out->redo_total = out->redo_rays[0] + out->redo_rays[1];
     return RTBVH_OK;
+}
+
+uint64_t rtbvh_bin_builds(rtbvh_ctx* c) { return c ? c->bin_builds : 0; }
+
+uint32_t rtbvh_bin_sets(rtbvh_ctx* c) {
+    uint32_t n = 0;
+    for (uint32_t k = 0; c && k < rtbvh_ctx::MAXSPLIT; k++) n += c->pb[k].bins ? 1u : 0u;
+    return n;
 }
 
 rtbvh_status rtbvh_set_flags(rtbvh_ctx* c, uint32_t flags) {

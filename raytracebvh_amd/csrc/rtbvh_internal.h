@@ -210,6 +210,16 @@ void launch_primary_binned(const TraceArgs& a, const PrimBins& pb, uint32_t rows
 void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
                     bool emit, bool zeroed, hipStream_t s, const BuildArgs* tail = nullptr, const Redo* redo = nullptr,
                     bool small_tiles = false);   // (512 threads a tile: a small pass one frame at a time)
+// ... and that pass in its two parts: the bins (count pass, scan, fill pass: they read the build's leaf footprints,
+// the root box's depth range, the frame shape and the band deal, and write pb.off / cur / sums / bins and the rank's
+// leaf list -- a product of (tree, frame shape) that api.hip keeps from trace to trace), and the kernels that only
+// read them (k_primary_binned, k_primary_redo)
+void launch_pb_bins(const TraceArgs& a, const PrimBins& pb, uint32_t rows, bool zeroed, hipStream_t s,
+                    const BuildArgs* tail = nullptr);
+void launch_pb_raster(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
+                      bool emit, hipStream_t s, const Redo* redo = nullptr, bool small_tiles = false);
+// PrimBins::keys is read and written (an RTBVH_PB_FUSE=0 build: the separate shading launch)
+bool pb_keys_used();
 // the count pass of launch_pb_pass with the climb of the build's crossing nodes in the same launch,
 // then their QNodes (build.hip: the build's launch_refit_tail, moved into the frame)
 void launch_pb_count_top(const BuildArgs& b, const TraceArgs& a, uint32_t* off, uint32_t* cur, uint4* bins, uint32_t cap,

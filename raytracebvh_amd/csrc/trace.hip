@@ -1211,8 +1211,11 @@ __device__ __forceinline__ void pb_shade_tile(const TraceArgs& a, uint32_t rows,
 #define RTBVH_PB_FUSE 1
 #endif
 #ifndef RTBVH_PB_WAVES
-#define RTBVH_PB_WAVES 8   // k_primary_binned's launch bounds: 8 waves per SIMD with 37 VGPRs spilled beat
-                                   // 6 (16 spilled) and 5 (none) -- primary pass 0.87-0.89 / 0.91-0.93 / 0.98 ms
+#define RTBVH_PB_WAVES 8   // k_primary_binned's launch bounds: 8 waves per SIMD (64 VGPRs, some spilled) beat 6
+                                   // and 5 -- round 5, primary pass 0.87-0.89 / 0.91-0.93 / 0.98 ms with 37 / 16 /
+                                   // no VGPRs spilled.  Since then, by the compiler's resource remarks at 8 waves:
+                                   // 5 spilled in the bench's instance (certified, no counts, no records, 256
+                                   // threads a tile), 10-16 in the instances with counts or records
 #endif
 // RB: threads per tile -- PB_RASTER_BLOCK, or PB_RASTER_BLOCK_SMALL for a small pass traced one frame at a time
 // (api.hip: a rank's ~1,000 tiles then all run at once, and more waves per tile shorten the longest tile)
@@ -2621,8 +2624,10 @@ void launch_zero(const ZeroList& z, hipStream_t s) {
     hipLaunchKernelGGL(k_zero, dim3((uint32_t)blocks, ZeroList::N), dim3(BLOCK), 0, s, z);
 }
 
-void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
-                    bool emit, bool zeroed, hipStream_t s, const BuildArgs* tail, const Redo* redo, bool small_tiles) {
+bool pb_keys_used() { return !RTBVH_PB_FUSE; }
+
+void launch_pb_bins(const TraceArgs& a, const PrimBins& pb, uint32_t rows, bool zeroed, hipStream_t s,
+                    const BuildArgs* tail) {
     if (rows == 0 || a.W == 0 || a.T == 0) return;
     const uint32_t keys = pb.ntx * pb.nty * PB_NZ;
     if (!zeroed) (void)hipMemsetAsync(pb.off, 0, ((size_t)keys + 1) * sizeof(uint32_t), s);
@@ -2634,6 +2639,11 @@ void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ*
     hipLaunchKernelGGL(k_pb_sums, dim3(sb), dim3(PB_SCAN), 0, s, pb.off, pb.sums, keys);
     hipLaunchKernelGGL(k_pb_scan, dim3(sb), dim3(PB_SCAN), 0, s, pb.off, pb.cur, pb.sums, keys);
     hipLaunchKernelGGL((k_pb_bin<true>), lg, dim3(BLOCK), 0, s, a, pb.off, pb.cur, pb.bins, pb.cap, pb.ntx);
+}
+
+void launch_pb_raster(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
+                      bool emit, hipStream_t s, const Redo* redo, bool small_tiles) {
+    if (rows == 0 || a.W == 0 || a.T == 0) return;
     const dim3 grid(pb.ntx, pb.nty);
     uint32_t* rl = redo ? redo->list : nullptr;
     uint32_t* rc = redo ? redo->count : nullptr;
@@ -2663,6 +2673,12 @@ void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ*
             hipLaunchKernelGGL((k_primary_redo<COUNT>), dim3(REDO_BLOCKS), dim3(BLOCK), 0, s, a, rl, rc, q, qcount, (int)emit);
         }, count);
     }
+}
+
+void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
+                    bool emit, bool zeroed, hipStream_t s, const BuildArgs* tail, const Redo* redo, bool small_tiles) {
+    launch_pb_bins(a, pb, rows, zeroed, s, tail);
+    launch_pb_raster(a, pb, rows, q, qcount, count, emit, s, redo, small_tiles);
 }
 
 void launch_pb_gate(const TraceArgs& a, const PrimBins& pb, RayQ* q, uint32_t* qcount, bool count, bool emit,

@@ -317,6 +317,14 @@ class Context:
     def set_flags(self, flags: int):
         self._check(_L.lib().rtbvh_set_flags(self._h, flags))
 
+    def bin_builds(self) -> int:
+        """rtbvh_bin_builds: fills of a bin set (the binned primary pass's count pass) enqueued since create."""
+        return int(_L.lib().rtbvh_bin_builds(self._h))
+
+    def bin_sets(self) -> int:
+        """rtbvh_bin_sets: the bin sets the context holds in device memory."""
+        return int(_L.lib().rtbvh_bin_sets(self._h))
+
     # -- primitives --
     def sort_pairs(self, keys: np.ndarray, vals: np.ndarray, key_bits: int = 32):
         keys = np.ascontiguousarray(keys, np.uint32)
