@@ -329,6 +329,47 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* ctx, uint32_t width, uint32_t height, 
                                uint32_t nranks, void* comm);
 rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
 
+/* ---- animated geometry: vertex updates and the topology-keeping refit ---------------------------
+ * (No reference equivalent: the reference uploads its mesh once, ObjLoader::UploadData, and rebuilds the
+ * BVH over it every frame, Graphics.cpp:56.)
+ *
+ * New positions (and normals) for vertices the scene already has.  Indices, materials, texcoords and
+ * textures stay, nothing is reallocated, nothing waits on the host, and a captured frame
+ * (RTBVH_FLAG_GRAPH) stays valid: rtbvh_update_vertices_async followed by rtbvh_compute_bvh replays it.
+ * In RTBVH_MORTON_CPUTESTS mode the object-space mesh box is recomputed on the device in stream order.
+ *
+ * count vertices starting at `first`: positions (3 floats each, pos_stride floats apart, >= 3) and,
+ * if dev_normals != NULL, normals (nrm_stride floats apart, >= 3), from device memory of the
+ * context's device, enqueued on `stream` (NULL = the context stream).  A packed (V, 3) array has stride
+ * 3, a float4 array 4, an rtbvh_vertex array 8 (positions at its base, normals 3 floats in).
+ * Ordering: the update waits for the frames in flight and for the work already on the context stream;
+ * the next build or refit waits for the update.  The arrays must stay as they are until the update has
+ * run on `stream`.
+ * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
+ * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_* and
+ * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
+ * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
+rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
+                                         const float* dev_normals, uint32_t nrm_stride,
+                                         uint32_t first, uint32_t count, void* stream);
+/* host arrays, synchronous (stages and runs the same kernel) */
+rtbvh_status rtbvh_update_vertices_host(rtbvh_ctx* ctx, const float* positions, uint32_t pos_stride,
+                                        const float* normals, uint32_t nrm_stride,
+                                        uint32_t first, uint32_t count);
+/* New boxes over the last build's sort order and topology, for the current positions and camera: the
+ * clip-space triangles, the leaf records and footprints, the node boxes or records (whichever the build
+ * wrote), the quantized nodes and the root box are recomputed on the context stream; the Morton codes,
+ * the sort and the Karras topology are kept (rtbvh_read_morton, rtbvh_read_sorted and the leaves' `code`
+ * stay the last build's).  At every size, the one-workgroup build's trees included.  About the cost of
+ * the build's last stage.  With RTBVH_MORTON_CPUTESTS (object-space codes) and unchanged vertices -- a
+ * camera move -- the refitted tree is the rebuilt one bit for bit; for moved vertices it is a valid BVH
+ * of the new geometry whose quality falls off as the mesh leaves the shape it was built for.
+ * RTBVH_ERR_NOT_READY without a built tree.  rtbvh_compute_bvh keeps rebuilding; a refit is never part
+ * of a captured frame, and RTBVH_FLAG_TIMING does not cover it. */
+rtbvh_status rtbvh_refit_async(rtbvh_ctx* ctx);
+rtbvh_status rtbvh_refit(rtbvh_ctx* ctx);
+
 /* ---- ray queries: closest-hit and any-hit for rays the caller chose ----------------------------
  * (No reference equivalent: findCollision, RayTraceTraversal.hlsl:106-193, is reachable only through
  * the reference's own pixel rays.)

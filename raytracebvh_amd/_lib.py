@@ -46,6 +46,7 @@ EXPORTS = [
     "rtbvh_present", "rtbvh_save_bmp", "rtbvh_assemble_bands", "rtbvh_comm_unique_id", "rtbvh_comm_init",
     "rtbvh_comm_destroy", "rtbvh_trace_tiles",
     "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts", "rtbvh_query_walk_counts",
+    "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
 
@@ -207,6 +208,10 @@ def lib() -> ctypes.CDLL:
         "rtbvh_query_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_query_counts": (i32, [vp, vp]),
         "rtbvh_query_walk_counts": (i32, [vp, vp]),
+        "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
+        "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
+        "rtbvh_refit_async": (i32, [vp]),
+        "rtbvh_refit": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -99,6 +99,12 @@ struct rtbvh_ctx {
     bool cam_dirty = false;     //   (sync_camera) when set_camera changed it
     bool have_scene = false, have_camera = false;
     Tree tree;
+    // Vertex updates (rtbvh_update_vertices_async), on any stream: they write d_opos, d_verts and the mesh box.
+    // The next build or refit waits for the last one (ev_update, wait_update); until then the built tree is not
+    // of the geometry (stale): traces and queries are refused, the readbacks return the last build's tree.
+    Event ev_update;
+    bool update_pending = false;   // ev_update recorded and no build, refit or update has waited for it yet
+    bool stale = false;
 
     // build buffers (capacity cap_T)
     uint32_t cap_T = 0;
@@ -309,6 +315,7 @@ void drop_graph(rtbvh_ctx* c) {
 // No tree: the buffers of the built one are about to be rewritten (set_scene, build_from_codes)
 void reset_tree(rtbvh_ctx* c) {
     c->tree = Tree{};
+    c->stale = false;
     c->bins_epoch++;   // (no bin set is of the next tree)
     c->tail_pending = c->leaf_pending = false;
 }
@@ -332,6 +339,7 @@ rtbvh_status sync_all(rtbvh_ctx* c) {
     rtbvh_status st = drain_slots(c);
     if (st) return st;
     if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
+    if (c->update_pending) HIPC(c, hipEventSynchronize(c->ev_update));   // (a vertex update on a caller stream)
     return RTBVH_OK;
 }
 
@@ -353,6 +361,22 @@ rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
         c->query_busy = false;
     }
     return RTBVH_OK;
+}
+
+// The next reader or writer of the vertices and the mesh box on stream s (a build, a refit, another update) waits
+// for the last vertex update.  (Never inside a capture: rtbvh_compute_bvh's plain frame before it has waited.)
+rtbvh_status wait_update(rtbvh_ctx* c, hipStream_t s) {
+    if (c->update_pending) {
+        HIPC(c, hipStreamWaitEvent(s, c->ev_update, 0));
+        c->update_pending = false;
+    }
+    return RTBVH_OK;
+}
+// What a trace or a query answers between a vertex update and the next build or refit
+rtbvh_status fail_stale(rtbvh_ctx* c, const char* what) {
+    return fail(c, RTBVH_ERR_NOT_READY,
+                std::string(what) + ": the vertices were updated after the last build -- the tree is not of this "
+                                    "geometry until rtbvh_build, rtbvh_refit or rtbvh_compute_bvh");
 }
 
 // Stream s is ordered after what the context stream holds now.  ev_built is recorded again every time (not inside
@@ -824,6 +848,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     } tail{c, c->tail_pending};
     c->tail_pending = false;
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
+    if (c->stale) return fail_stale(c, "trace");
     if (W == 0 || H == 0 || nranks == 0 || rank >= nranks || bounces > 14)
         return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
     rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
@@ -1141,6 +1166,7 @@ TracePlan plan_trace(const rtbvh_ctx* c, uint32_t f) {
 rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint32_t rank, uint32_t nranks,
                            float4* color, float* inten, hipStream_t s, uint32_t slot = 0) {
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
+    if (c->stale) return fail_stale(c, "trace");
     rtbvh_status st = sync_camera(c, s);
     if (st) return st;
     TracePlan p = plan_trace(c, c->cfg.flags);
@@ -1387,6 +1413,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     BuildArgs a = build_args(c);
     rtbvh_status cst = wait_slots(c, s);   // frames in flight read the old BVH
     if (!cst) cst = wait_queries(c, s);    // ... and so do the outstanding ray queries
+    if (!cst) cst = wait_update(c, s);     // the vertices and the mesh box of the last update
     if (!cst) cst = sync_camera(c, s);
     if (cst) return cst;
     c->bins_epoch++;   // new leaf footprints and depth range from here on: no bin set is of this tree
@@ -1411,6 +1438,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
         if (timing) c->n_builds++;
         if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, s));
         c->tree = Tree{true, clz64, RECORDS, RECORDS | PSEUDO | (qnodes ? QNODES : 0u)};
+        c->stale = false;
         return check_launch(c, "build kernel");
     }
     if (timing) HIPC(c, hipEventRecord(ev[1], s));   // (the mesh box is the scene's: rtbvh_set_scene)
@@ -1459,6 +1487,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     if (!c->capturing) HIPC(c, hipEventRecord(c->ev_built, s));
     // (the refit kernels quantize the QNodes)
     c->tree = Tree{true, clz64, nodes, (uint32_t)nodes | (a.pseudo ? PSEUDO : 0u) | QNODES};
+    c->stale = false;
     return check_launch(c, "build kernels");
 }
 
@@ -1547,6 +1576,7 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
     // frames in flight on caller streams, as rtbvh_build_async
     rtbvh_status cst = wait_slots(c, c->stream);
     if (!cst) cst = wait_queries(c, c->stream);
+    if (!cst) cst = wait_update(c, c->stream);   // (the replayed build reads the updated vertices and mesh box)
     if (!cst) cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
     if (cst) return cst;
     HIPC(c, hipGraphLaunch(c->graph_exec, c->stream));
@@ -1554,6 +1584,7 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
     // the host-side state of the captured frame: its tree (the replayed build rewrote it for this camera, so
     // whatever was derived since belongs to the old one) and its trace (one in between may have changed it)
     c->tree = c->graph_tree;
+    c->stale = false;
     c->bins_epoch++;   // (the replayed build rewrote the footprints, the replayed trace the context stream's bin set)
     const rtbvh_ctx::TraceState& g = c->graph_state;
     c->W = g.W;
@@ -1586,6 +1617,109 @@ rtbvh_status rtbvh_compute_bvh(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     return rtbvh_synchronize(c);
 }
 
+// ---- animated geometry: vertex updates and the topology-keeping refit -----------------------
+static rtbvh_status check_update(rtbvh_ctx* c, const float* positions, uint32_t pos_stride, const float* normals,
+                                 uint32_t nrm_stride, uint32_t first, uint32_t count) {
+    if (!positions) return fail(c, RTBVH_ERR_INVALID_ARG, "update_vertices: NULL positions");
+    if (pos_stride < 3 || (normals && nrm_stride < 3))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "update_vertices: a stride below 3 floats");
+    if (!c->have_scene) return fail(c, RTBVH_ERR_NOT_READY, "update_vertices before set_scene");
+    if (first > c->V || count > c->V - first)
+        return fail(c, RTBVH_ERR_INVALID_ARG, "update_vertices: first + count exceeds the scene's vertices");
+    return RTBVH_OK;
+}
+
+// One kernel (two with the mesh box's final reduction) on the caller's stream, behind the frames in flight -- they
+// read the normals -- and the context stream's work so far (a build reads the positions and the box, a trace the
+// normals); nothing is reallocated, nothing waits on the host, and a captured frame stays: its kernels read the
+// same buffers.
+rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* c, const float* dev_positions, uint32_t pos_stride,
+                                         const float* dev_normals, uint32_t nrm_stride, uint32_t first,
+                                         uint32_t count, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (count == 0) return RTBVH_OK;
+    rtbvh_status st = check_update(c, dev_positions, pos_stride, dev_normals, nrm_stride, first, count);
+    if (st) return st;
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!c->ev_update) HIPC(c, hipEventCreateWithFlags(c->ev_update.out(), hipEventDisableTiming));
+    st = wait_slots(c, s);
+    if (!st) st = order_after_context(c, s);
+    if (!st) st = wait_update(c, s);   // (an earlier update on another stream wrote the same buffers)
+    if (st) return st;
+    VertexUpdate u{};
+    u.pos = dev_positions;
+    u.pos_stride = pos_stride;
+    u.nrm = dev_normals;
+    u.nrm_stride = nrm_stride;
+    u.first = first;
+    u.count = count;
+    u.opos = c->d_opos;
+    u.verts = c->d_verts;
+    u.bounds = c->cfg.morton_mode == RTBVH_MORTON_CPUTESTS ? c->d_bounds.h : nullptr;
+    u.V = c->V;
+    launch_update_vertices(u, s);
+    st = check_launch(c, "vertex update");
+    HIPC(c, hipEventRecord(c->ev_update, s));
+    c->update_pending = true;
+    c->stale = c->tree.built;
+    return st;
+}
+
+rtbvh_status rtbvh_update_vertices_host(rtbvh_ctx* c, const float* positions, uint32_t pos_stride,
+                                        const float* normals, uint32_t nrm_stride, uint32_t first, uint32_t count) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (count == 0) return RTBVH_OK;
+    rtbvh_status st = check_update(c, positions, pos_stride, normals, nrm_stride, first, count);
+    if (st) return st;
+    HIPC(c, hipSetDevice(c->cfg.device));
+    // the arrays as they are, strides included: the last vertex's three floats end each
+    const size_t np = (size_t)(count - 1) * pos_stride + 3, nn = normals ? (size_t)(count - 1) * nrm_stride + 3 : 0;
+    DevBuf<float> d;
+    HIPC(c, d.alloc(np + nn));
+    HIPC(c, hipMemcpy(d, positions, np * sizeof(float), hipMemcpyHostToDevice));
+    if (normals) HIPC(c, hipMemcpy(d + np, normals, nn * sizeof(float), hipMemcpyHostToDevice));
+    st = rtbvh_update_vertices_async(c, d, pos_stride, normals ? d + np : nullptr, nrm_stride, first, count, nullptr);
+    if (st) return st;
+    HIPC(c, hipStreamSynchronize(c->stream));   // (the staging buffer goes with this scope)
+    return RTBVH_OK;
+}
+
+// New boxes over the last build's sort order and topology (sorted, topo, pleaf, pint stay): the clip-space
+// triangles of the current positions and camera (k_morton<false>), then the build's own refit stages, which write
+// everything downstream -- leaf records and footprints, node records or node boxes in the form the build wrote
+// (and the leaf pseudo-records if the tree had them), the QNodes with their margin codes, the root box with
+// its depth range and edge bound.  A one-workgroup build (k_build_small) leaves the same arrays, so its tree
+// is refitted by the same kernels.  Forms derived since the build (ensure_form) are of the old boxes: dropped.
+rtbvh_status rtbvh_refit_async(rtbvh_ctx* c) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (!c->have_scene || !c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "refit before build");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    rtbvh_status st = wait_slots(c, s);   // frames in flight and ray queries read the old boxes
+    if (!st) st = wait_queries(c, s);
+    if (!st) st = wait_update(c, s);
+    if (!st) st = sync_camera(c, s);
+    if (st) return st;
+    c->bins_epoch++;   // new leaf footprints and depth range: no bin set is of this tree
+    BuildArgs a = build_args(c);
+    a.pseudo = a.rec_on && (c->tree.valid & PSEUDO) ? 1u : 0u;
+    launch_clip(a, s);
+    launch_refit_leaves(a, s);
+    launch_refit_tail(a, s);
+    c->leaf_pending = c->tail_pending = false;
+    HIPC(c, hipEventRecord(c->ev_built, s));
+    c->tree.valid = (uint32_t)c->tree.wrote | (a.pseudo ? PSEUDO : 0u) | QNODES;
+    c->stale = false;
+    return check_launch(c, "refit kernels");
+}
+
+rtbvh_status rtbvh_refit(rtbvh_ctx* c) {
+    rtbvh_status st = rtbvh_refit_async(c);
+    if (st) return st;
+    return rtbvh_synchronize(c);
+}
+
 // The identity check of a fast walk (DESIGN.md "Traversal orders"): the frame in the
 // reference order (the exact findCollision DFS, RayTraceTraversal.hlsl:106-193) into a
 // scratch buffer, then the frame with the context's walks into the framebuffer, compared
@@ -1593,6 +1727,7 @@ rtbvh_status rtbvh_compute_bvh(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
 rtbvh_status rtbvh_verify_walk(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint64_t* differing) {
     if (!c || !differing) return RTBVH_ERR_INVALID_ARG;
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "verify_walk before build");
+    if (c->stale) return fail_stale(c, "verify_walk");
     if (W == 0 || H == 0 || bounces > 14) return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
     HIPC(c, hipSetDevice(c->cfg.device));
     rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
@@ -2130,6 +2265,7 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     if (n == 0) return RTBVH_OK;
     if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "query: NULL rays or hits");
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "query before build");
+    if (c->stale) return fail_stale(c, "query");
     static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "query record layouts");
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -2212,7 +2348,7 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
 
 rtbvh_status rtbvh_query_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->tree.built)   // (nothing to stage: the query's checks)
+    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
         return rtbvh_query_async(c, rays, n, hits, mode, nullptr);
     HIPC(c, hipSetDevice(c->cfg.device));
     DevBuf<char> d;

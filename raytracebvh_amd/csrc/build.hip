@@ -172,13 +172,58 @@ __global__ __launch_bounds__(BLOCK) void k_bounds_final(float* __restrict__ boun
     if (threadIdx.x == 0) st_box(bounds, mn, mx);
 }
 
+// rtbvh_update_vertices_async: vertices [first, first + count) from the caller's device arrays -- the position
+// into opos (float4, w = 0 as set_scene writes it), the normal, when given, into the vertex record's normal
+// words; texcoords stay.  The record's position words are not kept in step: no kernel and no readback reads
+// them (the shading takes words 3..7, the build opos), and writing them made the pass 0.58 ms instead of
+// 0.16 for C5's 30M vertices.
+// BOX (an update of all V vertices in CPUTests Morton mode): k_bounds's per-workgroup partials of the new
+// mesh box in the same pass -- the same grid and strides, so the same partials -- for k_bounds_final.
+template <bool BOX>
+__global__ __launch_bounds__(BLOCK) void k_update_vertices(VertexUpdate u) {
+    __shared__ float s_red[24];
+    f3 mn = mk(INFINITY, INFINITY, INFINITY), mx = mk(-INFINITY, -INFINITY, -INFINITY);
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < u.count; i += (size_t)gridDim.x * BLOCK) {
+        const float* p = u.pos + i * u.pos_stride;
+        const float x = p[0], y = p[1], z = p[2];
+        const size_t v = (size_t)u.first + i;
+        u.opos[v] = make_float4(x, y, z, 0.f);
+        if (u.nrm) {
+            const float* n = u.nrm + i * u.nrm_stride;
+            float* d = u.verts + 8 * v;
+            d[3] = n[0]; d[4] = n[1]; d[5] = n[2];
+        }
+        if (BOX) {
+            mn = vmin(mn, mk(x, y, z));
+            mx = vmax(mx, mk(x, y, z));
+        }
+    }
+    if (BOX) {
+        reduce_box_block<BLOCK / 64>(mn, mx, s_red);
+        if (threadIdx.x == 0) st_box(u.bounds + 8 + 6 * (size_t)blockIdx.x, mn, mx);
+    }
+}
+
+// Triangle t's object-space vertices p, their clip-space images c (MortonCodes.hlsl:60-85: mul(pos, WVP).xyz)
+// and its clip-space record: what the Morton pass stores in tclip, and all a refit over a kept topology
+// recomputes of it (k_morton<false>)
+__device__ __forceinline__ void clip_tri(const BuildArgs& a, uint32_t t, f3 (&p)[3], f3 (&c)[3], float4 (&clip)[4]) {
+    const uint32_t i0 = a.idx[3 * (size_t)t], i1 = a.idx[3 * (size_t)t + 1], i2 = a.idx[3 * (size_t)t + 2];
+    const float4 q0 = a.opos[i0], q1 = a.opos[i1], q2 = a.opos[i2];
+    p[0] = mk(q0.x, q0.y, q0.z); p[1] = mk(q1.x, q1.y, q1.z); p[2] = mk(q2.x, q2.y, q2.z);
+    c[0] = xform_point(a.cam, p[0]); c[1] = xform_point(a.cam, p[1]); c[2] = xform_point(a.cam, p[2]);
+    clip[0] = make_float4(c[0].x, c[0].y, c[0].z, __uint_as_float(t));
+    clip[1] = make_float4(c[1].x, c[1].y, c[1].z, 0.f);
+    clip[2] = make_float4(c[2].x, c[2].y, c[2].z, 0.f);
+    // the shading's gathers in one record: the vertex indices and the material index
+    clip[3] = make_float4(__uint_as_float(i0), __uint_as_float(i1), __uint_as_float(i2), __uint_as_float(a.matidx[t]));
+}
 // MortonCodes.hlsl:54-125 (HLSL mode) / ShaderSim/main.cpp:292-301 (CPUTests mode):
 // triangle t's code (also stored in keys/vals) and its clip-space triangle
 __device__ __forceinline__ uint32_t morton_code(const BuildArgs& a, uint32_t t, float4 (&clip)[4]) {
-    const uint32_t i0 = a.idx[3 * (size_t)t], i1 = a.idx[3 * (size_t)t + 1], i2 = a.idx[3 * (size_t)t + 2];
-    const float4 q0 = a.opos[i0], q1 = a.opos[i1], q2 = a.opos[i2];
-    const f3 p0 = mk(q0.x, q0.y, q0.z), p1 = mk(q1.x, q1.y, q1.z), p2 = mk(q2.x, q2.y, q2.z);
-    const f3 c0 = xform_point(a.cam, p0), c1 = xform_point(a.cam, p1), c2 = xform_point(a.cam, p2);
+    f3 p[3], c[3];
+    clip_tri(a, t, p, c, clip);
+    const f3 p0 = p[0], p1 = p[1], p2 = p[2], c0 = c[0], c1 = c[1], c2 = c[2];
     uint32_t code;
     if (a.morton_mode == 0) {
         f3 mn, mx;
@@ -199,11 +244,6 @@ __device__ __forceinline__ uint32_t morton_code(const BuildArgs& a, uint32_t t, 
     }
     a.keys[t] = code;
     a.vals[t] = t;
-    clip[0] = make_float4(c0.x, c0.y, c0.z, __uint_as_float(t));
-    clip[1] = make_float4(c1.x, c1.y, c1.z, 0.f);
-    clip[2] = make_float4(c2.x, c2.y, c2.z, 0.f);
-    // the shading's gathers in one record: the vertex indices and the material index
-    clip[3] = make_float4(__uint_as_float(i0), __uint_as_float(i1), __uint_as_float(i2), __uint_as_float(a.matidx[t]));
     return code;
 }
 __device__ __forceinline__ uint32_t morton_tri(const BuildArgs& a, uint32_t t) {
@@ -217,12 +257,20 @@ __device__ __forceinline__ uint32_t morton_tri(const BuildArgs& a, uint32_t t) {
 // One thread per triangle; the 48-B clip-space triangles of a wave (3 KB contiguous) are staged
 // in LDS and stored 16 B per lane (scripts/write_roofline.hip: 4.1 TB/s against 2.5-2.9 for a
 // whole record per lane).
+// CODES = false: the clip-space triangles alone, for a refit over the last build's sort order and topology
+// (launch_clip): the same transform and staging, and no write to keys / vals.
+template <bool CODES>
 __global__ __launch_bounds__(BLOCK) void k_morton(BuildArgs a) {
     __shared__ float4 s_clip[BLOCK / 64][TCS * 64];
     const uint32_t t = blockIdx.x * BLOCK + threadIdx.x, lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (t < a.T) {
         float4 clip[4];
-        morton_code(a, t, clip);
+        if (CODES) {
+            morton_code(a, t, clip);
+        } else {
+            f3 p[3], c[3];
+            clip_tri(a, t, p, c, clip);
+        }
 #pragma unroll
         for (int k = 0; k < 3; k++) s_clip[w][TCS * lane + k] = clip[k];
         if (TCS == 4) s_clip[w][TCS * lane + 3] = clip[3];
@@ -1638,8 +1686,28 @@ void launch_bounds(const BuildArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_bounds, dim3(blocks), dim3(BLOCK), 0, s, a.opos, a.V, a.bounds);
     hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(BLOCK), 0, s, a.bounds, blocks);
 }
+void launch_update_vertices(const VertexUpdate& u, hipStream_t s) {
+    uint32_t blocks = blocks_for(u.count);   // (k_bounds's grid: launch_bounds)
+    if (blocks > BOUNDS_BLOCKS) blocks = BOUNDS_BLOCKS;
+    if (u.bounds && u.first == 0 && u.count == u.V) {   // every vertex: the mesh box in the same pass
+        hipLaunchKernelGGL(k_update_vertices<true>, dim3(blocks), dim3(BLOCK), 0, s, u);
+        hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(BLOCK), 0, s, u.bounds, blocks);
+        return;
+    }
+    hipLaunchKernelGGL(k_update_vertices<false>, dim3(blocks), dim3(BLOCK), 0, s, u);
+    if (u.bounds) {   // a range: the box over all of opos afterwards
+        BuildArgs a{};
+        a.opos = u.opos;
+        a.V = u.V;
+        a.bounds = u.bounds;
+        launch_bounds(a, s);
+    }
+}
 void launch_morton(const BuildArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_morton, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_morton<true>, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a);
+}
+void launch_clip(const BuildArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_morton<false>, dim3(blocks_for(a.T)), dim3(BLOCK), 0, s, a);
 }
 void launch_karras(const BuildArgs& a, hipStream_t s) {
     if (a.T < 2) return;

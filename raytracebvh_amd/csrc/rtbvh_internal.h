@@ -81,6 +81,22 @@ struct BuildArgs {
 };
 void launch_bounds(const BuildArgs& a, hipStream_t s);
 void launch_morton(const BuildArgs& a, hipStream_t s);
+// the Morton pass without the codes: the clip-space triangles (tclip) of the current positions and camera, for a
+// refit over the last build's sort order and topology (keys and vals are left alone)
+void launch_clip(const BuildArgs& a, hipStream_t s);
+// A vertex update (rtbvh_update_vertices_async): `count` vertices from `first` on, read from device memory
+struct VertexUpdate {
+    const float* pos;         // positions, 3 floats each, pos_stride floats apart
+    uint32_t pos_stride;
+    const float* nrm;         // normals (nrm_stride floats apart), or null: the normals stay
+    uint32_t nrm_stride;
+    uint32_t first, count;    // count > 0, first + count <= V
+    float4* opos;             // [V] BuildArgs::opos
+    float* verts;             // [8 V] TraceArgs::verts
+    float* bounds;            // CPUTests Morton mode: BuildArgs::bounds, recomputed in stream order; else null
+    uint32_t V;
+};
+void launch_update_vertices(const VertexUpdate& u, hipStream_t s);
 // Karras topology (topo, pleaf, pint)
 void launch_karras(const BuildArgs& a, hipStream_t s);
 // leaf records + refit + node records + QNodes (zeroes the tickets it uses)

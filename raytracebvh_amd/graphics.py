@@ -75,6 +75,38 @@ def check_query_rays(rays, device=None):
     return "numpy", rays.view(_L.RAY_DTYPE).reshape(-1)
 
 
+def check_vertex_array(a, what="positions", device=None):
+    """Context.update_vertices' input check: (kind, array, stride in floats) for an (n, 3) float32 torch CUDA
+    tensor ("torch"; on `device` when given) or numpy array ("numpy") whose last dimension is contiguous and
+    whose rows are at least 3 floats apart -- a packed (V, 3) array (stride 3), the [:, :3] view of a float4
+    array (4) or of an rtbvh_vertex array (8); ValueError for anything else.  Calls nothing in the library."""
+    name = "update_vertices: " + what
+    if _is_tensor(a):
+        import torch
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must be an (n, 3) float32 tensor, got {tuple(a.shape)} {a.dtype}")
+        if not a.is_cuda:
+            raise ValueError(f"{name}: a torch tensor must be on the context's GPU (numpy arrays take the host path)")
+        if device is not None and a.device.index != device:
+            raise ValueError(f"{name} on {a.device}, the context on device {device}")
+        if a.shape[0] <= 1:
+            return "torch", a.contiguous(), 3
+        if a.stride(1) != 1 or a.stride(0) < 3:
+            raise ValueError(f"{name}: the last dimension must be contiguous and the rows at least 3 floats apart, "
+                             f"got strides {tuple(a.stride())}")
+        return "torch", a, a.stride(0)
+    if not isinstance(a, np.ndarray):
+        raise ValueError(f"{name} must be a torch CUDA tensor or a numpy array")
+    if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{name} must be an (n, 3) float32 array, got {a.shape} {a.dtype}")
+    if a.shape[0] <= 1:
+        return "numpy", np.ascontiguousarray(a), 3
+    if a.strides[1] != 4 or a.strides[0] % 4 or a.strides[0] < 12:
+        raise ValueError(f"{name}: the last dimension must be contiguous and the rows at least 3 floats apart, "
+                         f"got byte strides {a.strides}")
+    return "numpy", a, a.strides[0] // 4
+
+
 class Context:
     """One rtbvh_ctx: one HIP device, one stream, the scene/BVH/frame buffers."""
 
@@ -192,6 +224,50 @@ class Context:
 
     def synchronize(self):
         self._check(_L.lib().rtbvh_synchronize(self._h))
+
+    # -- animated geometry --
+    def update_vertices(self, positions, normals=None, first: int = 0, stream=None):
+        """rtbvh_update_vertices_async / rtbvh_update_vertices_host: new positions (and, when given, normals) for
+        the vertices [first, first + n) of the scene; indices, materials and texcoords stay (include/rtbvh.h).
+
+        (n, 3) float32 torch CUDA tensors on the context's device go to the device entry with no host copy,
+        enqueued on `stream` (a torch stream or a hipStream_t handle; default: the current torch stream; torch's
+        legacy default stream, which the library cannot name, is synchronised and the update runs on the context
+        stream); numpy arrays go through the synchronous host entry.  The row stride is taken from the array
+        (check_vertex_array).  Until the next build(), refit() or compute_bvh(), trace() and query() raise
+        ERR_NOT_READY.  ValueError for a wrong dtype, device, shape or layout."""
+        kind, pos, ps = check_vertex_array(positions, "positions", getattr(self, "device", None))
+        nrm, ns = None, 0
+        if normals is not None:
+            nkind, nrm, ns = check_vertex_array(normals, "normals", getattr(self, "device", None))
+            if nkind != kind or nrm.shape[0] != pos.shape[0]:
+                raise ValueError("update_vertices: normals must be of the positions' kind and length")
+        n = int(pos.shape[0])
+        if first < 0 or n < 0 or first + n > 0xFFFFFFFF:
+            raise ValueError("update_vertices: first + n out of range")
+        L = _L.lib()
+        if kind == "numpy":
+            self._check(L.rtbvh_update_vertices_host(self._h, ctypes.c_void_p(pos.ctypes.data), ps,
+                                                     ctypes.c_void_p(nrm.ctypes.data) if nrm is not None else None,
+                                                     ns, first, n))
+            return
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(pos.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(pos.device).synchronize()
+        self._check(L.rtbvh_update_vertices_async(self._h, ctypes.c_void_p(pos.data_ptr()), ps,
+                                                  ctypes.c_void_p(nrm.data_ptr()) if nrm is not None else None,
+                                                  ns, first, n, ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+
+    def refit(self, sync: bool = True):
+        """rtbvh_refit / rtbvh_refit_async: new boxes over the last build's sort order and topology, for the
+        current positions and camera."""
+        L = _L.lib()
+        self._check(L.rtbvh_refit(self._h) if sync else L.rtbvh_refit_async(self._h))
 
     # -- ray queries --
     def query(self, rays, mode: int = 0, out=None, stream=None):
