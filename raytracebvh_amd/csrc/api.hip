@@ -65,6 +65,28 @@ struct Pinned : Owner<T*, del_pinned<T>> {
 };
 using Event = Owner<hipEvent_t, del_event>;
 using Stream = Owner<hipStream_t, del_stream>;
+// A device buffer grown on demand, with the capacity it was allocated for: {null, 0} before the first reserve and
+// after one that failed, so a capacity never vouches for a pointer that is not there (the next call tries again).
+// What else a growth means -- a captured frame to drop, a wait for the readers of the old buffer, a memset of
+// the new one -- belongs to the call site: `if (!b.has(n)) { ...; HIPC(c, b.reserve(n)); ... }`.
+template <typename T>
+struct Grown {
+    DevBuf<T> buf;
+    size_t cap = 0;   // elements
+    bool has(size_t n) const { return n == 0 || (n <= cap && buf); }   // (no element needs no buffer)
+    hipError_t reserve(size_t n) {   // frees first, like DevBuf::alloc
+        if (has(n)) return hipSuccess;
+        const hipError_t e = buf.alloc(n);
+        if (e != hipSuccess) buf.h = nullptr;
+        cap = e == hipSuccess ? n : 0;
+        return e;
+    }
+    void reset() {
+        buf.reset();
+        cap = 0;
+    }
+    operator T*() const { return buf.h; }
+};
 
 // The forms of the built tree a walk or a reader may ask for (Tree::valid, ensure_form)
 enum Form : uint32_t { RECORDS = 1, NBOX = 2, PSEUDO = 4, QNODES = 8 };
@@ -80,11 +102,87 @@ struct Tree {
                              //   (the packet walks') and the QNodes (the 4-wide bounce walk's)
 };
 
+// RTBVH_FLAG_BINNED_PRIMARY: a bin set -- tile counts / offsets, fill cursors, the bins and the rank's leaf
+// list (trace.hip k_pb_bin) -- is a product of the built tree and the frame shape, like the leaf footprints it
+// is made from: the two bin passes and the scan read nothing else (PbKey), and every kernel behind them only
+// reads the set.  So a set records the key it was filled for, and a later binned trace with the same key, on any
+// stream, uses it as it is (find_bins) instead of zeroing and filling its own: one fill per build and frame
+// shape, and one set in memory for all the frames in flight.  A trace that finds none fills the set of its own
+// trace buffer set (prepare_walks).  RTBVH_BINS_REUSE=0: every trace fills its own set (A/B).
+struct PbKey {
+    uint64_t build = 0;           // bins_epoch of the fill: the tree whose footprints and depth range it read
+    uint32_t W = 0, H = 0, rows = 0, rank = 0, nranks = 0, T = 0, ntx = 0, nty = 0;
+    uint32_t share = 0;           // the band deal (root_share; 16 with one rank: no deal) ...
+    const uint32_t* deal = nullptr;   // ... and its device table (null: round-robin, computed in the kernel)
+    bool operator==(const PbKey& o) const {
+        return build == o.build && W == o.W && H == o.H && rows == o.rows && rank == o.rank &&
+               nranks == o.nranks && T == o.T && ntx == o.ntx && nty == o.nty && share == o.share &&
+               deal == o.deal;
+    }
+};
+struct PbBufs {
+    DevBuf<uint32_t> off, cur, sums;
+    DevBuf<uint4> bins;
+    uint32_t cap_T = 0, cap_tiles = 0, cap_bins = 0;   // (cap_bins is what the fill clipped at: the readers' `cap`)
+    Grown<uint32_t> list;       // N > 1: the rank's leaves (TraceArgs::pb_list)
+    PbKey key;                  // what the set holds, when `valid`
+    bool valid = false;
+    Event filled;               // recorded behind the fill pass: a reader on another stream waits for it
+    uint32_t readers = 0;       // trace buffer sets whose traces have read the set since its fill (bit k: set k)
+};
+
+// A trace buffer set: everything one primary -> bounce chain writes.  Set 0 is the context stream's; set b >= 1
+// is chain b of a context-stream trace dealt over chains (the rank's bands over `nsplit` chains on their own
+// streams, so one chain's kernel tail overlaps the others' work), or the set of a caller stream with frames in
+// flight (rtbvh_trace_band_async on a stream other than the context's): such traces run concurrently over the
+// one BVH, wait only for the last build (ev_built) and the next build waits for them (`done`).  A context does
+// one or the other (slots_used).
+struct TraceSet {
+    // `chain` stands first: destroyed after the set's buffers and events.  Across sets and the rest of the
+    // context the order does not matter: a chain is joined into the trace's stream before the trace ends, and
+    // rtbvh_destroy drains the context stream and every caller stream's frame before anything goes.
+    Stream chain;                   // chain b's stream (b >= 1), created on first use
+    Event join;                     //   ... joined into the trace's stream
+    hipStream_t caller = nullptr;   // the caller stream that owns the set (b >= 1), from its first trace on
+    Event done;                     //   recorded behind its last trace
+    bool busy = false;              //   ... which no build has waited for yet
+    DevBuf<RayQ> q[2];              // the bounce queues, ping-pong: set 0's hold cap_P rays, the others cap_split
+    DevBuf<float2> hit;             // per queued bounce ray: (t, leaf | INVALID)
+    // the certified walks: the rays a pass re-traces in the reference order (their counts:
+    // qcount 16..31), and the bounce walk's deferred rays (trace.hip DEFER_*), kept clean
+    Grown<uint32_t> redo, defer;
+    PbBufs pb;
+    Grown<unsigned long long> pbkeys;   // an RTBVH_PB_FUSE=0 build's (t, leaf) keys: a result, so per set
+    // its parts of the context's shared blocks (consecutive sets' parts are consecutive: one launch_zero covers
+    // a trace's chains), set where the blocks are allocated
+    uint32_t* qcount = nullptr;             // [32] of d_qcount: queue counts [0..15], re-trace counts [16..31]
+    uint32_t* next = nullptr;               // [NEXT_WORDS] of d_next: segmented bounce work counters
+    unsigned long long* counters = nullptr; // [64] of d_counters: see rtbvh_get_stats
+    unsigned long long* ovf = nullptr;      // its word of h_ovf
+};
+
+// What the readbacks and rtbvh_get_stats know of the last trace.  enqueue_walks assigns it whole; a replayed
+// graph (compute_graph) restores the record its capture ended with.
+struct LastTrace {
+    bool traced = false;
+    uint32_t W = 0, H = 0, bounces = 0, rank = 0, nranks = 1;
+    uint32_t nsplit = 1;             // its chains
+    uint32_t slot = 0;               // its buffer set (the counters there are the stats)
+    size_t rec_P = 0;                // pixels with ray records (RTBVH_FLAG_REFRACT_RECORDS), or 0
+    uint32_t walk = 0;               // its walk flags
+    uint32_t walk_state = 0;         // rtbvh_stats.walk_state
+    bool cert = false;               // certified (its re-trace counts)
+    bool frame_here = false;         // d_color holds its whole frame
+    bool intensity_here = false;     // d_intensity holds its intensities
+};
+
 struct rtbvh_ctx {
     rtbvh_config cfg{};
     // Members are destroyed last to first: the streams the context created stand first, so they outlive every
-    // buffer and event below (rtbvh_destroy has drained them by then).
-    Stream own_stream, side, sub[RTBVH_MAXSPLIT];
+    // buffer and event below (rtbvh_destroy has drained them by then).  The chains' streams: TraceSet.
+    Stream own_stream, side;
+    static constexpr uint32_t MAXSPLIT = RTBVH_MAXSPLIT;   // buffer sets: the context stream's + chains / caller streams
+    TraceSet sets[MAXSPLIT];
     hipStream_t stream = nullptr;   // the context stream: the caller's (cfg.stream) or own_stream
     std::string err;
 
@@ -110,8 +208,7 @@ struct rtbvh_ctx {
     uint32_t cap_T = 0;
     DevBuf<uint32_t> d_codes, d_ids, d_ka, d_va, d_kb, d_vb, d_sort_scratch;
     DevBuf<float4> d_tclip, d_leaf;
-    DevBuf<float4> d_band;                   // rtbvh_trace_tiles: this rank's bands; rank 0: all ranks'
-    size_t cap_band = 0;                     //   (float4 capacity)
+    Grown<float4> d_band;                    // rtbvh_trace_tiles: this rank's bands; rank 0: all ranks'
     DevBuf<Inner> d_inner;                   // box hand-off of refit nodes spanning workgroups
     DevBuf<uint4> d_topo;                    // Karras node: child ids + leaf range
     DevBuf<Inner> d_rec;                     // node records in slots (rtbvh_device.h), 2T-1
@@ -121,15 +218,14 @@ struct rtbvh_ctx {
     DevBuf<uint4> d_texinfo;
     DevBuf<float> d_srgb;
     uint32_t ntex = 0;
-    DevBuf<float> d_refl_rec;                // RTBVH_FLAG_REFRACT_RECORDS: reflectRay / refractRay
-    DevBuf<float> d_refr_rec;                //   RayPresent records, 14 floats per traced pixel
-    size_t cap_rec = 0, rec_P = 0;           // record capacity; pixels of the last records trace
+    Grown<float> d_refl_rec;                 // RTBVH_FLAG_REFRACT_RECORDS: reflectRay / refractRay
+    Grown<float> d_refr_rec;                 //   RayPresent records, 14 floats per traced pixel
     DevBuf<uint32_t> d_pleaf, d_pint, d_cnt;
     DevBuf<uint32_t> d_xlist, d_xcnt;        // refit: crossing nodes per workgroup
     DevBuf<uint32_t> d_qlate;                // BuildArgs::qlate
     DevBuf<unsigned long long> d_ovf;        // stack overflows + guard trips of every trace (never reset)
     Pinned<unsigned long long> h_ovf;        // pinned: a snapshot of *d_ovf copied at the end of each trace,
-                                             //   one word per slot; ovf_seen: the value last reported
+                                             //   one word per buffer set (TraceSet::ovf); ovf_seen: the value last reported
     unsigned long long ovf_seen = 0;
     DevBuf<float> d_bounds, d_rootbox, d_zpart;
     // rtbvh_compute_bvh: the binned primary pass of the frame starts on `side` once the build's
@@ -139,71 +235,27 @@ struct rtbvh_ctx {
     DevBuf<float> d_nbox;        // [6 (T-1)] internal node boxes
     // rtbvh_compute_bvh: the build leaves its crossing nodes (launch_refit_tail) to the frame's binned
     // pass, which runs them in its bin launches (launch_pb_bin_tail); any other first use of the tree
-    // runs them first (flush_tail).  The two *_pending are the build's hand-off to the trace, reset with `tree`
-    bool tail_want = false, tail_pending = false;
-    bool leaf_want = false;      // the next build records ev_leaf
+    // runs them first (flush_tail).  The two *_pending are the build's hand-off to the trace (build_tree's
+    // Handoff), reset with `tree`
+    bool tail_pending = false;
     bool leaf_pending = false;   // ev_leaf recorded and nothing enqueued on the stream since
     SortResult sorted{nullptr, nullptr};
 
-    // trace buffers (capacity cap_P pixels)
+    // trace buffers (capacity cap_P pixels; with them set 0's queues and hit records)
     size_t cap_P = 0;
-    uint32_t W = 0, H = 0, bounces = 0, rank = 0, nranks = 1;
     DevBuf<float4> d_color;
     DevBuf<float> d_intensity;
-    DevBuf<RayQ> d_q[2];
     DevBuf<uint32_t> d_bkin, d_bvin, d_bka, d_bva, d_bkb, d_bvb, d_bscratch;   // bounce coherence sort
-    DevBuf<uint32_t> d_qcount;                // [32 x MAXSPLIT]: per pipeline, queue counts [0..15] and
-                                              //   bounce work counters [16..31]
-    DevBuf<float2> d_hit;                     // per queued bounce ray: (t, leaf | INVALID)
-    DevBuf<uint32_t> d_next;                  // [NEXT_WORDS x MAXSPLIT]: segmented bounce work counters
-    // pipelines 1.. of a split trace (pipeline 0 = d_q / d_hit on the context stream): a
-    // rank's bands dealt over `nsplit` independent primary -> bounce chains on their own
-    // streams, so one chain's kernel tail overlaps the others' work
-    static constexpr uint32_t MAXSPLIT = RTBVH_MAXSPLIT;   // buffer sets: the context stream's + caller-stream slots
-    DevBuf<RayQ> d_qs[MAXSPLIT][2];
-    DevBuf<float2> d_hits[MAXSPLIT];
-    size_t cap_split = 0;                     // rays per pipeline queue
-    Event ev_fork, ev_join[MAXSPLIT];
-    uint32_t nsplit = 1;                      // pipelines of the last trace
-    // RTBVH_FLAG_BINNED_PRIMARY: a bin set -- tile counts / offsets, fill cursors, the bins and the rank's leaf
-    // list (trace.hip k_pb_bin) -- is a product of the built tree and the frame shape, like the leaf footprints it
-    // is made from: the two bin passes and the scan read nothing else (PbKey), and every kernel behind them only
-    // reads the set.  So a set records the key it was filled for, and a later binned trace with the same key, on any
-    // stream, uses it as it is (find_bins) instead of zeroing and filling its own: one fill per build and frame
-    // shape, and one set in memory for all the frames in flight.  A trace that finds none fills the set of its own
-    // buffer slot (enqueue_walks).  RTBVH_BINS_REUSE=0: every trace fills its slot's set (A/B).
-    struct PbKey {
-        uint64_t build = 0;           // bins_epoch of the fill: the tree whose footprints and depth range it read
-        uint32_t W = 0, H = 0, rows = 0, rank = 0, nranks = 0, T = 0, ntx = 0, nty = 0;
-        uint32_t share = 0;           // the band deal (root_share; 16 with one rank: no deal) ...
-        const uint32_t* deal = nullptr;   // ... and its device table (null: round-robin, computed in the kernel)
-        bool operator==(const PbKey& o) const {
-            return build == o.build && W == o.W && H == o.H && rows == o.rows && rank == o.rank &&
-                   nranks == o.nranks && T == o.T && ntx == o.ntx && nty == o.nty && share == o.share &&
-                   deal == o.deal;
-        }
-    };
-    struct PbBufs {
-        DevBuf<uint32_t> off, cur, sums;
-        DevBuf<uint4> bins;
-        uint32_t cap_T = 0, cap_tiles = 0, cap_bins = 0;   // (cap_bins is what the fill clipped at: the readers' `cap`)
-        DevBuf<uint32_t> list;      // N > 1: the rank's leaves (TraceArgs::pb_list)
-        size_t cap_list = 0;
-        PbKey key;                  // what the set holds, when `valid`
-        bool valid = false;
-        Event filled;               // recorded behind the fill pass: a reader on another stream waits for it
-        uint32_t readers = 0;       // buffer slots whose traces have read the set since its fill (bit k: slot k)
-    } pb[MAXSPLIT];
-    // the (t, leaf) keys of an RTBVH_PB_FUSE=0 build's separate shading launch: a result, so per buffer slot
-    DevBuf<unsigned long long> d_pbkeys[MAXSPLIT];
-    size_t cap_pbkeys[MAXSPLIT] = {};
+    // one block each for all the sets (TraceSet::qcount, next, counters)
+    DevBuf<uint32_t> d_qcount;                // [32 x MAXSPLIT]
+    DevBuf<uint32_t> d_next;                  // [NEXT_WORDS x MAXSPLIT]
+    DevBuf<unsigned long long> d_counters;    // [64 x MAXSPLIT]
+    size_t cap_split = 0;                     // rays per queue of the sets 1.. (ensure_split_capacity)
+    Event ev_fork;                            // a trace dealt over chains: they start behind it
     uint64_t bins_epoch = 1;        // bumped whenever the leaf footprints are (or are about to be) rewritten
     uint64_t bin_builds = 0;        // count passes launched (rtbvh_bin_builds)
     bool knob_bins_reuse = true;    // RTBVH_BINS_REUSE
-    DevBuf<unsigned long long> d_counters;    // [64]: see rtbvh_get_stats
-    bool traced = false;
-    bool frame_here = false;                 // d_color holds the last trace's whole frame
-    bool intensity_here = false;             // d_intensity holds its intensities
+    LastTrace last;
 
     // hipEvent rings: per build 6 events (before bounds, after bounds/morton/sort/karras/refit),
     // per trace 3 (before primary, after primary, after bounces)
@@ -212,47 +264,27 @@ struct rtbvh_ctx {
     Event evt[RING][5];             // trace start, primary done, end, first bounce traversal start/end
     bool evt_trav[RING] = {};
     uint32_t n_builds = 0, n_traces = 0;   // timed samples since reset
-    // Frames in flight (rtbvh_trace_band_async on a caller stream other than the context's):
-    // such a stream gets a trace-buffer set of its own -- slot k >= 1: d_qs[k], d_hits[k],
-    // the queue counts at d_qcount + 32k and the counters at d_counters + 64k -- so traces on
-    // different streams run concurrently over the one BVH.  They wait only for the last
-    // build (ev_built: the tree and every form marked valid in `tree` are complete, order_after_context); the
-    // next build waits for them (ev_slot).
-    hipStream_t slot_stream[MAXSPLIT] = {};   // (the callers' streams)
-    Event ev_built, ev_slot[MAXSPLIT];
-    bool slot_busy[MAXSPLIT] = {};
-    uint32_t last_slot = 0;   // slot of the last trace (its counters are the stats)
-    bool slots_used = false;  // a foreign-stream slot was used: trace chains are off
+    // ev_built: the tree and every form marked valid in `tree` are complete (order_after_context): what a trace
+    // or a query on a caller stream waits for
+    Event ev_built;
+    bool slots_used = false;  // a caller stream has a buffer set: trace chains are off
     // RTBVH_FLAG_GRAPH: the captured frame (build + trace) of rtbvh_compute_bvh and its key
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_key[5] = {};
     bool capturing = false;   // enqueueing into a capture: no event records
     uint64_t graph_captures = 0;
-    // host-side trace state of the captured frame, restored after every replay
-    struct TraceState {
-        uint32_t W, H, bounces, nsplit;
-        size_t rec_P;
-        uint32_t walk, walk_state;
-        bool cert;
-    } graph_state{};
-    Tree graph_tree;          // ... and the tree that frame leaves (its build's, with the forms its trace derived)
-    // RTBVH_FLAG_AUTO_WALK above AUTO_WALK_MAX_TRIS: the certified fast walks: per buffer
-    // set, the list of rays a pass re-traces in the reference order (their counts: d_qcount 16..31)
-    DevBuf<uint32_t> d_redo[MAXSPLIT];
-    size_t cap_redo[MAXSPLIT] = {};
-    DevBuf<uint32_t> d_defer[MAXSPLIT]; // the certified bounce walk's deferred rays (trace.hip DEFER_*), kept clean
-    size_t cap_defer[MAXSPLIT] = {};
-    uint64_t cert_traces = 0;                         // certified traces so far
-    uint32_t last_walk = 0;                           // walk flags of the last trace
-    uint32_t last_walk_state = 0;                     // rtbvh_stats.walk_state of the last trace
+    // host-side state of the captured frame, restored after every replay: its trace, and the tree it leaves
+    // (its build's, with the forms its trace derived)
+    LastTrace graph_trace;
+    Tree graph_tree;
+    uint64_t cert_traces = 0;                         // certified traces so far (DESIGN.md 3)
     // RTBVH_FLAG_AUTO_WALK at <= AUTO_WALK_MAX_TRIS: the primary kind, the reference order's lanes or its
     // wave packets (the same frame), timed on this scene and frame size (enqueue_trace)
     uint64_t small_key = 0;
     uint32_t small_flags = 0;     // the flags the small-scene primary kind was timed under
     bool small_packet = false;
     Event ev_small[2];            // its timing events (created on first use)
-    bool last_cert = false;                           // the last trace was certified (its re-trace counts)
     // tuning knobs of A/B runs, read once by rtbvh_create (RTBVH_BOUNCE_BLOCKS, RTBVH_OVERLAP,
     // RTBVH_SIDE_PRIORITY): a shipped context does not change its launches per frame
     uint32_t knob_bounce_blocks = 0;
@@ -273,11 +305,9 @@ struct rtbvh_ctx {
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
     DevBuf<uint32_t> d_qscratch;             // [QUERY_SCRATCH_WORDS]
-    DevBuf<uint32_t> d_qsort;                // RTBVH_QUERY_SORT: 6 arrays of cap_qsort words (keys and values: in,
-    DevBuf<uint32_t> d_qsort_scratch;        //   A, B), and the sort's digit counts; grown on demand
-    size_t cap_qsort = 0;
-    DevBuf<uint32_t> d_qredo;                // RTBVH_QUERY_CERTIFIED: the re-trace list, cap_qredo words; grown on demand
-    size_t cap_qredo = 0;
+    Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
+    Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
+    Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
     Event ev_query;
     bool query_busy = false;
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
@@ -301,6 +331,11 @@ rtbvh_status fail(rtbvh_ctx* c, rtbvh_status st, const std::string& msg) {
         if (_e != hipSuccess)                                                                    \
             return fail(ctx, _e == hipErrorOutOfMemory ? RTBVH_ERR_OOM : RTBVH_ERR_HIP,          \
                         std::string(#expr) + ": " + hipGetErrorString(_e));                      \
+    } while (0)
+// ... and of a step that has recorded its own failure
+#define TRY(expr)                                      \
+    do {                                               \
+        if (rtbvh_status _st = (expr)) return _st;     \
     } while (0)
 
 // A captured frame (RTBVH_FLAG_GRAPH) holds the device pointers of capture time: every
@@ -329,15 +364,14 @@ rtbvh_status check_launch(rtbvh_ctx* c, const char* what) {
 // ---- stream ordering ---------------------------------------------------------------------------------
 // The frames in flight on caller streams, drained on the host
 rtbvh_status drain_slots(rtbvh_ctx* c) {
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) HIPC(c, hipEventSynchronize(c->ev_slot[k]));
+    for (TraceSet& t : c->sets)
+        if (t.busy) HIPC(c, hipEventSynchronize(t.done));
     return RTBVH_OK;
 }
 // ... with the context stream and the ray queries: the one host drain
 rtbvh_status sync_all(rtbvh_ctx* c) {
     HIPC(c, hipStreamSynchronize(c->stream));
-    rtbvh_status st = drain_slots(c);
-    if (st) return st;
+    TRY(drain_slots(c));
     if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
     if (c->update_pending) HIPC(c, hipEventSynchronize(c->ev_update));   // (a vertex update on a caller stream)
     return RTBVH_OK;
@@ -345,10 +379,10 @@ rtbvh_status sync_all(rtbvh_ctx* c) {
 
 // The next writer of what the frames in flight read (a build: the BVH; a camera upload) on stream s waits for them
 rtbvh_status wait_slots(rtbvh_ctx* c, hipStream_t s) {
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->slot_busy[k]) {
-            HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
-            c->slot_busy[k] = false;
+    for (TraceSet& t : c->sets)
+        if (t.busy) {
+            HIPC(c, hipStreamWaitEvent(s, t.done, 0));
+            t.busy = false;
         }
     return RTBVH_OK;
 }
@@ -426,8 +460,8 @@ rtbvh_status ensure_trace_capacity(rtbvh_ctx* c, size_t P) {
     drop_graph(c);
     HIPC(c, c->d_color.alloc(P));
     HIPC(c, c->d_intensity.alloc(P));
-    HIPC(c, c->d_q[0].alloc(P));
-    HIPC(c, c->d_q[1].alloc(P));
+    HIPC(c, c->sets[0].q[0].alloc(P));
+    HIPC(c, c->sets[0].q[1].alloc(P));
     HIPC(c, c->d_bkin.alloc(P));
     HIPC(c, c->d_bvin.alloc(P));
     HIPC(c, c->d_bka.alloc(P));
@@ -435,10 +469,15 @@ rtbvh_status ensure_trace_capacity(rtbvh_ctx* c, size_t P) {
     HIPC(c, c->d_bkb.alloc(P));
     HIPC(c, c->d_bvb.alloc(P));
     HIPC(c, c->d_bscratch.alloc(sort_scratch_words((uint32_t)P)));
-    HIPC(c, c->d_hit.alloc(P));
+    HIPC(c, c->sets[0].hit.alloc(P));
     if (!c->d_qcount) HIPC(c, c->d_qcount.alloc(32 * rtbvh_ctx::MAXSPLIT));
     if (!c->d_next) HIPC(c, c->d_next.alloc((size_t)NEXT_WORDS * rtbvh_ctx::MAXSPLIT));
     if (!c->d_counters) HIPC(c, c->d_counters.alloc(64 * rtbvh_ctx::MAXSPLIT));
+    for (uint32_t b = 0; b < rtbvh_ctx::MAXSPLIT; b++) {   // (the blocks stay where they are from here on)
+        c->sets[b].qcount = c->d_qcount + 32 * b;
+        c->sets[b].next = c->d_next + (size_t)NEXT_WORDS * b;
+        c->sets[b].counters = c->d_counters + 64 * b;
+    }
     c->cap_P = P;
     return RTBVH_OK;
 }
@@ -450,36 +489,38 @@ uint32_t trace_split(const rtbvh_ctx* c) {
     return 1;
 }
 
-rtbvh_status ensure_split_capacity(rtbvh_ctx* c, uint32_t nsplit, size_t rays) {
-    if (nsplit < 2) return RTBVH_OK;
+// The sets 1 .. nsets - 1 (a trace's chains, or the caller streams' sets up to this trace's) with queues of `rays`
+// rays, and the chains' streams and events
+rtbvh_status ensure_split_capacity(rtbvh_ctx* c, uint32_t nsets, size_t rays) {
+    if (nsets < 2) return RTBVH_OK;
     const bool grow = rays > c->cap_split;
     if (grow) {
-        drop_graph(c);   // every chain's queues hold cap_split rays: drop the smaller ones
-        rtbvh_status st = drain_slots(c);   // (after any frame in flight on them)
-        if (st) return st;
+        drop_graph(c);   // every set's queues hold cap_split rays: drop the smaller ones
+        TRY(drain_slots(c));   // (after any frame in flight on them)
         c->cap_split = rays;
-        for (uint32_t g = nsplit; g < rtbvh_ctx::MAXSPLIT; g++) {
-            c->d_qs[g][0].reset(); c->d_qs[g][1].reset(); c->d_hits[g].reset();
+        for (uint32_t g = nsets; g < rtbvh_ctx::MAXSPLIT; g++) {
+            TraceSet& t = c->sets[g];
+            t.q[0].reset(); t.q[1].reset(); t.hit.reset();
         }
     }
-    for (uint32_t g = 1; g < nsplit; g++) {
-        if (!c->sub[g]) HIPC(c, hipStreamCreateWithFlags(c->sub[g].out(), hipStreamNonBlocking));
-        if (!c->ev_join[g]) HIPC(c, hipEventCreateWithFlags(c->ev_join[g].out(), hipEventDisableTiming));
+    for (uint32_t g = 1; g < nsets; g++) {
+        TraceSet& t = c->sets[g];
+        if (!t.chain) HIPC(c, hipStreamCreateWithFlags(t.chain.out(), hipStreamNonBlocking));
+        if (!t.join) HIPC(c, hipEventCreateWithFlags(t.join.out(), hipEventDisableTiming));
         if (!c->ev_fork) HIPC(c, hipEventCreateWithFlags(c->ev_fork.out(), hipEventDisableTiming));
-        if (c->d_qs[g][0] && !grow) continue;
-        HIPC(c, c->d_qs[g][0].alloc(c->cap_split));
-        HIPC(c, c->d_qs[g][1].alloc(c->cap_split));
-        HIPC(c, c->d_hits[g].alloc(c->cap_split));
+        if (t.q[0] && !grow) continue;
+        HIPC(c, t.q[0].alloc(c->cap_split));
+        HIPC(c, t.q[1].alloc(c->cap_split));
+        HIPC(c, t.hit.alloc(c->cap_split));
     }
     return RTBVH_OK;
 }
 
-// Binned primary buffers of buffer set b for T leaves and `tiles` screen tiles.  The bins hold
+// Binned primary buffers of a buffer set for T leaves and `tiles` screen tiles.  The bins hold
 // BINS_PER_LEAF entries per leaf (C5: 1.37 tiles per leaf); a tile whose bins would pass the end is
 // traced by the 4-wide packet walk instead (trace.hip pb_gate), so the capacity is a speed knob only.
 constexpr uint32_t BINS_PER_LEAF = 3;
-rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t tiles) {
-    rtbvh_ctx::PbBufs& p = c->pb[b];
+rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, PbBufs& p, uint32_t T, uint32_t tiles) {
     const uint32_t bins = BINS_PER_LEAF * T + 16 * tiles;
     if (T <= p.cap_T && tiles <= p.cap_tiles && bins <= p.cap_bins && p.off) return RTBVH_OK;
     drop_graph(c);
@@ -496,17 +537,19 @@ rtbvh_status ensure_pb_capacity(rtbvh_ctx* c, uint32_t b, uint32_t T, uint32_t t
     return RTBVH_OK;
 }
 
-// The bin set filled for `key`, if the context has one (rtbvh_ctx::PbBufs), or -1.  The key holds everything the bin
+// The buffer set whose bin set is filled for `key`, if the context has one, or -1.  The key holds everything the bin
 // passes and the scan read: the tree (bins_epoch: the leaf footprints and the root box's depth range, both written
 // by the build alone), T, the frame shape, the rank's rows and the band deal.  Not the camera: the passes read it only
 // through the footprints, which a camera upload without a build leaves as they are (the frame then still shows the
 // tree of the last build, whose clip-space triangles the walks read).  Not the walk flags, the counters or the
 // overflow word: no bin kernel reads them.  Never inside a capture: a captured frame holds its own bin passes, so
 // that its replay depends on no host state.
-int find_bins(const rtbvh_ctx* c, const rtbvh_ctx::PbKey& key) {
+int find_bins(const rtbvh_ctx* c, const PbKey& key) {
     if (!c->knob_bins_reuse || c->capturing) return -1;
-    for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++)
-        if (c->pb[k].valid && c->pb[k].off && c->pb[k].key == key) return (int)k;
+    for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++) {
+        const PbBufs& p = c->sets[k].pb;
+        if (p.valid && p.off && p.key == key) return (int)k;
+    }
     return -1;
 }
 
@@ -552,12 +595,6 @@ BuildArgs build_args(rtbvh_ctx* c) {
     const bool boxes = c->tree.wrote == NBOX;
     a.rec_on = boxes ? 0u : 1u;
     a.nbox = boxes ? c->d_nbox.h : nullptr;
-    return a;
-}
-// the same, with the node-box array for a kernel that reads (or writes) it
-BuildArgs build_args_nbox(rtbvh_ctx* c) {
-    BuildArgs a = build_args(c);
-    a.nbox = c->d_nbox;
     return a;
 }
 
@@ -626,8 +663,7 @@ rtbvh_status get_deal(rtbvh_ctx* c, uint32_t H, uint32_t nranks, const rtbvh_ctx
         }
     if (c->capturing) return fail(c, RTBVH_ERR_INVALID_ARG, "a new band deal inside a graph capture");
     if (c->deals.size() >= rtbvh_ctx::MAX_DEALS) {
-        rtbvh_status st = sync_all(c);
-        if (st) return st;
+        TRY(sync_all(c));
         c->deals.pop_back();
     }
     std::vector<uint32_t> owner;
@@ -730,7 +766,8 @@ bool records_skipped(const rtbvh_ctx* c) {
 // two); the leaf pseudo-records and the QNodes only when the context's walks at the build read none.
 rtbvh_status ensure_form(rtbvh_ctx* c, Form form, hipStream_t s) {
     if ((c->tree.valid & form) || !c->tree.built) return RTBVH_OK;
-    BuildArgs a = form == RECORDS || form == NBOX ? build_args_nbox(c) : build_args(c);
+    BuildArgs a = build_args(c);
+    if (form == RECORDS || form == NBOX) a.nbox = c->d_nbox;   // (the kernel reads, or writes, the node boxes)
     if (form == RECORDS) launch_records(a, c->stream);
     if (form == NBOX) {
         a.rec_on = 1;
@@ -818,60 +855,68 @@ const Rccl& rccl() {
 // camera in.
 rtbvh_status sync_camera(rtbvh_ctx* c, hipStream_t s) {
     if (!c->cam_dirty) return RTBVH_OK;
-    rtbvh_status st = wait_slots(c, c->stream);
-    if (st) return st;
+    TRY(wait_slots(c, c->stream));
     launch_set_camera(c->wvp, c->wv, c->d_cam, c->stream);
     HIPC(c, hipGetLastError());
     c->cam_dirty = false;
     return order_after_context(c, s);
 }
 
-// The kernels of one trace with the walks of `flags` (timed: record the stage events when
-// RTBVH_FLAG_TIMING asks for them).
-// cert: the certified walks (DESIGN.md 3; flags = the fast walks: binned primary pass, 4-wide bounce walk):
-// every pass checks each ray's certificate and re-traces the rays that fail it in the reference order.
-rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint32_t rank, uint32_t nranks,
-                           float4* color, float* inten, hipStream_t s, uint32_t slot, uint32_t flags, bool timed,
-                           bool cert = false) {
-    const bool leaf_pending = c->leaf_pending;   // (this trace is the first after the build or none is)
-    c->leaf_pending = false;
-    // the build's crossing nodes, if left to this trace: run in the binned pass's launches below, or
-    // before any walk (and on every early return) by the guard
-    struct TailGuard {
-        rtbvh_ctx* c;
-        bool pending;
-        void run() {
-            if (pending) launch_refit_tail(build_args(c), c->stream);
-            pending = false;
-        }
-        ~TailGuard() { run(); }
-    } tail{c, c->tail_pending};
-    c->tail_pending = false;
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
-    if (c->stale) return fail_stale(c, "trace");
-    if (W == 0 || H == 0 || nranks == 0 || rank >= nranks || bounces > 14)
-        return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
-    rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
-    if (st) return st;
-    if (!color) color = c->d_color;
-    const bool count = (c->cfg.flags & RTBVH_FLAG_COUNT_VISITS) != 0;
-    const bool timing = timed && (c->cfg.flags & RTBVH_FLAG_TIMING) != 0 && s == c->stream && !c->capturing;
-    TraceArgs a = trace_args(c, W, H, rank, nranks, color, inten);
-    const rtbvh_ctx::DealTab* deal = nullptr;
-    rtbvh_status dst = get_deal(c, H, nranks, &deal, s);
-    if (dst) return dst;
-    if (deal) {
-        a.my_bands = deal->off[rank + 1] - deal->off[rank];
-        a.band_list = deal->d + deal->off[rank];
-        a.band_slots = deal->d + (H + 7) / 8;
+// Stream s is about to rewrite the tree (a build, a refit, the replayed build of a captured frame): it waits for
+// the tree's readers -- the frames in flight, the outstanding ray queries -- for the last vertex update, whose
+// vertices and mesh box it reads, and for this frame's camera; from here on no bin set is of the tree (new
+// leaf footprints and depth range).
+rtbvh_status before_tree_write(rtbvh_ctx* c, hipStream_t s) {
+    TRY(wait_slots(c, s));
+    TRY(wait_queries(c, s));
+    TRY(wait_update(c, s));
+    TRY(sync_camera(c, s));
+    c->bins_epoch++;
+    return RTBVH_OK;
+}
+
+// The build's crossing nodes, if left to a trace (rtbvh_ctx::tail_pending): run in the trace's bin launches
+// (WalkPlan::fuse_tail), or before any walk reads the tree and on every early return by the guard
+struct TailGuard {
+    rtbvh_ctx* c;
+    bool pending;
+    void run() {
+        if (pending) launch_refit_tail(build_args(c), c->stream);
+        pending = false;
     }
-    a.counters = c->d_counters + 64 * slot;
-    Event* ev = c->evt[c->n_traces % rtbvh_ctx::RING];
-    const Walks wk = choose_walks(flags);
-    const bool sort = wk.sort, refill = wk.refill;
-    const bool records = (flags & RTBVH_FLAG_REFRACT_RECORDS) != 0;
-    if (records && slot) return fail(c, RTBVH_ERR_INVALID_ARG, "ray records are traced on the context stream only");
-    const uint32_t P = W * deal_rows(H, rank, nranks, c->root_share);   // max live rays of this shard
+    ~TailGuard() { run(); }
+};
+
+// What a trace launches and where: decided before anything is enqueued (plan_walks), read by prepare_walks
+// and launch_walks
+struct WalkPlan {
+    hipStream_t s;          // as asked: the trace's stream and buffer set,
+    uint32_t slot, bounces;
+    bool cert;
+    bool leaf_pending;      //   the first trace behind a build that recorded ev_leaf
+    bool count, timing, records;
+    Walks wk;
+    PrimaryKind pkind;
+    Form nodes;             // the node data its walks read
+    uint32_t P, rows;       // max live rays of this shard; its rows
+    uint32_t nsplit, Pg;    // chains; max live rays per chain
+    uint32_t tblocks;       // the bounce walk's persistent grid
+    uint32_t ntx, nty;      // the binned pass's tiles
+    bool inflight, fuse_tail, overlap, small_tiles, early_shade;
+    uint32_t bset;          // prepare_walks: the buffer set whose bin set the binned pass reads ...
+    bool fill_bins;         //   ... and fills first (its own)
+};
+
+WalkPlan plan_walks(const rtbvh_ctx* c, const TraceArgs& a, uint32_t bounces, hipStream_t s, uint32_t slot,
+                    uint32_t flags, bool cert, bool timed, bool tail_pending, bool leaf_pending) {
+    WalkPlan p{s, slot, bounces, cert, leaf_pending};
+    p.bset = slot;
+    p.count = (c->cfg.flags & RTBVH_FLAG_COUNT_VISITS) != 0;
+    p.timing = timed && (c->cfg.flags & RTBVH_FLAG_TIMING) != 0 && s == c->stream && !c->capturing;
+    p.wk = choose_walks(flags);
+    p.records = (flags & RTBVH_FLAG_REFRACT_RECORDS) != 0;
+    p.P = a.W * deal_rows(a.H, a.rank, a.nranks, c->root_share);
+    p.rows = p.P / a.W;
     // persistent grid of the bounce walk: 2048 blocks (8 waves/SIMD), 1024 for a shard of
     // < 4M pixels -- with frames in flight the next frame's primary blocks then share the CUs
     // (C5, rank of N=8, three frames in flight: 0.85 -> 0.78 ms per frame) -- and 512 below 3M pixels once
@@ -884,252 +929,275 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
 #endif
     // ("in flight": this trace is on a caller stream's slot, or another slot's frame is still running --
     // not a flag that stays set once any caller stream has traced: ADVICE r5)
-    bool inflight = slot != 0;
-    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT && !inflight && !c->capturing; k++)
-        inflight = c->slot_busy[k] && hipEventQuery(c->ev_slot[k]) == hipErrorNotReady;
-    uint32_t tblocks = P < (1u << 22) ? (!inflight ? 1536 : P < (3u << 20) ? 512 : 1024) : RTBVH_BOUNCE_GRID;
-    if (c->knob_bounce_blocks) tblocks = c->knob_bounce_blocks;   // tuning override (A/B runs)
-    if (records) {
-        if (c->cap_rec < P) {
+    p.inflight = slot != 0;
+    for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT && !p.inflight && !c->capturing; k++)
+        p.inflight = c->sets[k].busy && hipEventQuery(c->sets[k].done) == hipErrorNotReady;
+    p.tblocks = p.P < (1u << 22) ? (!p.inflight ? 1536 : p.P < (3u << 20) ? 512 : 1024) : RTBVH_BOUNCE_GRID;
+    if (c->knob_bounce_blocks) p.tblocks = c->knob_bounce_blocks;   // tuning override (A/B runs)
+    // chains: the rank's bands dealt round-robin over nsplit primary -> bounce chains (band k of this rank goes
+    // to chain k % nsplit), each with its own buffer set, chain 0 on the trace's stream, chain g on set g's;
+    // joined before the end event.  One chain where the buffers are not per set (the coherence sort's), where
+    // the sets are the caller streams', and for the binned primary pass, which covers the rank's whole frame.
+    // The build's leaf footprints are exact for frames of up to 32768 pixels a side (rtbvh_device.h
+    // leaf_footprint); a certified trace past that size: the reference-order lane walk, exact by construction
+    const bool binned = p.wk.primary == PrimaryKind::BINNED;
+    p.pkind = binned && (a.W > 32768u || a.H > 32768u)
+                  ? (cert ? PrimaryKind::LANE_REFERENCE : PrimaryKind::PACKET_WIDE)
+                  : p.wk.primary;
+    p.nsplit = trace_split(c);
+    if (p.wk.sort || a.my_bands < p.nsplit || slot || c->slots_used || binned) p.nsplit = 1;
+    p.Pg = p.nsplit == 1 ? p.P : a.W * 8 * ((a.my_bands + p.nsplit - 1) / p.nsplit);
+    // the walks' node data: a certified trace's re-traces walk the node boxes (TraceArgs::nb), every other walk
+    // the node records; a build writes one of the two, the other is derived from the complete tree (after the
+    // tail: prepare_walks), so only a trace that finds its form runs the build's crossing nodes in its bin launches
+    p.nodes = cert ? NBOX : RECORDS;
+    p.fuse_tail = tail_pending && p.pkind == PrimaryKind::BINNED && s == c->stream && slot == 0 && p.rows > 0 &&
+                  (c->tree.valid & p.nodes);
+    // rtbvh_compute_bvh: the binned pass (and the zeroing before it) on the side stream, concurrent
+    // with the build's crossing nodes (launch_refit_tail)
+    p.overlap = p.pkind == PrimaryKind::BINNED && leaf_pending && s == c->stream && slot == 0 && p.nsplit == 1;
+    p.ntx = pb_tiles_x(a.W);
+    p.nty = pb_tiles_y(p.rows);
+    // a rank's small pass one frame at a time: 512 threads a tile (its ~1,000 tiles all run at once;
+    // with frames in flight 256 is faster, round 5 r05_jj). Round 6 (r06_stl): the N = 8 rank's frame
+    // 1.13-1.15 -> 1.11 ms; N = 4 (2.1M pixels) the same, N = 2 (4.1M) +0.05 ms: below 1.5M pixels only
+    p.small_tiles = !p.inflight && !c->knob_no_small_tiles && (size_t)a.W * p.rows < (3u << 19);
+    // a frame one at a time shades its rays in the walk's tail (trace.hip RTBVH_EARLY_SHADE: one C5 frame
+    // 3.44-3.46 -> 3.37-3.40 ms); with frames in flight other frames' kernels fill that tail, and the
+    // shading workgroups cost the in-flight rate 1-3% (r06_x): not then
+    p.early_shade = cert && !p.inflight && !c->knob_no_early_shade;
+    return p;
+}
+
+// What the launches need before the first of them: capacities, the tree forms the walks read (behind the
+// build's crossing nodes), and the binned pass's bin set -- found, or the trace's own to be filled, ordered
+// behind the other sets' traces that still read it
+rtbvh_status prepare_walks(rtbvh_ctx* c, WalkPlan& p, TraceArgs& a, const rtbvh_ctx::DealTab* deal, TailGuard& tail) {
+    hipStream_t s = p.s;
+    TraceSet& mine = c->sets[p.slot];
+    const size_t P = p.P;
+    if (p.records) {
+        if (!(c->d_refl_rec.has(14 * P) && c->d_refr_rec.has(14 * P))) {
             drop_graph(c);
-            HIPC(c, c->d_refl_rec.alloc(14 * (size_t)P));
-            HIPC(c, c->d_refr_rec.alloc(14 * (size_t)P));
-            c->cap_rec = P;
+            HIPC(c, c->d_refl_rec.reserve(14 * P));
+            HIPC(c, c->d_refr_rec.reserve(14 * P));
         }
         a.refl_rec = c->d_refl_rec;
         a.refr_rec = c->d_refr_rec;
     }
-    c->rec_P = records ? P : 0;
-    // pipelines: the rank's bands dealt round-robin over nsplit primary -> bounce chains
-    // (band k of this rank goes to chain k % nsplit), each with its own queues and work
-    // counters, chain 0 on the context stream, chain g on sub[g]; joined before the end event
-    const uint32_t my_bands = a.my_bands;
-    uint32_t nsplit = trace_split(c);
-    // the coherence sort has one set of buffers; frames-in-flight slots use the chains' buffers
-    // the binned primary pass covers the rank's whole frame in one chain; the build's leaf footprints
-    // are exact for frames of up to 32768 pixels a side (rtbvh_device.h leaf_footprint)
-    const uint32_t rows = P / W;
-    const bool binned = wk.primary == PrimaryKind::BINNED;
-    // (a certified trace past that size: the reference-order lane walk, exact by construction)
-    const PrimaryKind pkind = binned && (W > 32768u || H > 32768u)
-                                  ? (cert ? PrimaryKind::LANE_REFERENCE : PrimaryKind::PACKET_WIDE)
-                                  : wk.primary;
-    if (sort || my_bands < nsplit || slot || c->slots_used || binned) nsplit = 1;
-    // the walks' node data: a certified trace's re-traces walk the node boxes (a.nb), every other walk the node
-    // records; a build writes one of the two, the other is derived here from the complete tree (after the tail)
-    const Form nodes = cert ? NBOX : RECORDS;
-    const bool need_conv = !(c->tree.valid & nodes);
-    const bool fuse_tail = tail.pending && pkind == PrimaryKind::BINNED && s == c->stream && slot == 0 && rows > 0 &&
-                           !need_conv;
-    if (!fuse_tail && tail.pending) {   // before any walk reads the tree
+    if (!p.fuse_tail && tail.pending) {   // before any walk reads the tree
         tail.run();
-        st = order_after_context(c, s);   // (a caller stream: ordered after it like after the build)
-        if (st) return st;
+        TRY(order_after_context(c, s));   // (a caller stream: ordered after it like after the build)
     }
-    st = ensure_form(c, nodes, s);
-    if (st) return st;
-    a.nb = cert;
-    const uint32_t Pg = nsplit == 1 ? P : W * 8 * ((my_bands + nsplit - 1) / nsplit);   // max live rays per chain
-    st = ensure_split_capacity(c, slot ? slot + 1 : nsplit, Pg);
-    if (st) return st;
+    TRY(ensure_form(c, p.nodes, s));
+    a.nb = p.cert;
+    TRY(ensure_split_capacity(c, p.slot ? p.slot + 1 : p.nsplit, p.Pg));
     // a 4-wide bounce walk over a one-workgroup build that quantized no nodes (the context's walks took none)
-    if (bounces > 0 && wk.refill && wk.bounce == BounceWalk::WIDE_QUANTIZED) {
-        st = ensure_form(c, QNODES, s);
-        if (st) return st;
-    }
+    if (p.bounces > 0 && p.wk.refill && p.wk.bounce == BounceWalk::WIDE_QUANTIZED) TRY(ensure_form(c, QNODES, s));
     // a packet walk over a tree built without the leaf pseudo-records (the context's walks took none;
     // set_flags since, or a frame past the binned pass's 32768 pixels a side)
-    if (pkind == PrimaryKind::PACKET_REFERENCE || pkind == PrimaryKind::PACKET_NEAREST ||
-        pkind == PrimaryKind::PACKET_WIDE) {
-        st = ensure_form(c, PSEUDO, s);
-        if (st) return st;
-    }
-    // a certified trace's re-trace list (one chain: buffer set `slot`; counts at d_qcount 16 + pass)
-    if (cert && bounces > 0 && c->cap_defer[slot] < P) {   // (zeroed once: its readers clear what they take)
+    if (p.pkind == PrimaryKind::PACKET_REFERENCE || p.pkind == PrimaryKind::PACKET_NEAREST ||
+        p.pkind == PrimaryKind::PACKET_WIDE)
+        TRY(ensure_form(c, PSEUDO, s));
+    // a certified trace's lists (one chain: the trace's own set)
+    if (p.cert && p.bounces > 0 && !mine.defer.has(P)) {   // (zeroed once: its readers clear what they take)
         drop_graph(c);
-        HIPC(c, c->d_defer[slot].alloc(P));
-        HIPC(c, hipMemsetAsync(c->d_defer[slot], 0, sizeof(uint32_t) * P, c->stream));
-        st = order_after_context(c, s);
-        if (st) return st;
-        c->cap_defer[slot] = P;
+        HIPC(c, mine.defer.reserve(P));
+        if (hipMemsetAsync(mine.defer, 0, sizeof(uint32_t) * P, c->stream) != hipSuccess) {
+            mine.defer.reset();   // (not clean: not kept)
+            return fail(c, RTBVH_ERR_HIP, "clearing the deferred-ray list failed");
+        }
+        TRY(order_after_context(c, s));
     }
-    if (cert && c->cap_redo[slot] < P) {
+    if (p.cert && !mine.redo.has(P)) {
         drop_graph(c);
-        HIPC(c, c->d_redo[slot].alloc(P));
-        c->cap_redo[slot] = P;
+        HIPC(c, mine.redo.reserve(P));
     }
-    // the binned pass's bin set (one chain): a set already filled for this tree and frame shape, or the buffer
-    // slot's own, filled by this trace (fill_bins)
-    const uint32_t ntx = pb_tiles_x(W), nty = pb_tiles_y(rows);
-    uint32_t bset = slot;
-    bool fill_bins = false;
-    if (pkind == PrimaryKind::BINNED && rows > 0) {
-        if (pb_keys_used() && (size_t)W * rows > c->cap_pbkeys[slot]) {   // (the slot's own, whichever the set)
-            drop_graph(c);
-            HIPC(c, c->d_pbkeys[slot].alloc((size_t)W * rows));
-            c->cap_pbkeys[slot] = (size_t)W * rows;
-        }
-        const rtbvh_ctx::PbKey key{c->bins_epoch, W, H, rows, rank, nranks, c->T, ntx, nty,
-                                   nranks > 1 ? c->root_share : 16u, deal ? deal->d.h : nullptr};
-        // (a trace that runs the build's crossing nodes in its count pass, or its pass beside them, is the first
-        // of its tree: it finds none)
-        const int found = fuse_tail || leaf_pending ? -1 : find_bins(c, key);
-        if (found >= 0) {
-            bset = (uint32_t)found;
-            rtbvh_ctx::PbBufs& p = c->pb[bset];
-            if (bset != slot) HIPC(c, hipStreamWaitEvent(s, p.filled, 0));   // (its own slot's: stream order)
-            p.readers |= 1u << slot;
-        } else {
-            fill_bins = true;
-            st = ensure_pb_capacity(c, slot, c->T, ntx * nty);
-            if (st) return st;
-            rtbvh_ctx::PbBufs& p = c->pb[slot];
-            if (nranks > 1 && p.cap_list < pb_list_words(c->T)) {
-                drop_graph(c);
-                HIPC(c, p.list.alloc(pb_list_words(c->T)));
-                p.cap_list = pb_list_words(c->T);
-            }
-            // the traces of other buffer slots that read what the set held (the same tree at another frame
-            // shape, rank or deal -- a new tree's build has waited for them all) end before this one overwrites
-            // it: stream-side, on their slot events, or the context stream's work so far for slot 0's.  Not
-            // inside a capture (no frame in flight outlives the wait_slots before every replay)
-            for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT && !c->capturing; k++) {
-                if (k == slot || !(p.readers & 1u << k)) continue;
-                if (k == 0) st = order_after_context(c, s);
-                else if (c->ev_slot[k]) HIPC(c, hipStreamWaitEvent(s, c->ev_slot[k], 0));
-                if (st) return st;
-            }
-            p.readers = 1u << slot;
-            p.valid = false;   // (until the fill is enqueued, below)
-            p.key = key;
-        }
+    if (p.pkind != PrimaryKind::BINNED || p.rows == 0) return RTBVH_OK;
+    // the binned pass's bin set (one chain): a set already filled for this tree and frame shape, or the trace's
+    // own, filled by this trace (fill_bins)
+    const size_t px = (size_t)a.W * p.rows;
+    if (pb_keys_used() && !mine.pbkeys.has(px)) {   // (the trace's own, whichever the bin set)
+        drop_graph(c);
+        HIPC(c, mine.pbkeys.reserve(px));
     }
-    // the trace's counters, queue counts, bounce work counters and bin counts: one launch
-    ZeroList z{};
-    z.ptr[0] = reinterpret_cast<uint32_t*>(a.counters);
+    const PbKey key{c->bins_epoch, a.W, a.H, p.rows, a.rank, a.nranks, c->T, p.ntx, p.nty,
+                    a.nranks > 1 ? c->root_share : 16u, deal ? deal->d.h : nullptr};
+    // (a trace that runs the build's crossing nodes in its count pass, or its pass beside them, is the first
+    // of its tree: it finds none)
+    const int found = p.fuse_tail || p.leaf_pending ? -1 : find_bins(c, key);
+    if (found >= 0) {
+        p.bset = (uint32_t)found;
+        PbBufs& pb = c->sets[p.bset].pb;
+        if (p.bset != p.slot) HIPC(c, hipStreamWaitEvent(s, pb.filled, 0));   // (its own set's: stream order)
+        pb.readers |= 1u << p.slot;
+        return RTBVH_OK;
+    }
+    p.fill_bins = true;
+    PbBufs& pb = mine.pb;
+    TRY(ensure_pb_capacity(c, pb, c->T, p.ntx * p.nty));
+    if (a.nranks > 1 && !pb.list.has(pb_list_words(c->T))) {
+        drop_graph(c);
+        HIPC(c, pb.list.reserve(pb_list_words(c->T)));
+    }
+    // the traces of other buffer sets that read what the bin set held (the same tree at another frame shape,
+    // rank or deal -- a new tree's build has waited for them all) end before this one overwrites it:
+    // stream-side, on their sets' events, or the context stream's work so far for set 0's.  Not inside a
+    // capture (no frame in flight outlives the wait_slots before every replay)
+    for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT && !c->capturing; k++) {
+        if (k == p.slot || !(pb.readers & 1u << k)) continue;
+        if (k == 0) TRY(order_after_context(c, s));
+        else if (c->sets[k].done) HIPC(c, hipStreamWaitEvent(s, c->sets[k].done, 0));
+    }
+    pb.readers = 1u << p.slot;
+    pb.valid = false;   // (until the fill is enqueued: launch_walks)
+    pb.key = key;
+    return RTBVH_OK;
+}
+
+// The launches: one zeroing of the trace's counters, queue counts, bounce work counters and bin counts, then
+// per chain the primary pass and the bounce passes
+rtbvh_status launch_walks(rtbvh_ctx* c, const WalkPlan& p, const TraceArgs& a, TailGuard& tail) {
+    hipStream_t s = p.s;
+    TraceSet& mine = c->sets[p.slot];   // the trace's set: chain 0's, and all that a one-chain trace uses
+    const uint32_t bounces = p.bounces, nsplit = p.nsplit;
+    const bool count = p.count, cert = p.cert, refill = p.wk.refill;
+    Event* ev = c->evt[c->n_traces % rtbvh_ctx::RING];
+    ZeroList z{};   // (a trace's chains use consecutive sets: their parts of the shared blocks are consecutive)
+    z.ptr[0] = reinterpret_cast<uint32_t*>(mine.counters);
     z.words[0] = 64 * 2;
-    z.ptr[1] = c->d_qcount + 32 * slot;
+    z.ptr[1] = mine.qcount;
     z.words[1] = 32 * nsplit;
     if (refill && bounces) {
-        z.ptr[2] = c->d_next + (size_t)NEXT_WORDS * slot;
+        z.ptr[2] = mine.next;
         z.words[2] = (size_t)NEXT_WORDS * nsplit;
     }
-    if (fill_bins) {
-        z.ptr[3] = c->pb[slot].off;
-        z.words[3] = (size_t)ntx * nty * PB_NZ + 1;
-        if (nranks > 1) {   // the list counters
-            z.ptr[4] = c->pb[slot].list;
+    if (p.fill_bins) {
+        z.ptr[3] = mine.pb.off;
+        z.words[3] = (size_t)p.ntx * p.nty * PB_NZ + 1;
+        if (a.nranks > 1) {   // the list counters
+            z.ptr[4] = mine.pb.list;
             z.words[4] = (size_t)PB_LISTS * PB_LIST_STRIDE;
         }
     }
-    // rtbvh_compute_bvh: the binned pass (and the zeroing before it) on the side stream, concurrent
-    // with the build's crossing nodes (launch_refit_tail)
-    const bool overlap = pkind == PrimaryKind::BINNED && leaf_pending && s == c->stream && slot == 0 && nsplit == 1;
-    hipStream_t sp = s;
-    if (overlap) {
+    hipStream_t sp = s;   // the binned pass's stream
+    if (p.overlap) {
         sp = c->side;
         HIPC(c, hipStreamWaitEvent(sp, c->ev_leaf, 0));
     }
     launch_zero(z, sp);
-    if (timing) HIPC(c, hipEventRecord(ev[0], sp));
+    if (p.timing) HIPC(c, hipEventRecord(ev[0], sp));
     if (nsplit > 1) HIPC(c, hipEventRecord(c->ev_fork, s));
     for (uint32_t g = 0; g < nsplit; g++) {
-        hipStream_t sg = g ? c->sub[g] : s;
+        TraceSet& set = c->sets[p.slot + g];   // chain g's set
+        hipStream_t sg = g ? set.chain : s;
         if (g) HIPC(c, hipStreamWaitEvent(sg, c->ev_fork, 0));
         TraceArgs ag = a;
         ag.band0 = g;
         ag.bstep = nsplit;
-        ag.pb_list = fill_bins && nranks > 1 ? c->pb[slot].list : nullptr;   // (the bin passes': one chain)
-        const uint32_t b = g + slot;   // buffer set: chain g of the context stream's trace, or the slot
-        RayQ* q[2] = {b ? c->d_qs[b][0] : c->d_q[0], b ? c->d_qs[b][1] : c->d_q[1]};
-        float2* hit = b ? c->d_hits[b] : c->d_hit;
-        uint32_t* qc = c->d_qcount + 32 * b;
-        uint32_t* nx = c->d_next + (size_t)NEXT_WORDS * b;
-        const bool tg = timing && g == 0;   // stage events: chain 0's kernels
-        if (pkind == PrimaryKind::BINNED) {
-            rtbvh_ctx::PbBufs& pbb = c->pb[bset];
-            const PrimBins pb{pbb.off, pbb.cur, pbb.bins, c->d_pbkeys[b], pbb.sums, pbb.cap_bins, ntx, nty};
-            if (rows) {
+        ag.pb_list = p.fill_bins && a.nranks > 1 ? mine.pb.list : nullptr;   // (the bin passes': one chain)
+        RayQ* q[2] = {set.q[0], set.q[1]};
+        uint32_t* qc = set.qcount;
+        const bool tg = p.timing && g == 0;   // stage events: chain 0's kernels
+        if (p.pkind == PrimaryKind::BINNED) {   // (one chain: `mine`)
+            PbBufs& pbb = c->sets[p.bset].pb;
+            const PrimBins pb{pbb.off, pbb.cur, pbb.bins, mine.pbkeys, pbb.sums, pbb.cap_bins, p.ntx, p.nty};
+            if (p.rows) {
                 const BuildArgs ba = build_args(c);
-                const Redo rd{c->d_redo[b], &qc[16]};
-                // a rank's small pass one frame at a time: 512 threads a tile (its ~1,000 tiles all run at once;
-                // with frames in flight 256 is faster, round 5 r05_jj). Round 6 (r06_stl): the N = 8 rank's frame
-                // 1.13-1.15 -> 1.11 ms; N = 4 (2.1M pixels) the same, N = 2 (4.1M) +0.05 ms: below 1.5M pixels only
-                const bool small_tiles = !inflight && !c->knob_no_small_tiles && (size_t)W * rows < (3u << 19);
-                if (fill_bins) {
-                    launch_pb_bins(ag, pb, rows, true, overlap ? sp : sg, fuse_tail ? &ba : nullptr);
+                const Redo rd{mine.redo, &qc[16]};
+                if (p.fill_bins) {
+                    launch_pb_bins(ag, pb, p.rows, true, sp, p.fuse_tail ? &ba : nullptr);
                     c->bin_builds++;
                     // the set is this key's from here on, for every later trace (they wait for `filled`); a
                     // captured fill is the graph's own, rewritten by every replay
                     if (c->knob_bins_reuse && !c->capturing) {
                         if (!pbb.filled) HIPC(c, hipEventCreateWithFlags(pbb.filled.out(), hipEventDisableTiming));
-                        HIPC(c, hipEventRecord(pbb.filled, overlap ? sp : sg));
+                        HIPC(c, hipEventRecord(pbb.filled, sp));
                         pbb.valid = true;
                     }
                 }
-                launch_pb_raster(ag, pb, rows, q[0], &qc[0], count, bounces > 0, overlap ? sp : sg,
-                                 cert ? &rd : nullptr, small_tiles);
-                if (fuse_tail) tail.pending = false;
-                if (overlap) {
-                    HIPC(c, hipEventRecord(c->ev_prim, sp));
-                    HIPC(c, hipStreamWaitEvent(sg, c->ev_prim, 0));
-                }
-                launch_pb_gate(ag, pb, q[0], &qc[0], count, bounces > 0, sg, cert);
-            } else if (overlap) {   // (nothing traced: the zeroing still joins)
+                launch_pb_raster(ag, pb, p.rows, q[0], &qc[0], count, bounces > 0, sp, cert ? &rd : nullptr,
+                                 p.small_tiles);
+                if (p.fuse_tail) tail.pending = false;
+            }
+            if (p.overlap) {   // (with nothing traced, the zeroing still joins)
                 HIPC(c, hipEventRecord(c->ev_prim, sp));
                 HIPC(c, hipStreamWaitEvent(sg, c->ev_prim, 0));
             }
+            if (p.rows) launch_pb_gate(ag, pb, q[0], &qc[0], count, bounces > 0, sg, cert);
         } else
-            launch_primary(ag, q[0], &qc[0], count, bounces > 0, pkind, sg);
+            launch_primary(ag, q[0], &qc[0], count, bounces > 0, p.pkind, sg);
         if (tg) HIPC(c, hipEventRecord(ev[1], sg));
         for (uint32_t b = 0; b < bounces; b++) {
             const uint32_t* perm = nullptr;
-            if (sort) {
-                launch_bounce_keys(q[b & 1], &qc[b], c->d_rootbox, P, c->d_bkin, c->d_bvin, sg);
-                perm = radix_sort_pairs(c->d_bkin, c->d_bvin, c->d_bka, c->d_bva, c->d_bkb, c->d_bvb, P, 30,
+            if (p.wk.sort) {
+                launch_bounce_keys(q[b & 1], &qc[b], c->d_rootbox, p.P, c->d_bkin, c->d_bvin, sg);
+                perm = radix_sort_pairs(c->d_bkin, c->d_bvin, c->d_bka, c->d_bva, c->d_bkb, c->d_bvb, p.P, 30,
                                         c->d_bscratch, sg).vals;
             }
             if (refill) {
                 if (tg && b == 0) HIPC(c, hipEventRecord(ev[3], sg));
-                uint32_t* nxb = nx + (size_t)NEXT_SEGS * NEXT_STRIDE * b;
-                // a frame one at a time shades its rays in the walk's tail (trace.hip RTBVH_EARLY_SHADE: one C5 frame
-                // 3.44-3.46 -> 3.37-3.40 ms); with frames in flight other frames' kernels fill that tail, and the
-                // shading workgroups cost the in-flight rate 1-3% (r06_x): not then
-                const BounceShade es{q[(b + 1) & 1], &qc[b + 1], b + 1 < bounces, c->d_redo[slot], &qc[17 + b], Pg};
-                launch_bounce_traverse(ag, q[b & 1], &qc[b], perm, count, wk.bounce, hit, nxb, tblocks, sg, cert,
-                                       c->d_defer[slot], cert && !inflight && !c->knob_no_early_shade ? &es : nullptr);
+                uint32_t* nxb = set.next + (size_t)NEXT_SEGS * NEXT_STRIDE * b;
+                const BounceShade es{q[(b + 1) & 1], &qc[b + 1], b + 1 < bounces, mine.redo, &qc[17 + b], p.Pg};
+                launch_bounce_traverse(ag, q[b & 1], &qc[b], perm, count, p.wk.bounce, set.hit, nxb, p.tblocks, sg, cert,
+                                       mine.defer, p.early_shade ? &es : nullptr);
                 if (tg && b == 0) HIPC(c, hipEventRecord(ev[4], sg));
-                const Redo rd{c->d_redo[slot], &qc[17 + b], c->d_defer[slot], nxb};
-                launch_bounce_shade(ag, q[b & 1], &qc[b], hit, q[(b + 1) & 1], &qc[b + 1], count, b + 1 < bounces,
-                                    Pg, sg, cert ? &rd : nullptr);
+                const Redo rd{mine.redo, &qc[17 + b], mine.defer, nxb};
+                launch_bounce_shade(ag, q[b & 1], &qc[b], set.hit, q[(b + 1) & 1], &qc[b + 1], count, b + 1 < bounces,
+                                    p.Pg, sg, cert ? &rd : nullptr);
             } else
                 launch_bounce(ag, q[b & 1], &qc[b], perm, q[(b + 1) & 1], &qc[b + 1], count, b + 1 < bounces,
-                              wk.nearest, sg);
+                              p.wk.nearest, sg);
         }
         if (g) {
-            HIPC(c, hipEventRecord(c->ev_join[g], sg));
-            HIPC(c, hipStreamWaitEvent(s, c->ev_join[g], 0));
+            HIPC(c, hipEventRecord(set.join, sg));
+            HIPC(c, hipStreamWaitEvent(s, set.join, 0));
         }
     }
-    // a snapshot of the overflow word for this stream's slot (rtbvh_synchronize reports a change)
-    HIPC(c, hipMemcpyAsync(c->h_ovf + slot, c->d_ovf, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    c->nsplit = nsplit;
-    c->last_slot = slot;
-    if (timing) {
+    // a snapshot of the overflow word for this trace's set (rtbvh_synchronize reports a change)
+    HIPC(c, hipMemcpyAsync(mine.ovf, c->d_ovf, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (p.timing) {
         HIPC(c, hipEventRecord(ev[2], s));
         c->evt_trav[c->n_traces % rtbvh_ctx::RING] = refill && bounces > 0;
         c->n_traces++;
     }
-    c->W = W;
-    c->H = H;
-    c->bounces = bounces;
-    c->rank = rank;
-    c->nranks = nranks;
-    c->traced = true;
-    c->frame_here = color == c->d_color && nranks == 1;
-    c->intensity_here = c->frame_here && inten != nullptr;
-    c->last_walk = flags & WALK_FLAGS;
-    c->last_cert = cert;
+    return RTBVH_OK;
+}
+
+// The kernels of one trace with the walks of `flags` (timed: record the stage events when
+// RTBVH_FLAG_TIMING asks for them); walk_state: what rtbvh_stats.walk_state reports of it.
+// cert: the certified walks (DESIGN.md 3; flags = the fast walks: binned primary pass, 4-wide bounce walk):
+// every pass checks each ray's certificate and re-traces the rays that fail it in the reference order.
+rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces, uint32_t rank, uint32_t nranks,
+                           float4* color, float* inten, hipStream_t s, uint32_t slot, uint32_t flags, bool timed,
+                           uint32_t walk_state, bool cert = false) {
+    const bool leaf_pending = c->leaf_pending;   // (this trace is the first after the build or none is)
+    c->leaf_pending = false;
+    TailGuard tail{c, c->tail_pending};
+    c->tail_pending = false;
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
+    if (c->stale) return fail_stale(c, "trace");
+    if (W == 0 || H == 0 || nranks == 0 || rank >= nranks || bounces > 14)
+        return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
+    TRY(ensure_trace_capacity(c, (size_t)W * H));
+    if (!color) color = c->d_color;
+    TraceArgs a = trace_args(c, W, H, rank, nranks, color, inten);
+    const rtbvh_ctx::DealTab* deal = nullptr;
+    TRY(get_deal(c, H, nranks, &deal, s));
+    if (deal) {
+        a.my_bands = deal->off[rank + 1] - deal->off[rank];
+        a.band_list = deal->d + deal->off[rank];
+        a.band_slots = deal->d + (H + 7) / 8;
+    }
+    a.counters = c->sets[slot].counters;
+    if ((flags & RTBVH_FLAG_REFRACT_RECORDS) && slot)
+        return fail(c, RTBVH_ERR_INVALID_ARG, "ray records are traced on the context stream only");
+    WalkPlan p = plan_walks(c, a, bounces, s, slot, flags, cert, timed, tail.pending, leaf_pending);
+    TRY(prepare_walks(c, p, a, deal, tail));
+    TRY(launch_walks(c, p, a, tail));
+    const bool frame_here = color == c->d_color && nranks == 1;
+    c->last = LastTrace{true, W, H, bounces, rank, nranks, p.nsplit, slot, p.records ? p.P : 0, flags & WALK_FLAGS,
+                        walk_state, cert, frame_here, frame_here && inten != nullptr};
     return check_launch(c, "trace kernels");
 }
 
@@ -1167,10 +1235,8 @@ rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
                            float4* color, float* inten, hipStream_t s, uint32_t slot = 0) {
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "trace before build");
     if (c->stale) return fail_stale(c, "trace");
-    rtbvh_status st = sync_camera(c, s);
-    if (st) return st;
+    TRY(sync_camera(c, s));
     TracePlan p = plan_trace(c, c->cfg.flags);
-    c->last_walk_state = p.state;
     if (p.cert && !c->capturing) c->cert_traces++;
     // AUTO_WALK on a small scene: the reference order, as one-ray-per-lane walks or as wave packets (the
     // same frame: both are the exact findCollision DFS per ray).  Which is faster depends on the scene
@@ -1196,9 +1262,8 @@ rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
             for (int round = 0; round < 2; round++)
                 for (int k = 0; k < 2; k++) {
                     HIPC(c, hipEventRecord(ev[0], s));
-                    rtbvh_status cs = enqueue_walks(c, W, H, 0, 0, 1, color, inten, s, 0,
-                                                    p.flags | (k ? RTBVH_FLAG_PACKET_PRIMARY : 0u), false);
-                    if (cs) return cs;
+                    TRY(enqueue_walks(c, W, H, 0, 0, 1, color, inten, s, 0,
+                                      p.flags | (k ? RTBVH_FLAG_PACKET_PRIMARY : 0u), false, p.state));
                     HIPC(c, hipEventRecord(ev[1], s));
                     HIPC(c, hipEventSynchronize(ev[1]));
                     float ms = 0.f;
@@ -1211,7 +1276,7 @@ rtbvh_status enqueue_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
         }
         if (c->small_key == key && c->small_flags == fw && c->small_packet) p.flags |= RTBVH_FLAG_PACKET_PRIMARY;
     }
-    return enqueue_walks(c, W, H, bounces, rank, nranks, color, inten, s, slot, p.flags, true, p.cert);
+    return enqueue_walks(c, W, H, bounces, rank, nranks, color, inten, s, slot, p.flags, true, p.state, p.cert);
 }
 
 }  // namespace
@@ -1281,6 +1346,7 @@ rtbvh_status rtbvh_create(const rtbvh_config* cfg, rtbvh_ctx** out) {
         return fail(nullptr, RTBVH_ERR_OOM, "overflow counter allocation failed");
     }
     memset(c->h_ovf, 0, sizeof(unsigned long long) * rtbvh_ctx::MAXSPLIT);
+    for (uint32_t b = 0; b < rtbvh_ctx::MAXSPLIT; b++) c->sets[b].ovf = c->h_ovf + b;
     if (c->d_cam.alloc(32) != hipSuccess ||
         hipMemset(c->d_cam, 0, 32 * sizeof(float)) != hipSuccess) {
         rtbvh_destroy(c);
@@ -1326,8 +1392,7 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
     for (uint32_t t = 0; t < T; t++)
         if (mat_idx[t] >= nmats) return fail(c, RTBVH_ERR_INVALID_ARG, "set_scene: material index out of range");
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status st = sync_all(c);   // frames in flight and ray queries on caller streams read the old scene and BVH
-    if (st) return st;
+    TRY(sync_all(c));   // frames in flight and ray queries on caller streams read the old scene and BVH
     c->query_busy = false;
     reset_tree(c);
     try {
@@ -1373,16 +1438,14 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
     c->V = nverts;
     c->T = T;
     c->nmat = nmats;
-    st = ensure_build_capacity(c, T);
-    if (st) return st;
+    TRY(ensure_build_capacity(c, T));
     if (c->cfg.morton_mode == RTBVH_MORTON_CPUTESTS) {
         // the object-space mesh box the CPUTests Morton codes are normalised by: a property of
         // the scene, computed once after loading as ShaderSim does (ShaderSim/main.cpp:277-285),
         // not per build (it does not depend on the camera)
         BuildArgs a = build_args(c);
         launch_bounds(a, c->stream);
-        st = check_launch(c, "mesh bounds");
-        if (st) return st;
+        TRY(check_launch(c, "mesh bounds"));
         HIPC(c, hipStreamSynchronize(c->stream));
     }
     c->have_scene = true;
@@ -1404,19 +1467,17 @@ rtbvh_status rtbvh_set_camera(rtbvh_ctx* c, const float wvp[16], const float wv[
     return RTBVH_OK;
 }
 
-rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
-    if (!c) return RTBVH_ERR_INVALID_ARG;
+// What a build leaves to the trace behind it (rtbvh_compute_bvh's frame): LEAF_EVENT: it records ev_leaf once the
+// leaves are written (rtbvh_ctx::leaf_pending); TAIL_TO_TRACE: it leaves its crossing nodes to the trace's bin
+// launches (tail_pending; flush_tail if no trace takes them)
+enum Handoff : uint32_t { LEAF_EVENT = 1, TAIL_TO_TRACE = 2 };
+static rtbvh_status build_tree(rtbvh_ctx* c, uint32_t handoff) {
     if (!c->have_scene || !c->have_camera) return fail(c, RTBVH_ERR_NOT_READY, "build before set_scene/set_camera");
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     const bool timing = (c->cfg.flags & RTBVH_FLAG_TIMING) != 0 && !c->capturing;
     BuildArgs a = build_args(c);
-    rtbvh_status cst = wait_slots(c, s);   // frames in flight read the old BVH
-    if (!cst) cst = wait_queries(c, s);    // ... and so do the outstanding ray queries
-    if (!cst) cst = wait_update(c, s);     // the vertices and the mesh box of the last update
-    if (!cst) cst = sync_camera(c, s);
-    if (cst) return cst;
-    c->bins_epoch++;   // new leaf footprints and depth range from here on: no bin set is of this tree
+    TRY(before_tree_write(c, s));
     const bool clz64 = c->cfg.delta_mode == RTBVH_DELTA_CLZ64;
     Event* ev = c->evb[c->n_builds % rtbvh_ctx::RING];
     if (timing) HIPC(c, hipEventRecord(ev[0], s));
@@ -1468,7 +1529,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     // after the leaves (ev_leaf)
     launch_refit_leaves(a, s);
     c->leaf_pending = false;
-    if (c->leaf_want) {
+    if (handoff & LEAF_EVENT) {
         if (!c->side) {   // high priority: its workgroups go first while the crossing nodes' fill the CUs
             int lo = 0, hi = 0;
             HIPC(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -1480,7 +1541,7 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
         HIPC(c, hipEventRecord(c->ev_leaf, s));
         c->leaf_pending = true;
     }
-    if (c->tail_want && !c->leaf_pending) c->tail_pending = true;   // (the trace runs it: launch_pb_bin_tail)
+    if ((handoff & TAIL_TO_TRACE) && !c->leaf_pending) c->tail_pending = true;   // (the trace runs it: launch_pb_bin_tail)
     else launch_refit_tail(a, s);
     if (timing) HIPC(c, hipEventRecord(ev[5], s));
     if (timing) c->n_builds++;
@@ -1491,23 +1552,22 @@ rtbvh_status rtbvh_build_async(rtbvh_ctx* c) {
     return check_launch(c, "build kernels");
 }
 
+rtbvh_status rtbvh_build_async(rtbvh_ctx* c) { return c ? build_tree(c, 0) : RTBVH_ERR_INVALID_ARG; }
+
 rtbvh_status rtbvh_build(rtbvh_ctx* c) {
-    rtbvh_status st = rtbvh_build_async(c);
-    if (st) return st;
+    TRY(rtbvh_build_async(c));
     return rtbvh_synchronize(c);
 }
 
 rtbvh_status rtbvh_trace_async(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
-    if (st) return st;
+    TRY(ensure_trace_capacity(c, (size_t)W * H));
     return enqueue_trace(c, W, H, bounces, 0, 1, c->d_color, c->d_intensity, c->stream);
 }
 
 rtbvh_status rtbvh_trace(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces) {
-    rtbvh_status st = rtbvh_trace_async(c, W, H, bounces);
-    if (st) return st;
+    TRY(rtbvh_trace_async(c, W, H, bounces));
     return rtbvh_synchronize(c);
 }
 
@@ -1526,7 +1586,12 @@ static rtbvh_status flush_tail(rtbvh_ctx* c, rtbvh_status st) {
     return st;
 }
 
-static bool side_overlap(const rtbvh_ctx* c) { return c->knob_overlap; }
+// rtbvh_compute_bvh's frame: the build hands its crossing nodes (and with RTBVH_OVERLAP its leaf event) to the trace
+static rtbvh_status enqueue_frame(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces) {
+    rtbvh_status st = build_tree(c, TAIL_TO_TRACE | (c->knob_overlap ? LEAF_EVENT : 0u));
+    if (!st) st = rtbvh_trace_async(c, W, H, bounces);
+    return flush_tail(c, st);
+}
 
 // RTBVH_FLAG_GRAPH: Graphics.cpp:56 rebuilds and traces every frame, ~20 launches and memsets
 // of little work each on the reference's own meshes; the frame is captured once into a
@@ -1541,22 +1606,12 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
                              (uint64_t)c->slots_used | (uint64_t)c->cfg.stack_limit << 1};
     if (!c->graph_exec || memcmp(key, c->graph_key, sizeof(key)) != 0) {
         drop_graph(c);
-        c->leaf_want = side_overlap(c);
-        c->tail_want = true;
-        rtbvh_status st = rtbvh_build_async(c);
-        c->leaf_want = c->tail_want = false;
-        if (!st) st = rtbvh_trace_async(c, W, H, bounces);
-        st = flush_tail(c, st);
+        rtbvh_status st = enqueue_frame(c, W, H, bounces);
         if (!st) st = rtbvh_synchronize(c);
         if (st && st != RTBVH_ERR_STACK_OVERFLOW) return st;
         HIPC(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         c->capturing = true;
-        c->leaf_want = side_overlap(c);
-        c->tail_want = true;
-        st = rtbvh_build_async(c);
-        c->leaf_want = c->tail_want = false;
-        if (!st) st = rtbvh_trace_async(c, W, H, bounces);
-        st = flush_tail(c, st);
+        st = enqueue_frame(c, W, H, bounces);
         hipGraph_t g = nullptr;
         const hipError_t e = hipStreamEndCapture(c->stream, &g);
         c->capturing = false;
@@ -1567,53 +1622,29 @@ static rtbvh_status compute_graph(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
         c->graph = g;
         HIPC(c, hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0));
         memcpy(c->graph_key, key, sizeof(key));
-        c->graph_state = rtbvh_ctx::TraceState{c->W,     c->H,         c->bounces,        c->nsplit,
-                                                c->rec_P, c->last_walk, c->last_walk_state, c->last_cert};
+        // (a whole frame into the framebuffer on the context stream: rank 0 of 1, set 0, frame and intensities here)
+        c->graph_trace = c->last;
         c->graph_tree = c->tree;   // (the forms the captured trace derived are in the graph too)
         c->graph_captures++;
     }
-    // the replayed build rewrites the BVH (and a split trace the slot queues): after the
-    // frames in flight on caller streams, as rtbvh_build_async
-    rtbvh_status cst = wait_slots(c, c->stream);
-    if (!cst) cst = wait_queries(c, c->stream);
-    if (!cst) cst = wait_update(c, c->stream);   // (the replayed build reads the updated vertices and mesh box)
-    if (!cst) cst = sync_camera(c, c->stream);   // this frame's camera, before the replay
-    if (cst) return cst;
+    // the replayed build rewrites the BVH and the bin set of the context stream's buffer set (the replayed
+    // trace fills it), with this frame's camera: as build_tree
+    TRY(before_tree_write(c, c->stream));
     HIPC(c, hipGraphLaunch(c->graph_exec, c->stream));
     HIPC(c, hipEventRecord(c->ev_built, c->stream));
     // the host-side state of the captured frame: its tree (the replayed build rewrote it for this camera, so
     // whatever was derived since belongs to the old one) and its trace (one in between may have changed it)
     c->tree = c->graph_tree;
     c->stale = false;
-    c->bins_epoch++;   // (the replayed build rewrote the footprints, the replayed trace the context stream's bin set)
-    const rtbvh_ctx::TraceState& g = c->graph_state;
-    c->W = g.W;
-    c->H = g.H;
-    c->bounces = g.bounces;
-    c->nsplit = g.nsplit;
-    c->rec_P = g.rec_P;
-    c->last_walk = g.walk;
-    c->last_walk_state = g.walk_state;
-    c->last_cert = g.cert;
-    if (g.cert) c->cert_traces++;
-    c->rank = 0;
-    c->nranks = 1;
-    c->last_slot = 0;
-    c->traced = true;
-    c->frame_here = c->intensity_here = true;
+    c->last = c->graph_trace;
+    if (c->last.cert) c->cert_traces++;
     return rtbvh_synchronize(c);
 }
 
 rtbvh_status rtbvh_compute_bvh(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounces) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     if (c->cfg.flags & RTBVH_FLAG_GRAPH) return compute_graph(c, W, H, bounces);
-    c->leaf_want = side_overlap(c);
-    c->tail_want = true;
-    rtbvh_status st = rtbvh_build_async(c);
-    c->leaf_want = c->tail_want = false;
-    if (st) return flush_tail(c, st);
-    st = flush_tail(c, rtbvh_trace_async(c, W, H, bounces));
-    if (st) return st;
+    TRY(enqueue_frame(c, W, H, bounces));
     return rtbvh_synchronize(c);
 }
 
@@ -1638,15 +1669,13 @@ rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* c, const float* dev_position
                                          uint32_t count, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     if (count == 0) return RTBVH_OK;
-    rtbvh_status st = check_update(c, dev_positions, pos_stride, dev_normals, nrm_stride, first, count);
-    if (st) return st;
+    TRY(check_update(c, dev_positions, pos_stride, dev_normals, nrm_stride, first, count));
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (!c->ev_update) HIPC(c, hipEventCreateWithFlags(c->ev_update.out(), hipEventDisableTiming));
-    st = wait_slots(c, s);
-    if (!st) st = order_after_context(c, s);
-    if (!st) st = wait_update(c, s);   // (an earlier update on another stream wrote the same buffers)
-    if (st) return st;
+    TRY(wait_slots(c, s));
+    TRY(order_after_context(c, s));
+    TRY(wait_update(c, s));   // (an earlier update on another stream wrote the same buffers)
     VertexUpdate u{};
     u.pos = dev_positions;
     u.pos_stride = pos_stride;
@@ -1659,7 +1688,7 @@ rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* c, const float* dev_position
     u.bounds = c->cfg.morton_mode == RTBVH_MORTON_CPUTESTS ? c->d_bounds.h : nullptr;
     u.V = c->V;
     launch_update_vertices(u, s);
-    st = check_launch(c, "vertex update");
+    const rtbvh_status st = check_launch(c, "vertex update");
     HIPC(c, hipEventRecord(c->ev_update, s));
     c->update_pending = true;
     c->stale = c->tree.built;
@@ -1670,8 +1699,7 @@ rtbvh_status rtbvh_update_vertices_host(rtbvh_ctx* c, const float* positions, ui
                                         const float* normals, uint32_t nrm_stride, uint32_t first, uint32_t count) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     if (count == 0) return RTBVH_OK;
-    rtbvh_status st = check_update(c, positions, pos_stride, normals, nrm_stride, first, count);
-    if (st) return st;
+    TRY(check_update(c, positions, pos_stride, normals, nrm_stride, first, count));
     HIPC(c, hipSetDevice(c->cfg.device));
     // the arrays as they are, strides included: the last vertex's three floats end each
     const size_t np = (size_t)(count - 1) * pos_stride + 3, nn = normals ? (size_t)(count - 1) * nrm_stride + 3 : 0;
@@ -1679,8 +1707,7 @@ rtbvh_status rtbvh_update_vertices_host(rtbvh_ctx* c, const float* positions, ui
     HIPC(c, d.alloc(np + nn));
     HIPC(c, hipMemcpy(d, positions, np * sizeof(float), hipMemcpyHostToDevice));
     if (normals) HIPC(c, hipMemcpy(d + np, normals, nn * sizeof(float), hipMemcpyHostToDevice));
-    st = rtbvh_update_vertices_async(c, d, pos_stride, normals ? d + np : nullptr, nrm_stride, first, count, nullptr);
-    if (st) return st;
+    TRY(rtbvh_update_vertices_async(c, d, pos_stride, normals ? d + np : nullptr, nrm_stride, first, count, nullptr));
     HIPC(c, hipStreamSynchronize(c->stream));   // (the staging buffer goes with this scope)
     return RTBVH_OK;
 }
@@ -1696,12 +1723,7 @@ rtbvh_status rtbvh_refit_async(rtbvh_ctx* c) {
     if (!c->have_scene || !c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "refit before build");
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    rtbvh_status st = wait_slots(c, s);   // frames in flight and ray queries read the old boxes
-    if (!st) st = wait_queries(c, s);
-    if (!st) st = wait_update(c, s);
-    if (!st) st = sync_camera(c, s);
-    if (st) return st;
-    c->bins_epoch++;   // new leaf footprints and depth range: no bin set is of this tree
+    TRY(before_tree_write(c, s));   // (frames in flight and ray queries read the old boxes)
     BuildArgs a = build_args(c);
     a.pseudo = a.rec_on && (c->tree.valid & PSEUDO) ? 1u : 0u;
     launch_clip(a, s);
@@ -1715,8 +1737,7 @@ rtbvh_status rtbvh_refit_async(rtbvh_ctx* c) {
 }
 
 rtbvh_status rtbvh_refit(rtbvh_ctx* c) {
-    rtbvh_status st = rtbvh_refit_async(c);
-    if (st) return st;
+    TRY(rtbvh_refit_async(c));
     return rtbvh_synchronize(c);
 }
 
@@ -1730,8 +1751,7 @@ rtbvh_status rtbvh_verify_walk(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     if (c->stale) return fail_stale(c, "verify_walk");
     if (W == 0 || H == 0 || bounces > 14) return fail(c, RTBVH_ERR_INVALID_ARG, "bad trace dimensions");
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status st = ensure_trace_capacity(c, (size_t)W * H);
-    if (st) return st;
+    TRY(ensure_trace_capacity(c, (size_t)W * H));
     const size_t n = (size_t)W * H;
     float4* ref = nullptr;
     unsigned long long* d_diff = nullptr;
@@ -1742,13 +1762,11 @@ rtbvh_status rtbvh_verify_walk(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     const uint32_t f = c->cfg.flags & ~RTBVH_FLAG_REFRACT_RECORDS;
     const uint32_t refw = f & ~(WALK_FLAGS | RTBVH_FLAG_AUTO_WALK);
     const TracePlan mine = plan_trace(c, f);
-    st = sync_camera(c, c->stream);
-    if (!st) st = enqueue_walks(c, W, H, bounces, 0, 1, ref, nullptr, c->stream, 0, refw, true);
-    if (!st) {
-        c->last_walk_state = mine.state;
+    rtbvh_status st = sync_camera(c, c->stream);
+    if (!st) st = enqueue_walks(c, W, H, bounces, 0, 1, ref, nullptr, c->stream, 0, refw, true, mine.state);
+    if (!st)
         st = enqueue_walks(c, W, H, bounces, 0, 1, c->d_color, c->d_intensity, c->stream, 0, mine.flags, true,
-                           mine.cert);
-    }
+                           mine.state, mine.cert);
     unsigned long long diff = 0;
     if (!st) {
         hipError_t e = hipMemsetAsync(d_diff, 0, sizeof(unsigned long long), c->stream);
@@ -1804,24 +1822,24 @@ rtbvh_status rtbvh_trace_band_async(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32
     HIPC(c, hipSetDevice(c->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     uint32_t slot = 0;
-    if (s != c->stream) {   // a frame in flight: this stream's buffer slot, after the last build
+    if (s != c->stream) {   // a frame in flight: this stream's buffer set, after the last build
         for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT && !slot; k++)
-            if (c->slot_stream[k] == s) slot = k;
+            if (c->sets[k].caller == s) slot = k;
         for (uint32_t k = 1; k < rtbvh_ctx::MAXSPLIT && !slot; k++)
-            if (!c->slot_stream[k]) {
-                c->slot_stream[k] = s;
+            if (!c->sets[k].caller) {
+                c->sets[k].caller = s;
                 slot = k;
             }
         if (!slot) return fail(c, RTBVH_ERR_INVALID_ARG, "more caller streams trace one context than it has slots");
-        if (!c->ev_slot[slot]) HIPC(c, hipEventCreateWithFlags(c->ev_slot[slot].out(), hipEventDisableTiming));
+        Event& done = c->sets[slot].done;
+        if (!done) HIPC(c, hipEventCreateWithFlags(done.out(), hipEventDisableTiming));
         c->slots_used = true;
         HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
     }
-    rtbvh_status st = enqueue_trace(c, W, H, bounces, rank, nranks, (float4*)dev_out, nullptr, s, slot);
-    if (st) return st;
+    TRY(enqueue_trace(c, W, H, bounces, rank, nranks, (float4*)dev_out, nullptr, s, slot));
     if (slot) {   // the next build (context stream) waits for this trace
-        HIPC(c, hipEventRecord(c->ev_slot[slot], s));
-        c->slot_busy[slot] = true;
+        HIPC(c, hipEventRecord(c->sets[slot].done, s));
+        c->sets[slot].busy = true;
     }
     return RTBVH_OK;
 }
@@ -1834,8 +1852,7 @@ rtbvh_status rtbvh_assemble_bands(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t
     HIPC(c, hipSetDevice(c->cfg.device));
     const rtbvh_ctx::DealTab* deal = nullptr;
     const hipStream_t as = stream ? (hipStream_t)stream : c->stream;
-    rtbvh_status st = get_deal(c, H, nranks, &deal, as);
-    if (st) return st;
+    TRY(get_deal(c, H, nranks, &deal, as));
     launch_assemble((const float4*)dev_bands, deal ? deal->d + (H + 7) / 8 : nullptr, stride_rows, W, H, nranks,
                     (float4*)dev_frame, as);
     return check_launch(c, "assemble bands");
@@ -1889,12 +1906,8 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     HIPC(c, hipSetDevice(c->cfg.device));
     const uint32_t rows0 = deal_max_rows(H, nranks, c->root_share);
     const size_t need = (size_t)(rank == 0 ? nranks : 1) * rows0 * W;
-    if (c->cap_band < need) {
-        HIPC(c, c->d_band.alloc(need));
-        c->cap_band = need;
-    }
-    rtbvh_status st = enqueue_trace(c, W, H, bounces, rank, nranks, c->d_band, nullptr, c->stream);
-    if (st) return st;
+    HIPC(c, c->d_band.reserve(need));
+    TRY(enqueue_trace(c, W, H, bounces, rank, nranks, c->d_band, nullptr, c->stream));
     const ncclComm_t cm = (ncclComm_t)comm;
     ncclResult_t e = r.GroupStart();
     if (rank != 0) {
@@ -1912,21 +1925,18 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
     if (e != ncclSuccess) return fail(c, RTBVH_ERR_COMM, std::string("band gather: ") + r.GetErrorString(e));
     if (rank == 0) {
         const rtbvh_ctx::DealTab* deal = nullptr;
-        st = get_deal(c, H, nranks, &deal, c->stream);
-        if (st) return st;
+        TRY(get_deal(c, H, nranks, &deal, c->stream));
         launch_assemble(c->d_band, deal ? deal->d + (H + 7) / 8 : nullptr, rows0, W, H, nranks, c->d_color,
                         c->stream);
-        st = check_launch(c, "assemble bands");
-        if (st) return st;
+        TRY(check_launch(c, "assemble bands"));
     }
-    c->frame_here = rank == 0;
+    c->last.frame_here = rank == 0;   // (assembled)
     return rtbvh_synchronize(c);
 }
 
 rtbvh_status rtbvh_synchronize(rtbvh_ctx* c) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    rtbvh_status st = sync_all(c);
-    if (st) return st;
+    TRY(sync_all(c));
     c->query_busy = false;
     // each trace ends by copying the never-reset overflow word into its slot's pinned word
     unsigned long long ovf = c->ovf_seen;
@@ -1953,18 +1963,19 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* c) {
 
 rtbvh_status rtbvh_read_framebuffer(rtbvh_ctx* c, float* rgba) {
     if (!c || !rgba) return RTBVH_ERR_INVALID_ARG;
-    if (!c->traced) return fail(c, RTBVH_ERR_NOT_READY, "no trace yet");
-    if (!c->frame_here) return fail(c, RTBVH_ERR_NOT_READY, "the last trace was a band trace: the frame is elsewhere");
+    if (!c->last.traced) return fail(c, RTBVH_ERR_NOT_READY, "no trace yet");
+    if (!c->last.frame_here)
+        return fail(c, RTBVH_ERR_NOT_READY, "the last trace was a band trace: the frame is elsewhere");
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipMemcpy(rgba, c->d_color, sizeof(float4) * (size_t)c->W * c->H, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(rgba, c->d_color, sizeof(float4) * (size_t)c->last.W * c->last.H, hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 
 rtbvh_status rtbvh_read_intensity(rtbvh_ctx* c, float* inten) {
     if (!c || !inten) return RTBVH_ERR_INVALID_ARG;
-    if (!c->traced || !c->intensity_here) return fail(c, RTBVH_ERR_NOT_READY, "no full-frame trace yet");
+    if (!c->last.traced || !c->last.intensity_here) return fail(c, RTBVH_ERR_NOT_READY, "no full-frame trace yet");
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipMemcpy(inten, c->d_intensity, sizeof(float) * (size_t)c->W * c->H, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(inten, c->d_intensity, sizeof(float) * (size_t)c->last.W * c->last.H, hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 
@@ -1992,12 +2003,13 @@ rtbvh_status rtbvh_read_bvh(rtbvh_ctx* c, rtbvh_node* out, uint32_t capacity) {
 
 rtbvh_status rtbvh_present(rtbvh_ctx* c, uint8_t* rgba8) {
     if (!c || !rgba8) return RTBVH_ERR_INVALID_ARG;
-    if (!c->traced || !c->frame_here) return fail(c, RTBVH_ERR_NOT_READY, "present: no full frame on this context");
+    if (!c->last.traced || !c->last.frame_here)
+        return fail(c, RTBVH_ERR_NOT_READY, "present: no full frame on this context");
     HIPC(c, hipSetDevice(c->cfg.device));
-    const size_t n = (size_t)c->W * c->H;
+    const size_t n = (size_t)c->last.W * c->last.H;
     uint32_t* d = nullptr;
     HIPC(c, hipMallocAsync((void**)&d, n * 4, c->stream));
-    launch_present(c->d_color, c->W, c->H, d, c->stream);
+    launch_present(c->d_color, c->last.W, c->last.H, d, c->stream);
     hipError_t e1 = hipGetLastError();
     hipError_t e2 = hipMemcpyAsync(rgba8, d, n * 4, hipMemcpyDeviceToHost, c->stream);
     hipError_t e3 = hipFreeAsync(d, c->stream);
@@ -2015,9 +2027,8 @@ rtbvh_status rtbvh_read_wide(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
     const size_t total = c->T > 1 ? 2 * (size_t)(c->T - 1) : 0;
     if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_wide: capacity < 2(n-1)");
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status rs = ensure_form(c, RECORDS, c->stream);   // (a certified-only build wrote node boxes instead)
-    if (!rs) rs = ensure_form(c, PSEUDO, c->stream);        // (binned / AUTO walks: a build without them)
-    if (rs) return rs;
+    TRY(ensure_form(c, RECORDS, c->stream));   // (a certified-only build wrote node boxes instead)
+    TRY(ensure_form(c, PSEUDO, c->stream));    // (binned / AUTO walks: a build without them)
     HIPC(c, hipStreamSynchronize(c->stream));
     if (total) HIPC(c, hipMemcpy(out, c->d_rec, total * sizeof(Inner), hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -2029,8 +2040,7 @@ rtbvh_status rtbvh_read_qnodes(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
     const size_t total = c->T > 1 ? 2 * (size_t)c->T - 1 : 0;
     if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_qnodes: capacity < 2n-1");
     HIPC(c, hipSetDevice(c->cfg.device));
-    rtbvh_status rs = ensure_form(c, QNODES, c->stream);
-    if (rs) return rs;
+    TRY(ensure_form(c, QNODES, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     if (total) HIPC(c, hipMemcpy(out, c->d_qnode, total * sizeof(QNode), hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -2055,11 +2065,11 @@ rtbvh_status rtbvh_read_sorted(rtbvh_ctx* c, uint32_t* keys, uint32_t* ids) {
 
 rtbvh_status rtbvh_read_rays(rtbvh_ctx* c, rtbvh_ray_present* reflect_out, rtbvh_ray_present* refract_out) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (!c->traced || c->rec_P == 0)
+    if (!c->last.traced || c->last.rec_P == 0)
         return fail(c, RTBVH_ERR_NOT_READY, "read_rays: the last trace ran without RTBVH_FLAG_REFRACT_RECORDS");
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = c->rec_P * sizeof(rtbvh_ray_present);
+    const size_t bytes = c->last.rec_P * sizeof(rtbvh_ray_present);
     if (reflect_out) HIPC(c, hipMemcpy(reflect_out, c->d_refl_rec, bytes, hipMemcpyDeviceToHost));
     if (refract_out) HIPC(c, hipMemcpy(refract_out, c->d_refr_rec, bytes, hipMemcpyDeviceToHost));
     return RTBVH_OK;
@@ -2071,8 +2081,10 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
     if (rtbvh_status st = sync_all(c)) return st;
     out->num_tris = c->T;
     out->num_nodes = c->T ? 2 * c->T - 1 : 0;
-    out->width = c->W;
-    out->height = c->H;
+    const LastTrace& t = c->last;
+    const TraceSet& set = c->sets[t.slot];   // the last trace's (chain 0's) set
+    out->width = t.W;
+    out->height = t.H;
     const uint32_t nb = c->n_builds < (uint32_t)rtbvh_ctx::RING ? c->n_builds : rtbvh_ctx::RING;
     for (uint32_t k = 0; k < nb; k++) {
         float ms;
@@ -2099,16 +2111,15 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
         }
     }
     out->timed_traces = nt;
-    if (c->traced && c->d_counters) {
+    if (t.traced && set.counters) {
         unsigned long long cnt[64];
-        uint32_t q[32 * rtbvh_ctx::MAXSPLIT];
-        HIPC(c, hipMemcpy(cnt, c->d_counters + 64 * c->last_slot, sizeof(cnt), hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(q, c->d_qcount + 32 * c->last_slot, sizeof(uint32_t) * 32 * c->nsplit,
-                          hipMemcpyDeviceToHost));
-        out->primary_rays = (uint64_t)c->W * deal_rows(c->H, c->rank, c->nranks, c->root_share);
+        uint32_t q[32 * rtbvh_ctx::MAXSPLIT];   // (its chains' sets follow it)
+        HIPC(c, hipMemcpy(cnt, set.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(q, set.qcount, sizeof(uint32_t) * 32 * t.nsplit, hipMemcpyDeviceToHost));
+        out->primary_rays = (uint64_t)t.W * deal_rows(t.H, t.rank, t.nranks, c->root_share);
         uint64_t b = 0;
-        for (uint32_t g = 0; g < c->nsplit; g++)
-            for (uint32_t k = 0; k < c->bounces; k++) b += q[32 * g + k];
+        for (uint32_t g = 0; g < t.nsplit; g++)
+            for (uint32_t k = 0; k < t.bounces; k++) b += q[32 * g + k];
         out->bounce_rays = b;
         for (int p = 0; p < 2; p++) {
             out->internal_visits[p] = cnt[2 + 3 * p];
@@ -2123,29 +2134,25 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
         for (int k = 0; k < 32; k++) out->trav_steps_log2[k] = cnt[32 + k];
         out->trav_mixed_steps = cnt[11];
         out->trav_active_lanes = cnt[12];
+        for (int p = 0; p < 2; p++) {
+            out->packet_steps[p] = cnt[14 + p];
+            out->bin_entries[p] = cnt[16 + p];
+        }
     }
     out->graph_captures = c->graph_captures;
-    if (c->traced && c->d_counters) {
-        unsigned long long w[4];
-        HIPC(c, hipMemcpy(w, c->d_counters + 64 * c->last_slot + 14, sizeof(w), hipMemcpyDeviceToHost));
-        out->packet_steps[0] = w[0];
-        out->packet_steps[1] = w[1];
-        out->bin_entries[0] = w[2];
-        out->bin_entries[1] = w[3];
-    }
-    out->walk_flags = c->last_walk;
-    out->walk_state = c->last_walk_state;
+    out->walk_flags = t.walk;
+    out->walk_state = t.walk_state;
     out->cert_traces = c->cert_traces;
-    if (c->traced && c->last_cert && c->d_qcount) {   // the last trace's re-trace counts (d_qcount 16..)
+    if (t.traced && t.cert && set.qcount) {   // the last trace's re-trace counts (qcount 16..)
         uint32_t q[32];
-        HIPC(c, hipMemcpy(q, c->d_qcount + 32 * c->last_slot, sizeof(q), hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(q, set.qcount, sizeof(q), hipMemcpyDeviceToHost));
         out->redo_rays[0] = q[16];
-        for (uint32_t k = 0; k < c->bounces && k < 15; k++) out->redo_rays[1] += q[17 + k];
+        for (uint32_t k = 0; k < t.bounces && k < 15; k++) out->redo_rays[1] += q[17 + k];
         // ... and the bounce walks' deferred rays (walked in the reference order by the walk or k_bounce_redo)
-        for (uint32_t k = 0; k < c->bounces && k < 15; k++) {
+        for (uint32_t k = 0; k < t.bounces && k < 15; k++) {
             uint32_t nd = 0;
-            HIPC(c, hipMemcpy(&nd, c->d_next + (size_t)NEXT_WORDS * c->last_slot + (size_t)NEXT_SEGS * NEXT_STRIDE * k +
-                                       DEFER_COUNT, sizeof(nd), hipMemcpyDeviceToHost));
+            HIPC(c, hipMemcpy(&nd, set.next + (size_t)NEXT_SEGS * NEXT_STRIDE * k + DEFER_COUNT, sizeof(nd),
+                              hipMemcpyDeviceToHost));
             out->redo_rays[1] += nd;
             out->redo_deferred += nd;
         }
@@ -2158,7 +2165,7 @@ uint64_t rtbvh_bin_builds(rtbvh_ctx* c) { return c ? c->bin_builds : 0; }
 
 uint32_t rtbvh_bin_sets(rtbvh_ctx* c) {
     uint32_t n = 0;
-    for (uint32_t k = 0; c && k < rtbvh_ctx::MAXSPLIT; k++) n += c->pb[k].bins ? 1u : 0u;
+    for (uint32_t k = 0; c && k < rtbvh_ctx::MAXSPLIT; k++) n += c->sets[k].pb.bins ? 1u : 0u;
     return n;
 }
 
@@ -2226,8 +2233,7 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     HIPC(c, hipSetDevice(c->cfg.device));
     if (c->ev_query) HIPC(c, hipEventSynchronize(c->ev_query));   // (the scene's BVH buffers are reused)
     c->query_busy = false;
-    rtbvh_status st = ensure_build_capacity(c, n);
-    if (st) return st;
+    TRY(ensure_build_capacity(c, n));
     DevBuf<float> d_boxes;
     DevBuf<rtbvh_node> d_out;
     HIPC(c, d_boxes.alloc((size_t)n * 6));
@@ -2244,7 +2250,7 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     a.nbox = nullptr;
     launch_from_codes(a, d_boxes, c->stream);
     launch_export(a, d_out, c->stream);
-    st = check_launch(c, "build_from_codes kernels");
+    const rtbvh_status st = check_launch(c, "build_from_codes kernels");
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (st) return st;
     HIPC(c, e);
@@ -2278,26 +2284,20 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     const bool cert = (mode & RTBVH_QUERY_CERTIFIED) != 0 && c->tree.clz64 && !limited;
     if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_SCRATCH_WORDS));
     if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && (n > c->cap_qsort || !c->d_qsort)) {
+    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
         // earlier queries sort in the old buffers: the first RTBVH_QUERY_SORT query and each larger one wait
         // for them on the host here (and hipMalloc blocks too), as include/rtbvh.h says
         HIPC(c, hipEventSynchronize(c->ev_query));
-        c->cap_qsort = 0;
-        HIPC(c, c->d_qsort.alloc(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.alloc(sort_scratch_words(N)));
-        c->cap_qsort = n;
+        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
     }
-    if (cert && (n > c->cap_qredo || !c->d_qredo)) {   // (earlier queries list in the old buffer: as the sort's)
+    if (cert && !c->d_qredo.has((size_t)n)) {   // (earlier queries list in the old buffer: as the sort's)
         HIPC(c, hipEventSynchronize(c->ev_query));
-        c->cap_qredo = 0;
-        HIPC(c, c->d_qredo.alloc((size_t)n));
-        c->cap_qredo = n;
+        HIPC(c, c->d_qredo.reserve((size_t)n));
     }
     if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (cert) {   // the QNodes of a build that wrote none, derived once (behind the earlier queries: none reads them)
-        const rtbvh_status qs = ensure_form(c, QNODES, s);
-        if (qs) return qs;
-    }
+    // the QNodes of a build that wrote none, derived once (behind the earlier queries: none reads them)
+    if (cert) TRY(ensure_form(c, QNODES, s));
     if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
     // the work counters; behind them a counting query's count block and walk counts, a certified query's list
     // length and its re-trace's work counters
@@ -2329,7 +2329,7 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
     if (sort) {
         uint32_t* q = c->d_qsort;
-        const size_t m = c->cap_qsort;
+        const size_t m = c->d_qsort.cap / 6;
         launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
         a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
     }
@@ -2357,8 +2357,7 @@ rtbvh_status rtbvh_query_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, r
     rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d + (size_t)n * sizeof(rtbvh_ray));
     if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
         return fail(c, RTBVH_ERR_HIP, "query_host: upload failed");
-    rtbvh_status st = rtbvh_query_async(c, dr, n, dh, mode, nullptr);
-    if (st) return st;
+    TRY(rtbvh_query_async(c, dr, n, dh, mode, nullptr));
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "query_host: sync");
     if (hipMemcpy(hits, dh, (size_t)n * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(c, RTBVH_ERR_HIP, "query_host: download failed");

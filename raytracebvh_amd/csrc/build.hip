@@ -1784,10 +1784,6 @@ __global__ __launch_bounds__(BLOCK) void k_pseudo(const float4* __restrict__ lea
 void launch_pseudo(const BuildArgs& a, hipStream_t s) {
     if (a.T > 1) hipLaunchKernelGGL(k_pseudo, dim3((a.T + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a.leaf, a.pleaf, a.rec, a.T);
 }
-void launch_refit(const BuildArgs& a, hipStream_t s) {
-    launch_refit_leaves(a, s);
-    launch_refit_tail(a, s);
-}
 void launch_records(const BuildArgs& a, hipStream_t s) {
     if (a.T > 1) hipLaunchKernelGGL(k_records, dim3(blocks_for(a.T - 1)), dim3(BLOCK), 0, s, a);
 }

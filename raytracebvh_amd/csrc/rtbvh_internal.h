@@ -99,9 +99,8 @@ struct VertexUpdate {
 void launch_update_vertices(const VertexUpdate& u, hipStream_t s);
 // Karras topology (topo, pleaf, pint)
 void launch_karras(const BuildArgs& a, hipStream_t s);
-// leaf records + refit + node records + QNodes (zeroes the tickets it uses)
-void launch_refit(const BuildArgs& a, hipStream_t s);
-// ... in two parts: the leaves (k_refit: leaf records, footprints, the in-workgroup nodes; then the
+// leaf records + refit + node records + QNodes (zeroes the tickets it uses),
+// in two parts: the leaves (k_refit: leaf records, footprints, the in-workgroup nodes; then the
 // leaves' depth range rootbox[6..7]) -- all the binned primary pass reads -- and the crossing nodes
 void launch_refit_leaves(const BuildArgs& a, hipStream_t s);
 void launch_refit_tail(const BuildArgs& a, hipStream_t s);
@@ -216,27 +215,21 @@ struct PrimBins {
 };
 inline uint32_t pb_tiles_x(uint32_t W) { return (W + PB_TILE - 1) / PB_TILE; }
 inline uint32_t pb_tiles_y(uint32_t rows) { return (rows + PB_TILE - 1) / PB_TILE; }
-// footprints, bins, the binned kernel, then k_primary (the lane walk) behind it for any tile whose
-// bins overflowed `cap`; rows = the rank's compact rows
-void launch_primary_binned(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount,
-                           bool count, bool emit, bool zeroed, hipStream_t s);
-// ... in two parts: the binned pass (reads what launch_refit_leaves writes) and the packet walk of
-// the overflowed tiles (the whole BVH)
-// redo: a certified pass (the shading checks each hit's certificate; the flagged pixels are re-traced)
-void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
-                    bool emit, bool zeroed, hipStream_t s, const BuildArgs* tail = nullptr, const Redo* redo = nullptr,
-                    bool small_tiles = false);   // (512 threads a tile: a small pass one frame at a time)
-// ... and that pass in its two parts: the bins (count pass, scan, fill pass: they read the build's leaf footprints,
+// The binned pass (reads what launch_refit_leaves writes; rows = the rank's compact rows), then k_primary (the lane
+// walk, launch_pb_gate) behind it for any tile whose bins overflowed `cap` (the whole BVH).  The pass in its two
+// parts: the bins (count pass, scan, fill pass: they read the build's leaf footprints,
 // the root box's depth range, the frame shape and the band deal, and write pb.off / cur / sums / bins and the rank's
 // leaf list -- a product of (tree, frame shape) that api.hip keeps from trace to trace), and the kernels that only
 // read them (k_primary_binned, k_primary_redo)
+// redo: a certified pass (the shading checks each hit's certificate; the flagged pixels are re-traced)
+// small_tiles: 512 threads a tile (a small pass one frame at a time)
 void launch_pb_bins(const TraceArgs& a, const PrimBins& pb, uint32_t rows, bool zeroed, hipStream_t s,
                     const BuildArgs* tail = nullptr);
 void launch_pb_raster(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
                       bool emit, hipStream_t s, const Redo* redo = nullptr, bool small_tiles = false);
 // PrimBins::keys is read and written (an RTBVH_PB_FUSE=0 build: the separate shading launch)
 bool pb_keys_used();
-// the count pass of launch_pb_pass with the climb of the build's crossing nodes in the same launch,
+// the count pass of launch_pb_bins with the climb of the build's crossing nodes in the same launch,
 // then their QNodes (build.hip: the build's launch_refit_tail, moved into the frame)
 void launch_pb_count_top(const BuildArgs& b, const TraceArgs& a, uint32_t* off, uint32_t* cur, uint4* bins, uint32_t cap,
                          uint32_t ntx, uint32_t leaf_blocks, hipStream_t s);
@@ -289,7 +282,6 @@ void launch_bounce_shade(const TraceArgs& a, const RayQ* qin, const uint32_t* qi
 struct CameraWords { float w[32]; };
 void launch_set_camera(const float* wvp, const float* wv, float* cam, hipStream_t s);
 void launch_count_diff(const float4* a, const float4* b, size_t n, unsigned long long* diff, hipStream_t s);
-void launch_count_diff32(const float* a, const float* b, size_t n, unsigned long long* diff, hipStream_t s);
 // frame from per-rank compact band buffers (stride_rows rows apart), see rtbvh_assemble_bands
 void launch_assemble(const float4* bands, const uint32_t* slots, uint32_t stride_rows, uint32_t W, uint32_t H,
                      uint32_t nranks,

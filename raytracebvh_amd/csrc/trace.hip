@@ -2272,15 +2272,6 @@ __global__ __launch_bounds__(BLOCK) void k_count_diff(const uint4* __restrict__ 
     if (lane_id() == 0 && cnt) atomicAdd(diff, cnt);
 }
 
-// the same for 32-bit words (intensities)
-__global__ __launch_bounds__(BLOCK) void k_count_diff32(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
-                                                        size_t n, unsigned long long* __restrict__ diff) {
-    unsigned long long cnt = 0;
-    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) cnt += a[i] != b[i];
-    cnt = wave_sum(cnt);
-    if (lane_id() == 0 && cnt) atomicAdd(diff, cnt);
-}
-
 // ---- instance selection on the host ------------------------------------------------------------
 // Run-time bools as compile-time constants: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{},
 // std::bool_constant<b1>{}, ...), so a generic lambda names the kernel instance `k<B0, B1>` of its arguments.
@@ -2675,12 +2666,6 @@ void launch_pb_raster(const TraceArgs& a, const PrimBins& pb, uint32_t rows, Ray
     }
 }
 
-void launch_pb_pass(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount, bool count,
-                    bool emit, bool zeroed, hipStream_t s, const BuildArgs* tail, const Redo* redo, bool small_tiles) {
-    launch_pb_bins(a, pb, rows, zeroed, s, tail);
-    launch_pb_raster(a, pb, rows, q, qcount, count, emit, s, redo, small_tiles);
-}
-
 void launch_pb_gate(const TraceArgs& a, const PrimBins& pb, RayQ* q, uint32_t* qcount, bool count, bool emit,
                     hipStream_t s, bool reference) {
     if (a.W == 0 || a.T == 0) return;
@@ -2692,13 +2677,6 @@ void launch_pb_gate(const TraceArgs& a, const PrimBins& pb, RayQ* q, uint32_t* q
     g.pb_cap = pb.cap;
     g.pb_ntx = pb.ntx;
     launch_primary(g, q, qcount, count, emit, reference ? PrimaryKind::LANE_REFERENCE : PrimaryKind::LANE_NEAREST, s);
-}
-
-void launch_primary_binned(const TraceArgs& a, const PrimBins& pb, uint32_t rows, RayQ* q, uint32_t* qcount,
-                           bool count, bool emit, bool zeroed, hipStream_t s) {
-    if (rows == 0) return;
-    launch_pb_pass(a, pb, rows, q, qcount, count, emit, zeroed, s);
-    launch_pb_gate(a, pb, q, qcount, count, emit, s, false);
 }
 
 void launch_bounce(const TraceArgs& a, const RayQ* qin, const uint32_t* qin_count, const uint32_t* perm, RayQ* qout,
@@ -2798,14 +2776,6 @@ void launch_count_diff(const float4* a, const float4* b, size_t n, unsigned long
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_count_diff, dim3((uint32_t)blocks), dim3(BLOCK), 0, s, reinterpret_cast<const uint4*>(a),
                        reinterpret_cast<const uint4*>(b), n, diff);
-}
-
-void launch_count_diff32(const float* a, const float* b, size_t n, unsigned long long* diff, hipStream_t s) {
-    if (n == 0) return;
-    size_t blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_count_diff32, dim3((uint32_t)blocks), dim3(BLOCK), 0, s, reinterpret_cast<const uint32_t*>(a),
-                       reinterpret_cast<const uint32_t*>(b), n, diff);
 }
 
 }  // namespace rtbvh

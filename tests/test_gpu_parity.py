@@ -874,6 +874,53 @@ def test_frames_in_flight_match_one_at_a_time(nranks):
             c.trace_band_async(W, H, 1, r, nranks, bufs[0].data_ptr(), stream_ptr=torch.cuda.Stream().cuda_stream)
 
 
+@pytest.mark.parametrize("flags", [TRACE_MODES["nearest+packet+wide"], rt.FLAG_CERTIFIED],
+                         ids=["nearest+packet+wide", "certified"])
+def test_buffer_sets_grow_with_frames_in_flight(flags):
+    """A buffer set's queues grow while other sets' frames are in flight, and the context stream's set is the
+    same record as a caller stream's: small and large frames dealt over three caller streams and the context
+    stream with no host synchronisation between them (the third call is the first growth of the caller sets'
+    queues, with two frames in flight), a rebuild in between -- every frame equals the one of its size traced
+    alone, and the stats are the last frame's."""
+    import torch
+    s = rt.synthetic(20_000, seed=0x5EED0021, half_extent=(100, 100, 50))
+    shapes = {"small": (320, 120), "large": (640, 360)}
+    streams = [torch.cuda.Stream() for _ in range(3)]
+    A, B, C = (st.cuda_stream for st in streams)
+
+    def blank(name):
+        W, H = shapes[name]
+        return torch.full((H, W, 4), -1.0, dtype=torch.float32, device="cuda:0")
+
+    with rt.Context(device=0, flags=flags) as c:
+        c.set_scene(s)
+        c.set_camera(*rt.camera_reference(640, 360))
+        c.build()
+        alone = {name: blank(name) for name in shapes}
+        torch.cuda.synchronize()
+        for name in ("small", "large"):
+            c.trace_band_async(*shapes[name], 1, 0, 1, alone[name].data_ptr())
+            c.synchronize()
+        st_alone = c.stats()
+        calls = [("small", A), ("small", B), ("large", C), ("large", A), ("small", B), None, ("large", B),
+                 ("large", None)]
+        bufs = [blank(call[0]) if call else None for call in calls]
+        torch.cuda.synchronize()
+        for call, b in zip(calls, bufs):
+            if call is None:
+                c.build()
+            else:
+                c.trace_band_async(*shapes[call[0]], 1, 0, 1, b.data_ptr(), stream_ptr=call[1])
+        c.synchronize()
+        torch.cuda.synchronize()
+        st = c.stats()
+        for i, (call, b) in enumerate(zip(calls, bufs)):
+            if call:
+                assert torch.equal(b, alone[call[0]]), (i, call[0])
+                assert (b[:, :, 3] != -1.0).all(), i
+        assert st["bounce_rays"] == st_alone["bounce_rays"] > 0 and st["hits"] == st_alone["hits"]
+
+
 def test_packet_frames_in_flight_after_a_binned_build():
     """A binned context's build leaves out the leaf pseudo-records; switched to the packet walk,
     its first frames go straight to caller streams (frames in flight): the pseudo-records are
