@@ -346,8 +346,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * the next build or refit waits for the update.  The arrays must stay as they are until the update has
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
- * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_* and
- * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*
+ * and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -451,6 +451,80 @@ rtbvh_status rtbvh_query_counts(rtbvh_ctx* ctx, uint64_t out[4]);
  * rtbvh_query_counts' visit words count what the kernels visited: 4-wide node steps as internal visits, plus the
  * re-traces' visits; rays and hits stay exact.  RTBVH_ERR_NOT_READY before any counting query. */
 rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- closest-point queries: the nearest triangle to points the caller chose ---------------------
+ * (No reference equivalent.)  For each point: which triangle is nearest, where on it, and how far away.
+ *
+ * Space: the space the BVH was built in, as the ray queries' -- vertex positions times the WVP of the last
+ * build, .xyz, with no divide.  The map is affine, not isometric: distances are object-space distances only when
+ * the BVH was built with an identity WVP (RTBVH_MORTON_CPUTESTS codes are object-space anyway, so that is the
+ * build to use for this).
+ *
+ * The answer is specified exactly, independent of the tree and of the walk order.  A triangle's dist2 to the
+ * point p is computed from its leaf record -- a = p0, e1 = fl(p1 - p0), e2 = fl(p2 - p0) and the leaf box
+ * [lo, hi] -- in fp32 without contraction, dots as (x*x' + y*y') + z*z':
+ *     ap = p - a;  d1 = dot(e1, ap);  d2 = dot(e2, ap)
+ *     e11 = dot(e1, e1);  e12 = dot(e1, e2);  e22 = dot(e2, e2)
+ *     d3 = d1 - e11;  d4 = d2 - e12;  d5 = d1 - e12;  d6 = d2 - e22
+ *     vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *     (u, v) = the first region that matches:
+ *       d1 <= 0 && d2 <= 0                   -> (0, 0)
+ *       d3 >= 0 && d4 <= d3                  -> (1, 0)
+ *       d6 >= 0 && d5 <= d6                  -> (0, 1)
+ *       vc <= 0 && d1 >= 0 && d3 <= 0        -> (d1 / (d1 - d3), 0)
+ *       vb <= 0 && d2 >= 0 && d6 <= 0        -> (0, d2 / (d2 - d6))
+ *       va <= 0 && d4-d3 >= 0 && d5-d6 >= 0  -> w = (d4-d3) / ((d4-d3) + (d5-d6)); (1 - w, w)
+ *       otherwise                            -> den = 1 / ((va + vb) + vc); (vb*den, vc*den)
+ *     u, v: NaN -> 0   (a degenerate triangle: vertex 0 stands for it)
+ *     q = (a + e1*u) + e2*v, then q = fmaxf(lo, fminf(hi, q)) per component
+ *     e = p - q;  dist2 = dot(e, e)
+ * The clamp into the leaf's own box makes dist2 never smaller than the point's distance to any box that contains
+ * the leaf box, computed as (dx*dx + dy*dy) + dz*dz with dk = fmaxf(fmaxf(lo_k - p_k, p_k - hi_k), 0): the walk
+ * prunes on that and still returns the brute-force answer bit for bit.
+ * The result for p with bound max_dist2 is the lexicographic minimum of (dist2, triangle id) over the triangles
+ * with dist2 <= max_dist2 (the id in triangle order, Node.index / 3); a NaN dist2 never wins.  No result, and no
+ * walk: !(max_dist2 >= 0) (NaN included), a non-finite coordinate of p, or no triangle within the bound. */
+/* A point, 16 B: {point.xyz, max_dist2}.  max_dist2 = +inf: no limit. */
+typedef struct {
+    float point[3];
+    float max_dist2;
+} rtbvh_point;
+/* A result, 32 B (two 16-B words): the closest point q on the triangle, its squared distance, its barycentrics
+ * on vertices 1 and 2 of the triangle (as rtbvh_hit's), the triangle's id in triangle order.
+ * No result: dist2 = -1, point = u = v = 0, tri = 0xFFFFFFFF.  reserved = 0 always. */
+typedef struct {
+    float point[3];
+    float dist2;
+    float u, v;
+    uint32_t tri;
+    uint32_t reserved;
+} rtbvh_nearest;
+enum {
+    RTBVH_NEAREST_SORT = 1u << 1,  /* walk the points in the order of their 30-bit Morton codes in the root box:
+                                      same results, each at its point's own index */
+    RTBVH_NEAREST_COUNT = 1u << 2  /* count points, results and steps for the counts call below (slower) */
+    /* (every other bit is rejected) */
+};
+/* n points at dev_points and n results at dev_out (device memory of the context's device, 16-B aligned), result k
+ * for point k, enqueued on `stream` (hipStream_t, NULL = the context stream).  The rules of rtbvh_query_async hold
+ * one for one: the walk reads the tree the last build or refit wrote (node records, or the topology and node
+ * boxes; never the quantized nodes); the call waits for the last build and only enqueues; closest-point and ray
+ * queries share the context's query scratch, so the library orders them all among themselves -- queries on
+ * different streams run one after the other -- and the next build waits for them; the first RTBVH_NEAREST_SORT
+ * query and each larger one grow the sort's buffers (shared with RTBVH_QUERY_SORT), which waits on the host.
+ * n == 0 returns RTBVH_OK and touches nothing; RTBVH_ERR_NOT_READY before a build and after a vertex update until
+ * the next build or refit; RTBVH_ERR_INVALID_ARG for NULL pointers with n > 0, unknown mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit ends with the best found so far, and the next synchronising call
+ * returns RTBVH_ERR_STACK_OVERFLOW, as after a ray query. */
+rtbvh_status rtbvh_nearest_async(rtbvh_ctx* ctx, const rtbvh_point* dev_points, uint64_t n, rtbvh_nearest* dev_out,
+                                 uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_nearest_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64_t n, rtbvh_nearest* out,
+                                uint32_t mode);
+/* The last RTBVH_NEAREST_COUNT query (waits for it): points, results found, internal-node steps, leaf steps.  Its
+ * own words: the ray queries' counts above keep reporting the last counting ray query.  RTBVH_ERR_NOT_READY before
+ * any counting closest-point query. */
+rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

@@ -6,9 +6,11 @@ reference's Manager/Graphics + ObjLoader surface; all compute is in the HIP libr
 from ._lib import (DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_FIRST, FLAG_REFRACT_RECORDS,
                    FLAG_SORT_BOUNCE, FLAG_TIMING, FLAG_AUTO_WALK, FLAG_PACKET_PRIMARY,
                    FLAG_REFILL_BOUNCE, FLAG_WIDE_BVH, FLAG_BINNED_PRIMARY, FLAG_CERTIFIED, FLAG_MULTI_KERNEL_BUILD, FLAG_SPLIT_SHIFT,
-                   FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NODE_DTYPE, QUERY_ANY,
+                   FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
+                   NEAREST_SORT, NODE_DTYPE, POINT_DTYPE, QUERY_ANY,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, RtbvhError, lib)
-from .graphics import Context, Graphics, check_query_rays, check_vertex_array, comm_destroy, comm_unique_id, make_rays, save_bmp
+from .graphics import (Context, Graphics, check_nearest_points, check_query_rays, check_vertex_array, comm_destroy,
+                       comm_unique_id, make_points, make_rays, save_bmp)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
                     camera_reference, load_npz, load_obj, synthetic)
 
@@ -21,4 +23,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "save_bmp", "comm_unique_id", "comm_destroy",
            "RAY_DTYPE", "HIT_DTYPE", "QUERY_CLOSEST", "QUERY_ANY", "QUERY_SORT", "QUERY_COUNT", "QUERY_CERTIFIED",
            "make_rays",
+           "POINT_DTYPE", "NEAREST_DTYPE", "NEAREST_SORT", "NEAREST_COUNT", "make_points", "check_nearest_points",
            "check_query_rays", "check_vertex_array"]

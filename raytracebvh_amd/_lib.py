@@ -46,6 +46,7 @@ EXPORTS = [
     "rtbvh_present", "rtbvh_save_bmp", "rtbvh_assemble_bands", "rtbvh_comm_unique_id", "rtbvh_comm_init",
     "rtbvh_comm_destroy", "rtbvh_trace_tiles",
     "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts", "rtbvh_query_walk_counts",
+    "rtbvh_nearest_async", "rtbvh_nearest_host", "rtbvh_nearest_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -62,6 +63,13 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 QUERY_CLOSEST, QUERY_ANY, QUERY_SORT, QUERY_COUNT = 0, 1, 2, 4   # RTBVH_QUERY_*
 QUERY_CERTIFIED = 1 << 8
+# rtbvh_point (16 B) and rtbvh_nearest (32 B), include/rtbvh.h; no result: dist2 = -1, point = u = v = 0,
+# tri = 0xFFFFFFFF
+POINT_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_dist2", "<f4")])
+NEAREST_DTYPE = np.dtype([("point", "<f4", (3,)), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"),
+                          ("reserved", "<u4")])
+assert POINT_DTYPE.itemsize == 16 and NEAREST_DTYPE.itemsize == 32
+NEAREST_SORT, NEAREST_COUNT = 2, 4   # RTBVH_NEAREST_*
 
 
 class Config(ctypes.Structure):
@@ -80,6 +88,17 @@ class Ray(ctypes.Structure):
 class Hit(ctypes.Structure):
     """rtbvh_hit (include/rtbvh.h)."""
     _fields_ = [("t", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float), ("tri", ctypes.c_uint32)]
+
+
+class Point(ctypes.Structure):
+    """rtbvh_point (include/rtbvh.h)."""
+    _fields_ = [("point", ctypes.c_float * 3), ("max_dist2", ctypes.c_float)]
+
+
+class Nearest(ctypes.Structure):
+    """rtbvh_nearest (include/rtbvh.h)."""
+    _fields_ = [("point", ctypes.c_float * 3), ("dist2", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float),
+                ("tri", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class Texture(ctypes.Structure):
@@ -208,6 +227,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_query_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_query_counts": (i32, [vp, vp]),
         "rtbvh_query_walk_counts": (i32, [vp, vp]),
+        "rtbvh_nearest_async": (i32, [vp, vp, u64, vp, u32, vp]),
+        "rtbvh_nearest_host": (i32, [vp, vp, u64, vp, u32]),
+        "rtbvh_nearest_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

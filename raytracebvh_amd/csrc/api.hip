@@ -304,7 +304,7 @@ struct rtbvh_ctx {
     // Ray queries (rtbvh_query_async), on any stream.  They share one scratch block (the walk's work counters and
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
-    DevBuf<uint32_t> d_qscratch;             // [QUERY_SCRATCH_WORDS]
+    DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts
     Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
     Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
     Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
@@ -313,6 +313,7 @@ struct rtbvh_ctx {
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
     bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
     uint64_t query_fallback = 0;             // ... its rays, when it took the present kernel for all of them; or 0
+    bool nearest_counted = false;            // the closest-point count block holds a RTBVH_NEAREST_COUNT query's counts
 };
 
 namespace {
@@ -2282,7 +2283,7 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     // tree, the full stack); otherwise the present kernel for every ray -- the same hits either way
     const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
     const bool cert = (mode & RTBVH_QUERY_CERTIFIED) != 0 && c->tree.clz64 && !limited;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_SCRATCH_WORDS));
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
     if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
     if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
         // earlier queries sort in the old buffers: the first RTBVH_QUERY_SORT query and each larger one wait
@@ -2383,6 +2384,96 @@ rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* c, uint64_t out[4]) {
     // certified, redone, uncovered from the walk; a query that took the present kernel wrote none (zeroed)
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WALK_AT, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost));
     out[3] = c->query_fallback;
+    return RTBVH_OK;
+}
+
+// ---- closest-point queries ---------------------------------------------------------------------------
+// rtbvh_query_async's rules, one for one: any stream, behind the last build (ev_built), a link of the ev_query
+// chain (the work counters and the sort's buffers are the ray queries'), the tree form the last build wrote --
+// never the quantized nodes, whose boxes are grown.  The count block is its own (QUERY_NEAREST_AT): a closest-point
+// query leaves the last counting ray query's words alone, and a ray query these.
+rtbvh_status rtbvh_nearest_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, rtbvh_nearest* dev_out,
+                                 uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_NEAREST_SORT | RTBVH_NEAREST_COUNT))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: unknown mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: 2^31 points or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_points || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: NULL points or results");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "nearest before build");
+    if (c->stale) return fail_stale(c, "nearest");
+    static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_nearest) == 32, "closest-point record layouts");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_NEAREST_SORT) != 0, count = (mode & RTBVH_NEAREST_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_NEAREST_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    NearestArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.points = reinterpret_cast<const float4*>(dev_points);
+    a.out = reinterpret_cast<float4*>(dev_out);
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_NEAREST_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    launch_nearest(a, count, s);
+    rtbvh_status st = check_launch(c, "nearest kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->nearest_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_nearest_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, rtbvh_nearest* out, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || !points || !out || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
+        return rtbvh_nearest_async(c, points, n, out, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;
+    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_point) + sizeof(rtbvh_nearest))));
+    rtbvh_nearest* dn = reinterpret_cast<rtbvh_nearest*>(d.h);
+    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + (size_t)n * sizeof(rtbvh_nearest));
+    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "nearest_host: upload failed");
+    TRY(rtbvh_nearest_async(c, dp, n, dn, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "nearest_host: sync");
+    if (hipMemcpy(out, dn, (size_t)n * sizeof(rtbvh_nearest), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "nearest_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->nearest_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_NEAREST_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_NEAREST_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 

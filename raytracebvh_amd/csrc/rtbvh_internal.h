@@ -334,4 +334,32 @@ void launch_query_certified(const QueryArgs& a, bool any, bool count, hipStream_
 void launch_query_keys(const float4* rays, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
                        hipStream_t s);
 
+// ---- closest-point queries (trace.hip k_nearest; rtbvh_nearest_async) --------
+// Caller points (rtbvh_point: one float4, {point, max_dist2}) walked on the tree form the last build wrote, as the
+// ray queries', and one rtbvh_nearest (two float4: {point, dist2}, {u, v, tri, 0}) stored per point at its own index.
+struct NearestArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* points;     // [n]
+    float4* out;              // [2n]
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_NEAREST_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_NEAREST_COUNT: [4] points, found, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the closest-point queries' own count block, behind the ray queries' scratch words (whose memsets never reach it)
+constexpr uint32_t QUERY_NEAREST_AT = QUERY_SCRATCH_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_NEAREST_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_NEAREST_AT % 2 == 0, "the count block's 8-byte words");
+void launch_nearest(const NearestArgs& a, bool count, hipStream_t s);
+// RTBVH_NEAREST_SORT's keys (the points' 30-bit Morton codes in the root box) and vals[i] = i
+void launch_nearest_keys(const float4* points, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                         hipStream_t s);
+
 }  // namespace rtbvh

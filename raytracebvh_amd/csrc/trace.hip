@@ -2547,7 +2547,222 @@ __global__ __launch_bounds__(BLOCK) void k_query_keys(const float4* __restrict__
     vals[i] = i;
 }
 
+// ---- closest-point queries (rtbvh_nearest_async): caller points in, (point, dist2, u, v, triangle) out ---------
+// For each point the lexicographic minimum of (dist2, triangle id) over the triangles with dist2 <= max_dist2, in
+// the space the BVH was built in.  include/rtbvh.h has the formulas; DESIGN.md 5d why the walk returns the
+// brute-force answer bit for bit: the closest point is clamped into the leaf's own box, so -- every operation of
+// the distance rounding monotonically -- a triangle's dist2 is never below the box distance of any box that
+// contains its leaf box, and a walk that enters a box iff its distance is <= the bound (non-strict: ties are
+// visited for the id tie-break) reaches every triangle that can win, whatever order it visits in.
+// One point per lane on k_query's frame: the same claims, stack, one 64-B fetch a step before the leaf / node
+// branch, walk-length guard and run-time stack limit.  The best is a u64 key (dist2 bits << 32 | id) started at
+// (max_dist2 bits, 0xFFFFFFFF): dist2 >= +0, so the bits order as the floats, a NaN dist2 is above every key,
+// dist2 == max_dist2 is accepted and a final sentinel id means no result.  (point, u, v) of the winner are
+// recomputed once at the end from its leaf record (bl: its sorted leaf index).
+// Plain fp32 as specified: no fma, no fast intrinsics; the one division of a triangle is the IEEE quotient.
+__device__ __forceinline__ float box_dist2(f3 p, f3 lo, f3 hi) {
+    const float dx = fmaxf(fmaxf(lo.x - p.x, p.x - hi.x), 0.f);
+    const float dy = fmaxf(fmaxf(lo.y - p.y, p.y - hi.y), 0.f);
+    const float dz = fmaxf(fmaxf(lo.z - p.z, p.z - hi.z), 0.f);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// The closest point of the triangle (a, e1, e2) to p, clamped into [lo, hi]: the Voronoi regions in the header's
+// order (the first that matches), as selects around ONE division -- each region's quotient is that division of its
+// own numerator and denominator, so the floats are the branchy form's.
+__device__ __forceinline__ float triangle_dist2(f3 p, f3 a, f3 e1, f3 e2, f3 lo, f3 hi, float& u, float& v, f3& q) {
+    const f3 ap = sub(p, a);
+    const float d1 = dot(e1, ap), d2 = dot(e2, ap);
+    const float e11 = dot(e1, e1), e12 = dot(e1, e2), e22 = dot(e2, e2);
+    const float d3 = d1 - e11, d4 = d2 - e12, d5 = d1 - e12, d6 = d2 - e22;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float d43 = d4 - d3, d56 = d5 - d6;
+    const bool r0 = d1 <= 0.f && d2 <= 0.f;                   // vertex 0
+    const bool r1 = d3 >= 0.f && d4 <= d3;                    // vertex 1
+    const bool r2 = d6 >= 0.f && d5 <= d6;                    // vertex 2
+    const bool r3 = vc <= 0.f && d1 >= 0.f && d3 <= 0.f;      // edge 0-1
+    const bool r4 = vb <= 0.f && d2 >= 0.f && d6 <= 0.f;      // edge 0-2
+    const bool r5 = va <= 0.f && d43 >= 0.f && d56 >= 0.f;    // edge 1-2
+    const float num = r3 ? d1 : r4 ? d2 : r5 ? d43 : 1.f;
+    const float den = r3 ? d1 - d3 : r4 ? d2 - d6 : r5 ? d43 + d56 : (va + vb) + vc;
+    const float w = num / den;
+    if (r0) { u = 0.f; v = 0.f; }
+    else if (r1) { u = 1.f; v = 0.f; }
+    else if (r2) { u = 0.f; v = 1.f; }
+    else if (r3) { u = w; v = 0.f; }
+    else if (r4) { u = 0.f; v = w; }
+    else if (r5) { u = 1.f - w; v = w; }
+    else { u = vb * w; v = vc * w; }
+    if (u != u) u = 0.f;   // a degenerate triangle: vertex 0 stands for it
+    if (v != v) v = 0.f;
+    q = add(add(a, mul(e1, u)), mul(e2, v));
+    q = mk(fmaxf(lo.x, fminf(hi.x, q.x)), fmaxf(lo.y, fminf(hi.y, q.y)), fmaxf(lo.z, fminf(hi.z, q.z)));
+    const f3 e = sub(p, q);
+    return dot(e, e);
+}
+// 8 waves per SIMD, as k_query: every instance fits the 64 registers without a spill
+template <bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_nearest(NearestArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t npoints = 0, nfound = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (bl: the best triangle's sorted leaf index; hit, best unused)
+    uint64_t key = 0;
+    f3 p = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    const float4 none0 = make_float4(0.f, 0.f, 0.f, -1.f), none1 = make_float4(0.f, 0.f, __uint_as_float(INVALID), 0.f);
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th point of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 pt = a.points[r];
+            p = mk(pt.x, pt.y, pt.z);
+            const float bound = pt.w + 0.f;   // (-0 -> +0: the key's bits order as the floats)
+            if (COUNT) npoints++;
+            const bool finite = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;
+            if (!(bound >= 0.f) || !finite) {   // no walk: no result
+                a.out[2 * (size_t)r] = none0;
+                a.out[2 * (size_t)r + 1] = none1;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                key = (uint64_t)__float_as_uint(bound) << 32 | 0xFFFFFFFFull;
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_query); NB: a node's children from
+        // the topology, then their boxes
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const float bound = key_t(key);
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            // the leaf's own box first (words 10..15): a triangle's dist2 is never below it
+            const f3 lo = mk(q2.z, q2.w, q3.x), hi = mk(q3.y, q3.z, q3.w);
+            if (box_dist2(p, lo, hi) <= bound) {
+                float u, v;
+                f3 q;
+                const float d = triangle_dist2(p, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), lo,
+                                               hi, u, v, q);
+                const uint64_t cand = (uint64_t)__float_as_uint(d) << 32 | (__float_as_uint(q2.y) & ~LEAF_BIT);
+                if (cand < key) {
+                    key = cand;
+                    w.bl = w.node & ~LEAF_BIT;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const float bdl = box_dist2(p, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const float bdr = box_dist2(p, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            const bool lh = bdl <= bound, rh = bdr <= bound;
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                const bool swap = lh && rh && bdr < bdl;   // the nearer child first
+                if (lh && rh) {
+                    st.store(w.sp, w.top);   // push the other
+                    w.sp++;
+                    w.top = swap ? cl : cr;
+                }
+                w.node = swap ? cr : (lh ? cl : cr);
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            float4 o0 = none0, o1 = none1;
+            if ((uint32_t)key != 0xFFFFFFFFu) {   // the winner's (point, u, v), recomputed from its leaf record
+                const float4* lr = leaf + 4 * (size_t)w.bl;
+                const float4 la = lr[0], lb = lr[1], lc = lr[2], ld = lr[3];
+                float u, v;
+                f3 q;
+                const float d = triangle_dist2(p, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y), mk(lb.z, lb.w, lc.x),
+                                               mk(lc.z, lc.w, ld.x), mk(ld.y, ld.z, ld.w), u, v, q);
+                o0 = make_float4(q.x, q.y, q.z, d);
+                o1 = make_float4(u, v, __uint_as_float((uint32_t)key), 0.f);
+            }
+            a.out[2 * (size_t)r] = o0;
+            a.out[2 * (size_t)r + 1] = o1;
+            has = false;
+            if (COUNT) nfound += (uint32_t)key != 0xFFFFFFFFu;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {npoints, nfound, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
+// RTBVH_NEAREST_SORT's key: the 30-bit Morton code of the point in the root box
+__global__ __launch_bounds__(BLOCK) void k_nearest_keys(const float4* __restrict__ points, uint32_t n,
+                                                        const float* __restrict__ box, uint32_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = points[i];
+    keys[i] = spread9(q9(p.x, box[0], box[3])) << 2 | spread9(q9(p.y, box[1], box[4])) << 1 |
+              spread9(q9(p.z, box[2], box[5]));
+    vals[i] = i;
+}
+
 }  // namespace
+
+void launch_nearest(const NearestArgs& a, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    // k_query's grid: the persistent one, or a workgroup per 256 points when that is fewer
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_nearest<COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, count, a.nb);
+}
+
+void launch_nearest_keys(const float4* points, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                         hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_nearest_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, points, n, box, keys, vals);
+}
 
 void launch_query(const QueryArgs& a, bool any, bool count, hipStream_t s) {
     if (a.n == 0) return;

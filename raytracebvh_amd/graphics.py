@@ -75,6 +75,65 @@ def check_query_rays(rays, device=None):
     return "numpy", rays.view(_L.RAY_DTYPE).reshape(-1)
 
 
+def make_points(points, max_dist2=float("inf")):
+    """Packs (N, 3) points (and one max_dist2, or N of them) as closest-point queries: a torch tensor gives an
+    (N, 4) float32 tensor on its device, anything else a POINT_DTYPE array (include/rtbvh.h rtbvh_point).  The
+    points live in the space the BVH was built in."""
+    if _is_tensor(points):
+        import torch
+        p = points.to(torch.float32).reshape(-1, 3)
+        out = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
+        out[:, 0:3] = p
+        out[:, 3] = torch.as_tensor(max_dist2, dtype=torch.float32, device=p.device)
+        return out
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), _L.POINT_DTYPE)
+    out["point"] = p
+    out["max_dist2"] = np.asarray(max_dist2, np.float32)
+    return out
+
+
+def check_nearest_points(points, max_dist2=float("inf"), device=None):
+    """Context.nearest's input check: ("torch", points) for an (N, 4) float32 contiguous CUDA tensor (on `device`
+    when given), ("numpy", POINT_DTYPE array) for a C-contiguous POINT_DTYPE array, (N, 4) float32 array or
+    (N, 3) float32 array (packed with max_dist2: one value or N of them); ValueError for anything else, and for
+    a max_dist2 given beside points that carry their own.  Calls nothing in the library."""
+    own_bound = np.ndim(max_dist2) == 0 and float(max_dist2) == float("inf")   # (the default: nothing asked for)
+    if _is_tensor(points):
+        import torch
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
+            raise ValueError(f"nearest: points must be an (N, 4) float32 tensor (make_points), got "
+                             f"{tuple(points.shape)} {points.dtype}")
+        if not points.is_cuda:
+            raise ValueError("nearest: a torch tensor of points must be on the context's GPU (numpy arrays take the "
+                             "host path)")
+        if device is not None and points.device.index != device:
+            raise ValueError(f"nearest: points on {points.device}, the context on device {device}")
+        if not points.is_contiguous():
+            raise ValueError("nearest: points must be contiguous")
+        if not own_bound:
+            raise ValueError("nearest: an (N, 4) tensor carries max_dist2 in its fourth column")
+        return "torch", points
+    if not isinstance(points, np.ndarray):
+        raise ValueError("nearest: points must be a torch CUDA tensor or a numpy array")
+    if points.dtype == _L.POINT_DTYPE:
+        if points.ndim != 1:
+            raise ValueError(f"nearest: a POINT_DTYPE array must be one-dimensional, got shape {points.shape}")
+    elif points.dtype != np.float32 or points.ndim != 2 or points.shape[1] not in (3, 4):
+        raise ValueError(f"nearest: points must be POINT_DTYPE, (N, 3) or (N, 4) float32, got {points.shape} "
+                         f"{points.dtype}")
+    if not points.flags["C_CONTIGUOUS"]:
+        raise ValueError("nearest: points must be C-contiguous")
+    if points.dtype != _L.POINT_DTYPE and points.shape[1] == 3:
+        bound = np.asarray(max_dist2, np.float32)
+        if bound.ndim > 1 or (bound.ndim == 1 and len(bound) != len(points)):
+            raise ValueError(f"nearest: max_dist2 must be one value or {len(points)} of them, got shape {bound.shape}")
+        return "numpy", make_points(points, bound)
+    if not own_bound:
+        raise ValueError("nearest: POINT_DTYPE and (N, 4) points carry max_dist2 themselves")
+    return "numpy", points.view(_L.POINT_DTYPE).reshape(-1)
+
+
 def check_vertex_array(a, what="positions", device=None):
     """Context.update_vertices' input check: (kind, array, stride in floats) for an (n, 3) float32 torch CUDA
     tensor ("torch"; on `device` when given) or numpy array ("numpy") whose last dimension is contiguous and
@@ -323,6 +382,56 @@ class Context:
         out = np.zeros(4, np.uint64)
         self._check(_L.lib().rtbvh_query_walk_counts(self._h, _L.ptr(out)))
         return dict(zip(("certified", "redone", "uncovered", "fallback"), (int(v) for v in out)))
+
+    # -- closest-point queries --
+    def nearest(self, points, max_dist2=float("inf"), mode: int = 0, out=None, stream=None):
+        """rtbvh_nearest_async / rtbvh_nearest_host: for each point the nearest triangle within max_dist2, the
+        closest point on it, its squared distance and barycentrics, in the space the BVH was built in
+        (include/rtbvh.h: distances are object-space distances only under an identity WVP).
+
+        An (N, 4) float32 contiguous CUDA tensor {x, y, z, max_dist2} on the context's device (make_points) goes to
+        the device entry with no host copy and no synchronisation, enqueued on `stream` (a torch stream or a
+        hipStream_t handle; default: the current torch stream; torch's legacy default stream as in query), and
+        returns an (N, 8) float32 device tensor {point, dist2, u, v, tri, 0}: read the triangle ids with
+        out[:, 6].view(torch.int32) (no result: dist2 = -1, tri = -1).  A POINT_DTYPE, (N, 4) or (N, 3) float32
+        numpy array -- the last packed with `max_dist2`, one value or N -- goes through the synchronous host entry
+        and returns a NEAREST_DTYPE array.  `out` receives the results when given.  mode: NEAREST_SORT,
+        NEAREST_COUNT.  ValueError for a wrong shape, dtype, device or layout."""
+        kind, pts = check_nearest_points(points, max_dist2, getattr(self, "device", None))
+        n = len(pts)
+        if kind == "numpy":
+            if out is None:
+                out = np.zeros(n, _L.NEAREST_DTYPE)
+            elif not (isinstance(out, np.ndarray) and out.dtype == _L.NEAREST_DTYPE and out.shape == (n,) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"nearest: out must be a contiguous NEAREST_DTYPE array of {n} results")
+            self._check(_L.lib().rtbvh_nearest_host(self._h, ctypes.c_void_p(pts.ctypes.data), n,
+                                                    ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=pts.device)
+        elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and
+                  out.device == pts.device and out.is_contiguous()):
+            raise ValueError(f"nearest: out must be a contiguous ({n}, 8) float32 tensor on {pts.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(pts.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(pts.device).synchronize()
+        self._check(_L.lib().rtbvh_nearest_async(self._h, ctypes.c_void_p(pts.data_ptr()), n,
+                                                 ctypes.c_void_p(out.data_ptr()), mode,
+                                                 ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def nearest_counts(self) -> dict:
+        """rtbvh_nearest_counts: points, results found, internal-node and leaf steps of the last NEAREST_COUNT
+        query (the ray queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_nearest_counts(self._h, _L.ptr(out)))
+        return dict(zip(("points", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
