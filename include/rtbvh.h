@@ -346,8 +346,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * the next build or refit waits for the update.  The arrays must stay as they are until the update has
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
- * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*
- * and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
+ * rtbvh_within_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -525,6 +525,62 @@ rtbvh_status rtbvh_nearest_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint6
  * own words: the ray queries' counts above keep reporting the last counting ray query.  RTBVH_ERR_NOT_READY before
  * any counting closest-point query. */
 rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- radius queries: every triangle within a distance of points the caller chose ---------------
+ * (No reference equivalent.)  Same points (rtbvh_point: {point.xyz, max_dist2}), same space and the same dist2 as
+ * the closest-point queries above -- a triangle's dist2 is that section's, from the leaf record, fp32, no
+ * contraction, with the clamp into the leaf's box.  The result of point k is the list of (triangle id, dist2) over
+ * exactly the triangles with dist2 <= max_dist2 (the id in triangle order, Node.index / 3); a NaN dist2 is never
+ * in the list.  The list is empty, and there is no walk, where the closest-point query has no walk:
+ * !(max_dist2 >= 0) (NaN included) or a non-finite coordinate.  -0 counts as +0; max_dist2 = +inf lists every
+ * triangle.  The set is exact, whatever the tree: dist2 is never below the distance to a box that contains the
+ * leaf box, so pruning on box distance <= max_dist2 skips no member.
+ * Order within a point's list: ascending by the triangle's position in the last build's sort order (tri_ids of
+ * rtbvh_read_sorted; a refit keeps it) -- the order a left-first depth-first walk meets the leaves in, so the output
+ * is reproducible down to the byte.
+ * Output in CSR form: dev_offsets[0] = 0, point k's pairs are dev_pairs[dev_offsets[k] .. dev_offsets[k + 1]), and
+ * dev_offsets[n] is the true total whatever `capacity` is.  A pair whose index is >= capacity is not written:
+ * nothing is ever written past dev_pairs + capacity, capacity may be 0 (dev_pairs may then be NULL), and the
+ * caller compares dev_offsets[n] with capacity. */
+typedef struct {
+    uint32_t tri;
+    float dist2;
+} rtbvh_pair; /* 8 B */
+enum {
+    RTBVH_WITHIN_SORT = 1u << 1,  /* walk the points in their Morton order (as RTBVH_NEAREST_SORT): same output */
+    RTBVH_WITHIN_COUNT = 1u << 2, /* count points, pairs and steps for rtbvh_within_counts (slower) */
+    RTBVH_WITHIN_SIZES = 1u << 4, /* write dev_offsets only; dev_pairs may be NULL */
+    RTBVH_WITHIN_FILL = 1u << 5   /* dev_offsets is INPUT (from a SIZES call for the same points and tree): write
+                                     the pairs only */
+    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG */
+};
+/* n points at dev_points, n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` pairs at dev_pairs
+ * (device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the context stream).  Mode 0
+ * runs the sizes pass, a scan of the offsets on the device and the fill pass in one call, with no host round trip;
+ * RTBVH_WITHIN_SIZES then RTBVH_WITHIN_FILL is the two-call form for a caller who sizes dev_pairs from
+ * dev_offsets[n].  A FILL over any non-decreasing offsets writes point k's pairs only inside
+ * [dev_offsets[k], min(dev_offsets[k + 1], capacity)): offsets of another tree or bound truncate lists, they never
+ * make a write go astray.
+ * Everything else follows rtbvh_nearest_async one for one: the walk reads the tree the last build or refit wrote
+ * (node records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and
+ * only enqueues; the library orders it among the ray and closest-point queries, and the next build waits for it.
+ * The first RTBVH_WITHIN_SORT query and each larger one grow the sort's buffers, and the first query that writes
+ * offsets and each larger one grow the scan's block sums: growing waits on the host for the outstanding queries.
+ * n == 0 returns RTBVH_OK and writes dev_offsets[0] = 0 only if dev_offsets is non-NULL; RTBVH_ERR_NOT_READY before
+ * a build and after a vertex update until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL points or offsets
+ * with n > 0, NULL pairs with capacity > 0 outside RTBVH_WITHIN_SIZES, bad mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit loses that subtree's pairs -- both passes lose them identically, so
+ * offsets and pairs stay consistent -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_within_async(rtbvh_ctx* ctx, const rtbvh_point* dev_points, uint64_t n, uint64_t* dev_offsets,
+                                rtbvh_pair* dev_pairs, uint64_t capacity, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (n + 1) and pairs
+ * are host arrays; pairs receives min(total, capacity) entries.  With RTBVH_WITHIN_FILL, offsets is read. */
+rtbvh_status rtbvh_within_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64_t n, uint64_t* offsets,
+                               rtbvh_pair* pairs, uint64_t capacity, uint32_t mode);
+/* The last RTBVH_WITHIN_COUNT query (waits for it): points, pairs (the true total, counted once), internal-node
+ * steps and leaf steps summed over the passes the call ran.  Its own words: the ray and closest-point counts keep
+ * theirs.  RTBVH_ERR_NOT_READY before any counting radius query. */
+rtbvh_status rtbvh_within_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

@@ -7,8 +7,9 @@ from ._lib import (DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_
                    FLAG_SORT_BOUNCE, FLAG_TIMING, FLAG_AUTO_WALK, FLAG_PACKET_PRIMARY,
                    FLAG_REFILL_BOUNCE, FLAG_WIDE_BVH, FLAG_BINNED_PRIMARY, FLAG_CERTIFIED, FLAG_MULTI_KERNEL_BUILD, FLAG_SPLIT_SHIFT,
                    FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
-                   NEAREST_SORT, NODE_DTYPE, POINT_DTYPE, QUERY_ANY,
-                   QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, RtbvhError, lib)
+                   NEAREST_SORT, NODE_DTYPE, PAIR_DTYPE, POINT_DTYPE, QUERY_ANY,
+                   QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
+                   WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, check_nearest_points, check_query_rays, check_vertex_array, comm_destroy,
                        comm_unique_id, make_points, make_rays, save_bmp)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
@@ -24,4 +25,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "RAY_DTYPE", "HIT_DTYPE", "QUERY_CLOSEST", "QUERY_ANY", "QUERY_SORT", "QUERY_COUNT", "QUERY_CERTIFIED",
            "make_rays",
            "POINT_DTYPE", "NEAREST_DTYPE", "NEAREST_SORT", "NEAREST_COUNT", "make_points", "check_nearest_points",
+           "PAIR_DTYPE", "WITHIN_SORT", "WITHIN_COUNT", "WITHIN_SIZES", "WITHIN_FILL",
            "check_query_rays", "check_vertex_array"]

@@ -47,6 +47,7 @@ EXPORTS = [
     "rtbvh_comm_destroy", "rtbvh_trace_tiles",
     "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts", "rtbvh_query_walk_counts",
     "rtbvh_nearest_async", "rtbvh_nearest_host", "rtbvh_nearest_counts",
+    "rtbvh_within_async", "rtbvh_within_host", "rtbvh_within_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -70,6 +71,10 @@ NEAREST_DTYPE = np.dtype([("point", "<f4", (3,)), ("dist2", "<f4"), ("u", "<f4")
                           ("reserved", "<u4")])
 assert POINT_DTYPE.itemsize == 16 and NEAREST_DTYPE.itemsize == 32
 NEAREST_SORT, NEAREST_COUNT = 2, 4   # RTBVH_NEAREST_*
+# rtbvh_pair (8 B): one entry of a radius query's lists
+PAIR_DTYPE = np.dtype([("tri", "<u4"), ("dist2", "<f4")])
+assert PAIR_DTYPE.itemsize == 8
+WITHIN_SORT, WITHIN_COUNT, WITHIN_SIZES, WITHIN_FILL = 2, 4, 16, 32   # RTBVH_WITHIN_*
 
 
 class Config(ctypes.Structure):
@@ -230,6 +235,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_nearest_async": (i32, [vp, vp, u64, vp, u32, vp]),
         "rtbvh_nearest_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_nearest_counts": (i32, [vp, vp]),
+        "rtbvh_within_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
+        "rtbvh_within_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
+        "rtbvh_within_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

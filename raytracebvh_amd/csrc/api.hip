@@ -304,16 +304,19 @@ struct rtbvh_ctx {
     // Ray queries (rtbvh_query_async), on any stream.  They share one scratch block (the walk's work counters and
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
-    DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts
+    DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts,
+                                             //   the radius queries' counts
     Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
     Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
     Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
+    Grown<unsigned long long> d_qscan;       // rtbvh_within_async: the offset scan's block sums; grown on demand
     Event ev_query;
     bool query_busy = false;
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
     bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
     uint64_t query_fallback = 0;             // ... its rays, when it took the present kernel for all of them; or 0
     bool nearest_counted = false;            // the closest-point count block holds a RTBVH_NEAREST_COUNT query's counts
+    bool within_counted = false;             // the radius queries' count block holds a RTBVH_WITHIN_COUNT query's counts
 };
 
 namespace {
@@ -2473,6 +2476,138 @@ rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_NEAREST_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- radius queries ------------------------------------------------------------------------------------
+// rtbvh_nearest_async's rules and its place in the ev_query chain; [keys + sort], then [sizes + scan], then [fill],
+// all on the caller's stream.  Each walk launch needs the work counters zeroed again.  Its count block is
+// QUERY_WITHIN_AT.
+rtbvh_status rtbvh_within_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, uint64_t* dev_offsets,
+                                rtbvh_pair* dev_pairs, uint64_t capacity, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_WITHIN_SORT | RTBVH_WITHIN_COUNT | RTBVH_WITHIN_SIZES | RTBVH_WITHIN_FILL;
+    constexpr uint32_t BOTH = RTBVH_WITHIN_SIZES | RTBVH_WITHIN_FILL;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "within: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "within: 2^31 points or more");
+    const bool sizes = !(mode & RTBVH_WITHIN_FILL), fill = !(mode & RTBVH_WITHIN_SIZES);
+    static_assert(sizeof(rtbvh_pair) == 8 && sizeof(uint64_t) == sizeof(unsigned long long), "radius query layouts");
+    if (n == 0) {
+        if (!dev_offsets || !sizes) return RTBVH_OK;
+        HIPC(c, hipSetDevice(c->cfg.device));
+        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+        return RTBVH_OK;
+    }
+    if (!dev_points || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "within: NULL points or offsets");
+    if (fill && capacity > 0 && !dev_pairs) return fail(c, RTBVH_ERR_INVALID_ARG, "within: NULL pairs");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "within before build");
+    if (c->stale) return fail_stale(c, "within");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_WITHIN_SORT) != 0, count = (mode & RTBVH_WITHIN_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
+    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
+    if (grow_sort || grow_scan) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort and scan in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        if (grow_sort) {
+            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+        }
+        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_WITHIN_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    WithinArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.points = reinterpret_cast<const float4*>(dev_points);
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.pairs = reinterpret_cast<uint2*>(dev_pairs);
+    a.capacity = capacity;
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_WITHIN_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {   // one permutation for both passes
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_pairs = true;
+        launch_within(a, false, count, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_pairs = !sizes;
+        launch_within(a, true, count, s);
+    }
+    rtbvh_status st = check_launch(c, "within kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->within_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_within_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, uint64_t* offsets,
+                               rtbvh_pair* pairs, uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_WITHIN_FILL) != 0, sizes_only = (mode & RTBVH_WITHIN_SIZES) != 0;
+    if (n == 0) {   // (nothing to stage)
+        const rtbvh_status st = rtbvh_within_async(c, points, 0, nullptr, pairs, capacity, mode, nullptr);
+        if (!st && offsets && !fill_only) offsets[0] = 0;
+        return st;
+    }
+    if (n >= (1ull << 31) || !points || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !pairs) ||
+        !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_within_async(c, points, n, offsets, pairs, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // offsets, then points: 8- and 16-B aligned
+    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
+    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_point)));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
+    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + off_bytes);
+    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "within_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "within_host: upload failed");
+    DevBuf<rtbvh_pair> dpairs;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dpairs.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another tree or bound leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dpairs, 0, (size_t)capacity * sizeof(rtbvh_pair), c->stream));
+    TRY(rtbvh_within_async(c, dp, n, doff, dpairs, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "within_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "within_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(pairs, dpairs, (size_t)m * sizeof(rtbvh_pair), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "within_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_within_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->within_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_WITHIN_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WITHIN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

@@ -355,11 +355,47 @@ struct NearestArgs {
 };
 // the closest-point queries' own count block, behind the ray queries' scratch words (whose memsets never reach it)
 constexpr uint32_t QUERY_NEAREST_AT = QUERY_SCRATCH_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_NEAREST_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_NEAREST_AT % 2 == 0, "the count block's 8-byte words");
 void launch_nearest(const NearestArgs& a, bool count, hipStream_t s);
 // RTBVH_NEAREST_SORT's keys (the points' 30-bit Morton codes in the root box) and vals[i] = i
 void launch_nearest_keys(const float4* points, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
                          hipStream_t s);
+
+// ---- radius queries (trace.hip k_within; rtbvh_within_async) -----------------
+// The same points on the same tree forms; the output is CSR: a sizes pass stores point r's count at offsets[r + 1],
+// scan_offsets turns the counts into offsets, a fill pass stores point r's (triangle, dist2) pairs at
+// [offsets[r], min(offsets[r + 1], capacity)).
+struct WithinArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* points;     // [n]
+    unsigned long long* offsets;    // [n + 1]: the sizes pass writes [1, n], the fill pass reads
+    uint2* pairs;             // the fill pass: [capacity] {triangle, dist2 bits}
+    unsigned long long capacity;
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_WITHIN_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_WITHIN_COUNT: [4] points, pairs, internal-node steps, leaf steps
+    bool count_pairs;         // ... this pass adds the points and pairs (one pass of a call does), not only steps
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the radius queries' own count block, behind the closest-point one
+constexpr uint32_t QUERY_WITHIN_AT = QUERY_NEAREST_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_WITHIN_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_WITHIN_AT % 2 == 0, "the count block's 8-byte words");
+void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s);
+// sort.hip: offsets[0] = 0 and offsets[1..n] = their inclusive scan, in place, in stream order; `sums`:
+// scan_sums_words(n) words of scratch
+constexpr uint32_t SCAN_TILE = 2048;   // 256 threads x 8 offsets
+inline size_t scan_sums_words(uint32_t n) {
+    const size_t t1 = ((size_t)n + SCAN_TILE - 1) / SCAN_TILE, t2 = (t1 + SCAN_TILE - 1) / SCAN_TILE;
+    return t1 + t2;
+}
+void scan_offsets(unsigned long long* offsets, uint32_t n, unsigned long long* sums, hipStream_t s);
 
 }  // namespace rtbvh

@@ -201,7 +201,91 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_downsweep(const uint32_t* __rest
     }
 }
 
+// ---- the radius queries' offsets: a scan of 64-bit counts (rtbvh_within_async) ---------------------------
+// Reduce-then-scan over tiles of SCAN_TILE values, as the sort's passes: the tiles' sums, their exclusive scan (the
+// same two kernels again on the sums; 2^31 values are three levels), then each tile's own scan on top of its base.
+// Kernel boundaries order the phases.  Thread t of a tile owns its values [8t, 8t + 8).
+using u64 = unsigned long long;
+__device__ __forceinline__ u64 block_exclusive_scan256(u64 v, u64* s_wave /*[4]*/, u64* total) {
+    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
+    u64 incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        u64 t = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += t;
+    }
+    if (lane == 63) s_wave[w] = incl;
+    __syncthreads();
+    u64 wpre = 0, tot = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        u64 x = s_wave[k];
+        if (k < w) wpre += x;
+        tot += x;
+    }
+    __syncthreads();
+    if (total) *total = tot;
+    return wpre + incl - v;
+}
+static_assert(SCAN_TILE == 8 * SORT_BLOCK, "eight values per thread");
+
+__global__ __launch_bounds__(SORT_BLOCK) void k_scan_sums(const u64* __restrict__ v, uint32_t n, u64* __restrict__ sums) {
+    __shared__ u64 s_wave[4];
+    const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + threadIdx.x * 8;
+    u64 sum = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (b0 + k < n) sum += v[b0 + k];
+    u64 tot;
+    block_exclusive_scan256(sum, s_wave, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+// v[i] = bases[tile] + the scan of the tile's values up to i (INCLUSIVE: v[i] included); bases null: 0.
+// zero (the top level: offsets[0]) is set to 0.
+template <bool INCLUSIVE>
+__global__ __launch_bounds__(SORT_BLOCK) void k_scan_tiles(u64* __restrict__ v, uint32_t n, const u64* __restrict__ bases,
+                                                           u64* __restrict__ zero) {
+    __shared__ u64 s_wave[4];
+    const size_t b0 = (size_t)blockIdx.x * SCAN_TILE + threadIdx.x * 8;
+    u64 x[8], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        x[k] = b0 + k < n ? v[b0 + k] : 0ull;
+        sum += x[k];
+    }
+    u64 pre = block_exclusive_scan256(sum, s_wave, nullptr) + (bases ? bases[blockIdx.x] : 0ull);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (b0 + k < n) v[b0 + k] = INCLUSIVE ? pre + x[k] : pre;
+        pre += x[k];
+    }
+    if (zero && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
+}
+
+// the exclusive scan of v[0..n) in place (the sums of a level above)
+void scan_exclusive(u64* v, uint32_t n, u64* sums, hipStream_t s) {
+    const uint32_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_scan_sums, dim3(tiles), dim3(SORT_BLOCK), 0, s, v, n, sums);
+        scan_exclusive(sums, tiles, sums + tiles, s);
+    }
+    hipLaunchKernelGGL(k_scan_tiles<false>, dim3(tiles), dim3(SORT_BLOCK), 0, s, v, n, tiles > 1 ? sums : nullptr,
+                       (u64*)nullptr);
+}
+
 }  // namespace
+
+void scan_offsets(unsigned long long* offsets, uint32_t n, unsigned long long* sums, hipStream_t s) {
+    if (n == 0) return;
+    u64* v = offsets + 1;
+    const uint32_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_scan_sums, dim3(tiles), dim3(SORT_BLOCK), 0, s, v, n, sums);
+        scan_exclusive(sums, tiles, sums + tiles, s);
+    }
+    hipLaunchKernelGGL(k_scan_tiles<true>, dim3(tiles), dim3(SORT_BLOCK), 0, s, v, n, tiles > 1 ? sums : nullptr, offsets);
+}
 
 SortResult radix_sort_pairs(const uint32_t* kin, const uint32_t* vin, uint32_t* ka, uint32_t* va, uint32_t* kb,
                             uint32_t* vb, uint32_t n, uint32_t key_bits, uint32_t* scratch, hipStream_t s) {

@@ -2747,7 +2747,150 @@ __global__ __launch_bounds__(BLOCK) void k_nearest_keys(const float4* __restrict
     vals[i] = i;
 }
 
+// ---- radius queries (rtbvh_within_async): caller points in, every (triangle, dist2) with dist2 <= max_dist2 out --
+// k_nearest's frame and its two distances, unchanged; the bound is the point's max_dist2 for the whole walk, so
+// DESIGN.md 5d's lemma gives the exact set (5e): a member's dist2 is never below the box distance of a box around
+// its leaf, and every box with distance <= bound is entered.  Nothing is gained from the nearer child first, so
+// the walk is left-first, which meets the leaves in the build's sort order: that is the order of a point's list.
+// FILL = false counts a point's members and stores the count at offsets[r + 1] (the scan makes offsets of them);
+// FILL = true stores the members at offsets[r] + i while that is below min(offsets[r + 1], capacity): whatever the
+// offsets hold, no store leaves the point's segment or the first `capacity` pairs.
+// Every instance fits 64 registers without a spill at 8 waves per SIMD.
+template <bool FILL, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_within(WithinArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t npoints = 0;
+    unsigned long long npairs = 0;
+    bool has = false;
+    uint32_t r = 0, cnt = 0;
+    unsigned long long pos = 0, end = 0;   // FILL: the next pair's index and the end of the point's segment
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    float bound = 0.f;
+    f3 p = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th point of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 pt = a.points[r];
+            p = mk(pt.x, pt.y, pt.z);
+            bound = pt.w + 0.f;   // (-0 -> +0)
+            if (COUNT && a.count_pairs) npoints++;
+            const bool finite = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;
+            if (!(bound >= 0.f) || !finite) {   // no walk: an empty list
+                if (!FILL) a.offsets[(size_t)r + 1] = 0;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[r];
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            const f3 lo = mk(q2.z, q2.w, q3.x), hi = mk(q3.y, q3.z, q3.w);   // the leaf's own box first
+            if (box_dist2(p, lo, hi) <= bound) {
+                float u, v;
+                f3 q;
+                const float d = triangle_dist2(p, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), lo,
+                                               hi, u, v, q);
+                if (d <= bound) {   // (false for a NaN dist2)
+                    if (!FILL || COUNT) cnt++;
+                    if (FILL && pos < end) {
+                        a.pairs[pos] = make_uint2(__float_as_uint(q2.y) & ~LEAF_BIT, __float_as_uint(d));
+                        pos++;
+                    }
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const float bdl = box_dist2(p, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const float bdr = box_dist2(p, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            const bool lh = bdl <= bound, rh = bdr <= bound;
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            if (!FILL) a.offsets[(size_t)r + 1] = cnt;
+            if (COUNT && a.count_pairs) npairs += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {npoints, npairs, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto FILL, auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_within<FILL, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.nb);
+}
 
 void launch_nearest(const NearestArgs& a, bool count, hipStream_t s) {
     if (a.n == 0) return;

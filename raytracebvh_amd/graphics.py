@@ -433,6 +433,78 @@ class Context:
         self._check(_L.lib().rtbvh_nearest_counts(self._h, _L.ptr(out)))
         return dict(zip(("points", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- radius queries --
+    def within(self, points, max_dist2=float("inf"), mode: int = 0, capacity=None, stream=None):
+        """rtbvh_within_async / rtbvh_within_host: for each point every triangle whose dist2 (Context.nearest's) is
+        <= max_dist2, as (offsets, pairs) in CSR form: point k's (triangle id, dist2) pairs are
+        pairs[offsets[k]:offsets[k + 1]], in the last build's sort order (read_sorted), and offsets[n] is the total.
+
+        `points` as Context.nearest takes them.  A numpy input goes through the synchronous host entry and returns a
+        uint64 (n + 1,) array and a PAIR_DTYPE array of offsets[n] pairs (of min(offsets[n], capacity) when
+        `capacity` is given).  A torch CUDA (N, 4) tensor goes to the device entry, enqueued on `stream` as nearest's,
+        and returns an int64 (n + 1,) device tensor and a (capacity, 2) float32 device tensor {tri, dist2} whose rows
+        [0, min(total, capacity)) are written: read the ids with pairs[:, 0].view(torch.int32).  With `capacity`
+        given that is one call, with no host copy and no synchronisation -- compare offsets[-1] with it afterwards;
+        with capacity=None a WITHIN_SIZES call, one .item() read of the total (the only synchronisation) and a
+        WITHIN_FILL call.  mode: WITHIN_SORT, WITHIN_COUNT (WITHIN_SIZES and WITHIN_FILL are this method's to set).
+        ValueError for a wrong shape, dtype, device or layout."""
+        kind, pts = check_nearest_points(points, max_dist2, getattr(self, "device", None))
+        if mode & (_L.WITHIN_SIZES | _L.WITHIN_FILL):
+            raise ValueError("within: WITHIN_SIZES and WITHIN_FILL are set by within itself")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"within: capacity must be a non-negative integer, got {capacity!r}")
+        n = len(pts)
+        L = _L.lib()
+        if kind == "numpy":
+            offsets = np.zeros(n + 1, np.uint64)
+            p, o = ctypes.c_void_p(pts.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                pairs = np.zeros(int(capacity), _L.PAIR_DTYPE)
+                self._check(L.rtbvh_within_host(self._h, p, n, o, ctypes.c_void_p(pairs.ctypes.data), len(pairs), mode))
+                return offsets, pairs[:min(int(offsets[n]), len(pairs))]
+            self._check(L.rtbvh_within_host(self._h, p, n, o, None, 0, mode | _L.WITHIN_SIZES))
+            pairs = np.zeros(int(offsets[n]), _L.PAIR_DTYPE)
+            self._check(L.rtbvh_within_host(self._h, p, n, o, ctypes.c_void_p(pairs.ctypes.data), len(pairs),
+                                            mode | _L.WITHIN_FILL))
+            return offsets, pairs
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=pts.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(pts.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(pts.device).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        p, o = ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
+
+        def call(pairs, m):
+            self._check(L.rtbvh_within_async(self._h, p, n, o, ctypes.c_void_p(pairs.data_ptr()) if pairs is not None
+                                             and pairs.numel() else None, 0 if pairs is None else pairs.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            pairs = torch.empty((int(capacity), 2), dtype=torch.float32, device=pts.device)
+            call(pairs, mode)
+            return offsets, pairs
+        call(None, mode | _L.WITHIN_SIZES)
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=pts.device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        pairs = torch.empty((total, 2), dtype=torch.float32, device=pts.device)
+        call(pairs, mode | _L.WITHIN_FILL)
+        return offsets, pairs
+
+    def within_counts(self) -> dict:
+        """rtbvh_within_counts: points, pairs (the total), internal-node and leaf steps (summed over the passes) of
+        the last WITHIN_COUNT query (the ray and closest-point counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_within_counts(self._h, _L.ptr(out)))
+        return dict(zip(("points", "pairs", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
         out = np.zeros((self.height, self.width, 4), np.float32)
