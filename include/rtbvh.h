@@ -347,7 +347,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
- * rtbvh_within_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_within_*, rtbvh_allhits_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return
+ * the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -581,6 +582,76 @@ rtbvh_status rtbvh_within_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64
  * steps and leaf steps summed over the passes the call ran.  Its own words: the ray and closest-point counts keep
  * theirs.  RTBVH_ERR_NOT_READY before any counting radius query. */
 rtbvh_status rtbvh_within_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- all-hits ray queries: every triangle a ray crosses within t_max ----------------------------
+ * (No reference equivalent.)  Space, rays and hits are the ray queries' above: rtbvh_ray in, rtbvh_hit
+ * {t, u, v, tri} out.  The result of ray k is the list of the hits of exactly its MEMBERS, specified independently
+ * of the tree and of the walk.  With o, d, t_max the ray's and inv = 1 / d per component (fp32, correctly
+ * rounded), triangle x is a member iff both hold, on the floats of its leaf record (p0, e1 = fl(p1 - p0),
+ * e2 = fl(p2 - p0), the leaf box [lo, hi]):
+ *   (B) its own leaf box passes the any-hit box rule: with t0 = (lo - o) * inv, t1 = (hi - o) * inv per axis,
+ *         mn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z))
+ *         mx = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z))
+ *       (fminf and fmaxf drop NaN), the box passes iff 0 <= mx && mn <= mx && !(mn > t_max);
+ *   (T) rayTriangleCollision (RayTraceTraversal.hlsl:41-86, fp32, no contraction) accepts with some t, and
+ *       t <= t_max.
+ * Its hit is {t, u, v, tri}: the floats the accepting test computed -- the bits rtbvh_query_* reports for that
+ * triangle -- and the id in triangle order (Node.index / 3).  (B) is part of the definition because findCollision
+ * reaches a triangle only through its leaf box: for an axis-parallel ray that starts exactly on the box's face the
+ * reference's own slab test rejects the leaf, and a triangle it never tests is no hit of the ray.  So the list is
+ * exactly the set of hits findCollision can ever return for the ray: rtbvh_query_*'s closest hit is always in it,
+ * and it is empty iff that query misses.  The set is exact whatever the tree: the slab test is monotone in the
+ * box, so every box around a member's leaf box passes too, and a walk with the fixed bound t_max skips no member
+ * (DESIGN.md 5f).
+ * The list is empty, and there is no walk, for a ray with a non-finite component of o or d, with d all zero, or
+ * with !(t_max > 0) (NaN included).  t_max = +inf: no limit.
+ * Order within a ray's list: ascending by the triangle's position in the last build's sort order (tri_ids of
+ * rtbvh_read_sorted; a refit keeps it), as a radius query's list; with RTBVH_ALLHITS_BY_T ascending by (t, tri)
+ * -- t > 0, so by the 64-bit key t bits << 32 | tri -- a total order: the output is then a function of the rays
+ * and the triangles alone.
+ * Output in CSR form, as rtbvh_within_async's: dev_offsets[0] = 0, ray k's hits are
+ * dev_hits[dev_offsets[k] .. dev_offsets[k + 1]), and dev_offsets[n] is the true total whatever `capacity` is.  A
+ * hit whose index is >= capacity is not written: nothing is ever written past dev_hits + capacity, capacity may be
+ * 0 (dev_hits may then be NULL), and the caller compares dev_offsets[n] with capacity. */
+enum {
+    RTBVH_ALLHITS_SORT = 1u << 1,  /* walk the rays in (direction octant, origin Morton) order, as RTBVH_QUERY_SORT:
+                                      same output */
+    RTBVH_ALLHITS_COUNT = 1u << 2, /* count rays, hits and steps for rtbvh_allhits_counts (slower) */
+    RTBVH_ALLHITS_BY_T = 1u << 3,  /* each ray's list ascending by (t, tri) instead of sort-order position */
+    RTBVH_ALLHITS_SIZES = 1u << 4, /* write dev_offsets only; dev_hits may be NULL */
+    RTBVH_ALLHITS_FILL = 1u << 5   /* dev_offsets is INPUT (from a SIZES call for the same rays and tree): write
+                                      (and with BY_T order) the hits only */
+    /* SIZES | FILL, SIZES | BY_T and every other bit: RTBVH_ERR_INVALID_ARG */
+};
+/* n rays at dev_rays (16-B aligned), n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` hits at
+ * dev_hits (16-B aligned; device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the
+ * context stream).  Mode 0 runs the sizes pass, a scan of the offsets on the device and the fill pass in one call,
+ * with no host round trip; RTBVH_ALLHITS_SIZES then RTBVH_ALLHITS_FILL is the two-call form.  A FILL over any
+ * non-decreasing offsets writes ray k's hits only inside [dev_offsets[k], min(dev_offsets[k + 1], capacity)): a
+ * list that does not fit its segment is cut to its first hits in sort-order position.  RTBVH_ALLHITS_BY_T orders,
+ * in place and after the fill, exactly the hits that were written: a cut list is that prefix, ordered.
+ * Everything else follows rtbvh_within_async one for one: the walk reads the tree the last build or refit wrote
+ * (node records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and
+ * only enqueues; the library orders it among all other queries, and the next build waits for it.  The first
+ * RTBVH_ALLHITS_SORT query and each larger one grow the sort's buffers, the first query that writes offsets and
+ * each larger one the scan's block sums, the first RTBVH_ALLHITS_BY_T query and each larger one two words per
+ * ray: growing waits on the host for the outstanding queries.  No device memory proportional to the output is
+ * allocated.
+ * n == 0 returns RTBVH_OK and writes dev_offsets[0] = 0 only if dev_offsets is non-NULL; RTBVH_ERR_NOT_READY before
+ * a build and after a vertex update until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL rays or offsets
+ * with n > 0, NULL hits with capacity > 0 outside RTBVH_ALLHITS_SIZES, bad mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit loses that subtree's hits -- both passes lose them identically, so
+ * offsets and hits stay consistent -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_allhits_async(rtbvh_ctx* ctx, const rtbvh_ray* dev_rays, uint64_t n, uint64_t* dev_offsets,
+                                 rtbvh_hit* dev_hits, uint64_t capacity, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (n + 1) and hits
+ * are host arrays; hits receives min(total, capacity) entries.  With RTBVH_ALLHITS_FILL, offsets is read. */
+rtbvh_status rtbvh_allhits_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t n, uint64_t* offsets,
+                                rtbvh_hit* hits, uint64_t capacity, uint32_t mode);
+/* The last RTBVH_ALLHITS_COUNT query (waits for it): rays, hits (the true total, counted once), internal-node
+ * steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts keep theirs.
+ * RTBVH_ERR_NOT_READY before any counting all-hits query. */
+rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

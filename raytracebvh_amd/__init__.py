@@ -3,7 +3,8 @@ Fierykev/RayTraceBVH) as hand-written HIP kernels for gfx950 behind a C ABI
 (include/rtbvh.h, librtbvh.so).  This package is the thin host-side mirror of the
 reference's Manager/Graphics + ObjLoader surface; all compute is in the HIP library.
 """
-from ._lib import (DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_FIRST, FLAG_REFRACT_RECORDS,
+from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALLHITS_SORT,
+                   DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_FIRST, FLAG_REFRACT_RECORDS,
                    FLAG_SORT_BOUNCE, FLAG_TIMING, FLAG_AUTO_WALK, FLAG_PACKET_PRIMARY,
                    FLAG_REFILL_BOUNCE, FLAG_WIDE_BVH, FLAG_BINNED_PRIMARY, FLAG_CERTIFIED, FLAG_MULTI_KERNEL_BUILD, FLAG_SPLIT_SHIFT,
                    FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
@@ -26,4 +27,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "make_rays",
            "POINT_DTYPE", "NEAREST_DTYPE", "NEAREST_SORT", "NEAREST_COUNT", "make_points", "check_nearest_points",
            "PAIR_DTYPE", "WITHIN_SORT", "WITHIN_COUNT", "WITHIN_SIZES", "WITHIN_FILL",
+           "ALLHITS_SORT", "ALLHITS_COUNT", "ALLHITS_BY_T", "ALLHITS_SIZES", "ALLHITS_FILL",
            "check_query_rays", "check_vertex_array"]

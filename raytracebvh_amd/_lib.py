@@ -48,6 +48,7 @@ EXPORTS = [
     "rtbvh_query_async", "rtbvh_query_host", "rtbvh_query_counts", "rtbvh_query_walk_counts",
     "rtbvh_nearest_async", "rtbvh_nearest_host", "rtbvh_nearest_counts",
     "rtbvh_within_async", "rtbvh_within_host", "rtbvh_within_counts",
+    "rtbvh_allhits_async", "rtbvh_allhits_host", "rtbvh_allhits_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -75,6 +76,7 @@ NEAREST_SORT, NEAREST_COUNT = 2, 4   # RTBVH_NEAREST_*
 PAIR_DTYPE = np.dtype([("tri", "<u4"), ("dist2", "<f4")])
 assert PAIR_DTYPE.itemsize == 8
 WITHIN_SORT, WITHIN_COUNT, WITHIN_SIZES, WITHIN_FILL = 2, 4, 16, 32   # RTBVH_WITHIN_*
+ALLHITS_SORT, ALLHITS_COUNT, ALLHITS_BY_T, ALLHITS_SIZES, ALLHITS_FILL = 2, 4, 8, 16, 32   # RTBVH_ALLHITS_*
 
 
 class Config(ctypes.Structure):
@@ -238,6 +240,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_within_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_within_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_within_counts": (i32, [vp, vp]),
+        "rtbvh_allhits_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
+        "rtbvh_allhits_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
+        "rtbvh_allhits_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

@@ -305,11 +305,13 @@ struct rtbvh_ctx {
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
     DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts,
-                                             //   the radius queries' counts
+                                             //   the radius queries' counts, the all-hits queries' counts
     Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
     Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
     Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
-    Grown<unsigned long long> d_qscan;       // rtbvh_within_async: the offset scan's block sums; grown on demand
+    Grown<unsigned long long> d_qscan;       // rtbvh_within_async, rtbvh_allhits_async: the offset scan's block sums
+    Grown<uint32_t> d_qorder;                // RTBVH_ALLHITS_BY_T: 2 arrays of cap / 2 words (each ray's stored hits, the
+                                             //   rays with long lists); grown on demand
     Event ev_query;
     bool query_busy = false;
     bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
@@ -317,6 +319,7 @@ struct rtbvh_ctx {
     uint64_t query_fallback = 0;             // ... its rays, when it took the present kernel for all of them; or 0
     bool nearest_counted = false;            // the closest-point count block holds a RTBVH_NEAREST_COUNT query's counts
     bool within_counted = false;             // the radius queries' count block holds a RTBVH_WITHIN_COUNT query's counts
+    bool allhits_counted = false;            // the all-hits count block holds a RTBVH_ALLHITS_COUNT query's counts
 };
 
 namespace {
@@ -2608,6 +2611,151 @@ rtbvh_status rtbvh_within_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WITHIN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+
+// ---- all-hits ray queries --------------------------------------------------------------------------------
+// rtbvh_within_async's structure with rtbvh_query_async's rays and sort keys: [keys + sort], [sizes + scan],
+// [fill], then for RTBVH_ALLHITS_BY_T the ordering pass, all on the caller's stream.  Its count block is
+// QUERY_ALLHITS_AT.  The ordering pass takes the work counters' first word (the walks are over) for the length of
+// its list.
+rtbvh_status rtbvh_allhits_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, uint64_t* dev_offsets,
+                                 rtbvh_hit* dev_hits, uint64_t capacity, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_ALLHITS_SORT | RTBVH_ALLHITS_COUNT | RTBVH_ALLHITS_BY_T | RTBVH_ALLHITS_SIZES |
+                             RTBVH_ALLHITS_FILL;
+    constexpr uint32_t BOTH = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_FILL;
+    constexpr uint32_t SIZES_BY_T = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_BY_T;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH || (mode & SIZES_BY_T) == SIZES_BY_T)
+        return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: 2^31 rays or more");
+    const bool sizes = !(mode & RTBVH_ALLHITS_FILL), fill = !(mode & RTBVH_ALLHITS_SIZES);
+    if (n == 0) {
+        if (!dev_offsets || !sizes) return RTBVH_OK;
+        HIPC(c, hipSetDevice(c->cfg.device));
+        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+        return RTBVH_OK;
+    }
+    if (!dev_rays || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: NULL rays or offsets");
+    if (fill && capacity > 0 && !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: NULL hits");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "allhits before build");
+    if (c->stale) return fail_stale(c, "allhits");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_ALLHITS_SORT) != 0, count = (mode & RTBVH_ALLHITS_COUNT) != 0;
+    const bool by_t = (mode & RTBVH_ALLHITS_BY_T) != 0 && capacity > 0;   // (nothing stored: nothing to order)
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
+    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
+    const bool grow_order = by_t && !c->d_qorder.has(2 * (size_t)n);
+    if (grow_sort || grow_scan || grow_order) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort, scan and order in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        if (grow_sort) {
+            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+        }
+        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+        if (grow_order) HIPC(c, c->d_qorder.reserve(2 * (size_t)n));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_ALLHITS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    AllhitsArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.rays = reinterpret_cast<const float4*>(dev_rays);
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.hits = reinterpret_cast<float4*>(dev_hits);
+    a.capacity = capacity;
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_ALLHITS_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {   // one permutation for both passes
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_hits = true;
+        launch_allhits(a, false, count, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_hits = !sizes;
+        uint32_t* ord = c->d_qorder;
+        if (by_t) a.written = ord;
+        launch_allhits(a, true, count, s);
+        if (by_t) {
+            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t), s));   // the list's length
+            launch_allhits_order(a.hits, a.offsets, ord, N, ord + c->d_qorder.cap / 2, c->d_qscratch, s);
+        }
+    }
+    rtbvh_status st = check_launch(c, "allhits kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->allhits_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_allhits_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, uint64_t* offsets, rtbvh_hit* hits,
+                                uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_ALLHITS_FILL) != 0, sizes_only = (mode & RTBVH_ALLHITS_SIZES) != 0;
+    if (n == 0) {   // (nothing to stage)
+        const rtbvh_status st = rtbvh_allhits_async(c, rays, 0, nullptr, hits, capacity, mode, nullptr);
+        if (!st && offsets && !fill_only) offsets[0] = 0;
+        return st;
+    }
+    if (n >= (1ull << 31) || !rays || !offsets || (fill_only && sizes_only) ||
+        (sizes_only && (mode & RTBVH_ALLHITS_BY_T)) || (!sizes_only && capacity > 0 && !hits) || !c->tree.built ||
+        c->stale)   // (the query's checks)
+        return rtbvh_allhits_async(c, rays, n, offsets, hits, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // rays, then offsets: 16- and 8-B aligned
+    HIPC(c, d.alloc((size_t)n * sizeof(rtbvh_ray) + (size_t)(n + 1) * sizeof(uint64_t)));
+    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d.h);
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d + (size_t)n * sizeof(rtbvh_ray));
+    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "allhits_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "allhits_host: upload failed");
+    DevBuf<rtbvh_hit> dhits;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dhits.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another tree or bound leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dhits, 0, (size_t)capacity * sizeof(rtbvh_hit), c->stream));
+    TRY(rtbvh_allhits_async(c, dr, n, doff, dhits, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "allhits_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "allhits_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(hits, dhits, (size_t)m * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "allhits_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->allhits_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_ALLHITS_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_ALLHITS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

@@ -386,7 +386,6 @@ struct WithinArgs {
 };
 // the radius queries' own count block, behind the closest-point one
 constexpr uint32_t QUERY_WITHIN_AT = QUERY_NEAREST_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_WITHIN_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_WITHIN_AT % 2 == 0, "the count block's 8-byte words");
 void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s);
 // sort.hip: offsets[0] = 0 and offsets[1..n] = their inclusive scan, in place, in stream order; `sums`:
@@ -397,5 +396,49 @@ inline size_t scan_sums_words(uint32_t n) {
     return t1 + t2;
 }
 void scan_offsets(unsigned long long* offsets, uint32_t n, unsigned long long* sums, hipStream_t s);
+
+// ---- all-hits ray queries (trace.hip k_allhits; rtbvh_allhits_async) ---------
+// QueryArgs' rays on the same tree forms, WithinArgs' CSR output: a sizes pass stores ray r's count at
+// offsets[r + 1], scan_offsets makes offsets of them, a fill pass stores ray r's hits (float4: t, u, v, tri) at
+// [offsets[r], min(offsets[r + 1], capacity)) and, for RTBVH_ALLHITS_BY_T, how many it stored at written[r].
+struct AllhitsArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* rays;       // [2n]
+    unsigned long long* offsets;    // [n + 1]: the sizes pass writes [1, n], the fill pass reads
+    float4* hits;             // the fill pass: [capacity]
+    unsigned long long capacity;
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_ALLHITS_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_ALLHITS_COUNT: [4] rays, hits, internal-node steps, leaf steps
+    bool count_hits;          // ... this pass adds the rays and hits (one pass of a call does), not only steps
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+    uint32_t* written;        // the fill pass of a BY_T call: [n] the hits stored of each ray; else null
+};
+// the all-hits queries' own count block, behind the radius queries'
+constexpr uint32_t QUERY_ALLHITS_AT = QUERY_WITHIN_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_ALLHITS_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_ALLHITS_AT % 2 == 0, "the count block's 8-byte words");
+void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s);
+// RTBVH_ALLHITS_BY_T: each ray's stored hits [offsets[r], offsets[r] + written[r]) ordered by (t, tri), in place.
+// Lists of up to ALLHITS_LANE_MAX hits are sorted by their ray's lane; the rays with longer ones are listed in
+// `list` ([n] words; *list_n zeroed) and sorted one workgroup a list: up to ALLHITS_LDS_MAX hits in LDS, longer
+// ones chunk by chunk in LDS with the network's long-distance steps on global memory.
+// (The thresholds: DESIGN.md 5f has what was measured.)
+#ifndef RTBVH_ALLHITS_LANE_MAX
+#define RTBVH_ALLHITS_LANE_MAX 32
+#endif
+#ifndef RTBVH_ALLHITS_LDS_MAX
+#define RTBVH_ALLHITS_LDS_MAX 2048   // 32 KB of LDS
+#endif
+constexpr uint32_t ALLHITS_LANE_MAX = RTBVH_ALLHITS_LANE_MAX, ALLHITS_LDS_MAX = RTBVH_ALLHITS_LDS_MAX;
+void launch_allhits_order(float4* hits, const unsigned long long* offsets, const uint32_t* written, uint32_t n,
+                          uint32_t* list, uint32_t* list_n, hipStream_t s);
 
 }  // namespace rtbvh

@@ -2882,7 +2882,290 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_within(WithinArgs a) {
     }
 }
 
+// ---- all-hits ray queries (rtbvh_allhits_async): caller rays in, every (t, u, v, triangle) with t <= t_max out ----
+// k_within's frame and CSR protocol with k_query's rays.  The bound never shrinks: a child is entered iff its box
+// passes the any-hit rule query_box<true> with the ray's t_max, left first, and a leaf's triangle is a member iff
+// ray_triangle accepts it at t <= t_max.  The slab test is monotone in the box, so every box around a member's
+// leaf box passes when the leaf box does: the walk lists the brute-force set, in the build's sort
+// order.  A leaf's own box is tested at its parent (the same floats); a one-triangle tree has no parent, so the
+// box is tested at the leaf there.
+// rayTriangleCollision with (u, v) kept: ray_triangle's operations in ray_triangle's order
+__device__ __forceinline__ float ray_triangle_tuv(f3 o, f3 d, f3 p0, f3 e1, f3 e2, float& u, float& v) {
+    f3 tmp = cross(d, e2);
+    const float dx = dot(e1, tmp);
+    if (fabsf(dx) < EPSILON) return -1.f;
+    const float idx = 1.f / dx;
+    const f3 rt = sub(o, p0);
+    u = dot(rt, tmp) * idx;
+    if (u < .0f || 1.f < u) return -1.f;
+    tmp = cross(rt, e1);
+    v = dot(d, tmp) * idx;
+    if (v < .0f || 1.f < u + v) return -1.f;
+    const float t = dot(e2, tmp) * idx;
+    if (EPSILON < t) return t;
+    return -1.f;
+}
+// FILL = false counts a ray's members and stores the count at offsets[r + 1]; FILL = true stores the members at
+// offsets[r] + i while that is below min(offsets[r + 1], capacity), one 16-B store each: whatever the offsets hold,
+// no store leaves the ray's segment or the first `capacity` hits.
+template <bool FILL, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_allhits(AllhitsArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nrays = 0;
+    unsigned long long nhits = 0;
+    bool has = false;
+    uint32_t r = 0, cnt = 0;
+    unsigned long long pos = 0, end = 0;   // FILL: the next hit's index and the end of the ray's segment
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    float tmax = 0.f;
+    f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
+            r = a.perm ? a.perm[p] : p;
+            const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
+            o = mk(q0.x, q0.y, q0.z);
+            tmax = q0.w;
+            d = mk(q1.x, q1.y, q1.z);
+            inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            if (COUNT && a.count_hits) nrays++;
+            const bool finite = fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY &&
+                                fabsf(d.x) < INFINITY && fabsf(d.y) < INFINITY && fabsf(d.z) < INFINITY;
+            const bool zero = d.x == 0.f && d.y == 0.f && d.z == 0.f;
+            if (!finite || zero || !(tmax > 0.f)) {   // no walk: an empty list
+                if (!FILL) a.offsets[(size_t)r + 1] = 0;
+                else if (a.written) a.written[r] = 0;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[r];
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_query)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        float mn;
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            // (T == 1: the root is the leaf, and no parent tested its box -- words 10..15 of the record)
+            if (T > 1 || query_box<true>(o, inv, f2v{q2.z, q2.w}, f2v{q3.y, q3.z}, q3.x, q3.w, false, 0.f, tmax, mn)) {
+                float u = 0.f, v = 0.f;
+                const float t = ray_triangle_tuv(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y),
+                                                 mk(q1.z, q1.w, q2.x), u, v);
+                if (t != -1.f && t <= tmax) {
+                    if (!FILL || COUNT) cnt++;
+                    if (FILL && pos < end) {
+                        a.hits[pos] = make_float4(t, u, v, __uint_as_float(__float_as_uint(q2.y) & ~LEAF_BIT));
+                        pos++;
+                    }
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = query_box<true>(o, inv, q0.xy, q0.zw, q2.x, q2.y, false, 0.f, tmax, mn);
+            const bool rh = query_box<true>(o, inv, q1.xy, q1.zw, q2.z, q2.w, false, 0.f, tmax, mn);
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            if (!FILL) a.offsets[(size_t)r + 1] = cnt;
+            else if (a.written) a.written[r] = (uint32_t)(pos - a.offsets[r]);   // (pos started there)
+            if (COUNT && a.count_hits) nhits += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nrays, nhits, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
+// ---- RTBVH_ALLHITS_BY_T: each ray's stored hits ordered by (t, tri), in place ---------------------------------
+// t > EPSILON > 0, so the floats order as their bits and (t, tri) is the u64 key t bits << 32 | tri: a total order
+// (a ray's list holds a triangle once).  A hit moves as one 16-B word.
+__device__ __forceinline__ uint64_t hit_key(float4 h) {
+    return (uint64_t)__float_as_uint(h.x) << 32 | __float_as_uint(h.w);
+}
+// One lane per ray: a list of up to ALLHITS_LANE_MAX hits is insertion-sorted where it lies (mostly already in
+// order or nearly so, and L1-resident); the rays with longer lists are appended to `list`, one atomic a wave.
+__global__ __launch_bounds__(BLOCK) void k_allhits_order_lane(float4* __restrict__ hits,
+                                                              const unsigned long long* __restrict__ offsets,
+                                                              const uint32_t* __restrict__ written, uint32_t n,
+                                                              uint32_t* __restrict__ list, uint32_t* list_n) {
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t len = r < n ? written[r] : 0;
+    const bool lng = len > ALLHITS_LANE_MAX;
+    const uint32_t slot = wave_append(lng, list_n);   // (all lanes converged)
+    if (lng) list[slot] = r;
+    if (lng || len < 2) return;
+    float4* h = hits + offsets[r];
+    for (uint32_t i = 1; i < len; i++) {
+        const float4 x = h[i];
+        const uint64_t kx = hit_key(x);
+        uint32_t j = i;
+        while (j > 0) {
+            const float4 y = h[j - 1];
+            if (hit_key(y) <= kx) break;
+            h[j] = y;
+            j--;
+        }
+        if (j != i) h[j] = x;
+    }
+}
+// The bitonic network with every comparator ascending (a stage's first step pairs i with its mirror in the 2k
+// block, the others i with i + j), by one workgroup over a[0, len), len of any size: the network is that of the
+// next power of two with +inf behind the list -- a comparator never moves its larger element down, so those stay
+// where they are and a pair that reaches past the list is skipped.  `a`: LDS or global memory (the workgroup's
+// own stores, ordered by the barrier).
+template <class Ptr> __device__ __forceinline__ void order_pair(Ptr a, uint32_t i, uint32_t l) {
+    const float4 x = a[i], y = a[l];
+    if (hit_key(y) < hit_key(x)) {
+        a[i] = y;
+        a[l] = x;
+    }
+}
+// stage k's first step: i in the lower half of its k-block, and its mirror
+template <class Ptr> __device__ __forceinline__ void order_mirror(Ptr a, uint32_t len, uint32_t k, uint32_t tid) {
+    const uint32_t hb = k >> 1;
+    for (uint32_t p = tid;; p += BLOCK) {
+        const uint32_t base = (p & ~(hb - 1)) << 1, off = p & (hb - 1);
+        const uint32_t i = base | off, l = base + (k - 1 - off);
+        if (i >= len) break;   // (i grows with p)
+        if (l < len) order_pair(a, i, l);
+    }
+    __syncthreads();
+}
+// the steps at the distances j_first, j_first / 2, ... down to j_last: index i with bit j clear, and i + j
+template <class Ptr>
+__device__ __forceinline__ void order_steps(Ptr a, uint32_t len, uint32_t j_first, uint32_t j_last, uint32_t tid) {
+    for (uint32_t j = j_first; j >= j_last && j >= 1; j >>= 1) {
+        for (uint32_t p = tid;; p += BLOCK) {
+            const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+            if (i >= len) break;
+            if (l < len) order_pair(a, i, l);
+        }
+        __syncthreads();
+    }
+}
+template <class Ptr> __device__ __forceinline__ void order_network(Ptr a, uint32_t len, uint32_t tid) {
+    for (uint32_t k = 2; (k >> 1) < len; k <<= 1) {   // (len < 2^30: a list holds a triangle once)
+        order_mirror(a, len, k, tid);
+        order_steps(a, len, k >> 2, 1, tid);
+    }
+}
+// One workgroup per listed ray.  A list of up to C = ALLHITS_LDS_MAX hits is sorted in LDS.  A longer one chunk by
+// chunk: the stages up to C are each chunk's own sort (C divides a chunk's start, so the network's blocks are the
+// chunks); of a later stage the steps at distances >= C run on global memory and the rest, again chunk-local, in
+// LDS -- 2 + log2(P / C) (3 + log2(P / C)) / 2 passes over the list instead of one per step.
+__global__ __launch_bounds__(BLOCK) void k_allhits_order_block(float4* hits, const unsigned long long* __restrict__ offsets,
+                                                               const uint32_t* __restrict__ written,
+                                                               const uint32_t* __restrict__ list,
+                                                               const uint32_t* __restrict__ list_n) {
+    constexpr uint32_t C = ALLHITS_LDS_MAX;
+    static_assert((C & (C - 1)) == 0 && C >= 2, "the LDS chunk: a power of two");
+    __shared__ float4 s_h[C];
+    const uint32_t m = *list_n, tid = threadIdx.x;
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
+        const uint32_t r = list[i], len = written[r];
+        float4* g = hits + offsets[r];
+        uint32_t k = C;   // k = C: the chunks' own sorts; then the stages 2C, 4C, ... while half a stage is inside the list
+        do {
+            if (k > C) {
+                order_mirror(g, len, k, tid);
+                order_steps(g, len, k >> 2, C, tid);
+            }
+            for (uint32_t c0 = 0; c0 < len; c0 += C) {
+                const uint32_t n = len - c0 < C ? len - c0 : C;
+                for (uint32_t e = tid; e < n; e += BLOCK) s_h[e] = g[c0 + e];
+                __syncthreads();
+                if (k == C) order_network(&s_h[0], n, tid);
+                else order_steps(&s_h[0], n, C >> 1, 1, tid);
+                for (uint32_t e = tid; e < n; e += BLOCK) g[c0 + e] = s_h[e];
+                __syncthreads();   // (the next loads overwrite s_h; the next global step reads g)
+            }
+            k <<= 1;
+        } while ((k >> 1) < len);
+    }
+}
+
 }  // namespace
+
+void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto FILL, auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_allhits<FILL, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.nb);
+}
+
+void launch_allhits_order(float4* hits, const unsigned long long* offsets, const uint32_t* written, uint32_t n,
+                          uint32_t* list, uint32_t* list_n, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_allhits_order_lane, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, hits, offsets, written,
+                       n, list, list_n);
+    // (the list's length is on the device: the workgroups past it leave at once)
+    hipLaunchKernelGGL(k_allhits_order_block, dim3(n < 1024u ? n : 1024u), dim3(BLOCK), 0, s, hits, offsets, written,
+                       list, list_n);
+}
 
 void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s) {
     if (a.n == 0) return;

@@ -505,6 +505,87 @@ class Context:
         self._check(_L.lib().rtbvh_within_counts(self._h, _L.ptr(out)))
         return dict(zip(("points", "pairs", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- all-hits ray queries --
+    def allhits(self, rays, mode: int = 0, capacity=None, stream=None, sizes_only: bool = False):
+        """rtbvh_allhits_async / rtbvh_allhits_host: for each ray every triangle it crosses at t <= t_max, as
+        (offsets, hits) in CSR form: ray k's hits {t, u, v, tri} are hits[offsets[k]:offsets[k + 1]], in the last
+        build's sort order (read_sorted) or, with ALLHITS_BY_T, ascending by (t, tri); offsets[n] is the total.
+
+        `rays` as Context.query takes them.  A numpy input goes through the synchronous host entry and returns a
+        uint64 (n + 1,) array and a HIT_DTYPE array of offsets[n] hits (of min(offsets[n], capacity) when `capacity`
+        is given).  A torch CUDA (N, 8) tensor goes to the device entry, enqueued on `stream` as query's, and returns
+        an int64 (n + 1,) device tensor and a (capacity, 4) float32 device tensor whose rows [0, min(total, capacity))
+        are written: read the ids with hits[:, 3].view(torch.int32).  With `capacity` given that is one call, with no
+        host copy and no synchronisation -- compare offsets[-1] with it afterwards; with capacity=None an
+        ALLHITS_SIZES call, one .item() read of the total (the only synchronisation) and an ALLHITS_FILL call.
+        sizes_only=True returns the offsets alone (crossing parity needs no hits).  mode: ALLHITS_SORT,
+        ALLHITS_COUNT, ALLHITS_BY_T (ALLHITS_SIZES and ALLHITS_FILL are this method's to set).  ValueError for a
+        wrong shape, dtype, device or layout."""
+        kind, rays = check_query_rays(rays, getattr(self, "device", None))
+        if mode & (_L.ALLHITS_SIZES | _L.ALLHITS_FILL):
+            raise ValueError("allhits: ALLHITS_SIZES and ALLHITS_FILL are set by allhits itself")
+        if mode & ~(_L.ALLHITS_SORT | _L.ALLHITS_COUNT | _L.ALLHITS_BY_T):
+            raise ValueError(f"allhits: unknown mode bits {mode:#x}")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"allhits: capacity must be a non-negative integer, got {capacity!r}")
+        if sizes_only and (capacity is not None or mode & _L.ALLHITS_BY_T):
+            raise ValueError("allhits: sizes_only takes no capacity and no ALLHITS_BY_T")
+        n = len(rays)
+        L = _L.lib()
+        if kind == "numpy":
+            offsets = np.zeros(n + 1, np.uint64)
+            p, o = ctypes.c_void_p(rays.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                hits = np.zeros(int(capacity), _L.HIT_DTYPE)
+                self._check(L.rtbvh_allhits_host(self._h, p, n, o, ctypes.c_void_p(hits.ctypes.data), len(hits), mode))
+                return offsets, hits[:min(int(offsets[n]), len(hits))]
+            self._check(L.rtbvh_allhits_host(self._h, p, n, o, None, 0, (mode & ~_L.ALLHITS_BY_T) | _L.ALLHITS_SIZES))
+            if sizes_only:
+                return offsets
+            hits = np.zeros(int(offsets[n]), _L.HIT_DTYPE)
+            self._check(L.rtbvh_allhits_host(self._h, p, n, o, ctypes.c_void_p(hits.ctypes.data), len(hits),
+                                             mode | _L.ALLHITS_FILL))
+            return offsets, hits
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(rays.device).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        p, o = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
+
+        def call(hits, m):
+            self._check(L.rtbvh_allhits_async(self._h, p, n, o, ctypes.c_void_p(hits.data_ptr()) if hits is not None
+                                              and hits.numel() else None, 0 if hits is None else hits.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            hits = torch.empty((int(capacity), 4), dtype=torch.float32, device=rays.device)
+            call(hits, mode)
+            return offsets, hits
+        call(None, (mode & ~_L.ALLHITS_BY_T) | _L.ALLHITS_SIZES)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=rays.device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        hits = torch.empty((total, 4), dtype=torch.float32, device=rays.device)
+        call(hits, mode | _L.ALLHITS_FILL)
+        return offsets, hits
+
+    def allhits_counts(self) -> dict:
+        """rtbvh_allhits_counts: rays, hits (the total), internal-node and leaf steps (summed over the passes) of
+        the last ALLHITS_COUNT query (the other queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_allhits_counts(self._h, _L.ptr(out)))
+        return dict(zip(("rays", "hits", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
         out = np.zeros((self.height, self.width, 4), np.float32)
