@@ -347,8 +347,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
- * rtbvh_within_*, rtbvh_allhits_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return
- * the last build's tree.
+ * rtbvh_within_*, rtbvh_allhits_*, rtbvh_overlap_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the
+ * rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -652,6 +652,82 @@ rtbvh_status rtbvh_allhits_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t 
  * steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts keep theirs.
  * RTBVH_ERR_NOT_READY before any counting all-hits query. */
 rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
+ * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The
+ * result of box k is the list of the ids (in triangle order, Node.index / 3) of exactly the triangles that are
+ * members of it.  Membership is defined on the floats of the triangle's leaf record -- a = p0, e1 = fl(p1 - p0),
+ * e2 = fl(p2 - p0) and the leaf box [lo, hi] -- independently of the tree and of the walk; arithmetic is fp32
+ * without contraction.  Triangle x is a member of the query box [qlo, qhi] iff
+ *  (B) on every axis k: qlo_k <= hi_k && lo_k <= qhi_k.  The intervals are closed: touching counts.  There is no
+ *      arithmetic, so no rounding; a NaN in a leaf box fails it.
+ *  (T) with RTBVH_OVERLAP_TRIANGLE only: none of the ten axes below separates the triangle from the box (the three
+ *      box-face axes are (B)).  In every `separated` comparison a NaN compares false: it does not separate.
+ *      Set-up, per component: c = (qlo + qhi) * 0.5f, h = (qhi - qlo) * 0.5f; v0 = a - c, v1 = v0 + e1, v2 = v0 + e2.
+ *      Plane: n = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x);
+ *             d = (n.x*v0.x + n.y*v0.y) + n.z*v0.z;  r = (h.x*|n.x| + h.y*|n.y|) + h.z*|n.z|;
+ *             separated iff d > r || d < -r.
+ *      Edges: for each edge f of e1, fl(e2 - e1), e2, in that order, and each of three axes, the projections p_i of
+ *             v0, v1, v2 and a radius rr:
+ *               x: p_i = v_i.z*f.y - v_i.y*f.z,  rr = h.y*|f.z| + h.z*|f.y|;
+ *               y: p_i = v_i.x*f.z - v_i.z*f.x,  rr = h.x*|f.z| + h.z*|f.x|;
+ *               z: p_i = v_i.y*f.x - v_i.x*f.y,  rr = h.x*|f.y| + h.y*|f.x|;
+ *             separated iff fminf(fminf(p0, p1), p2) > rr || fmaxf(fmaxf(p0, p1), p2) < -rr.
+ *      (T) is the usual separating-axis test evaluated in fp32 with no error margins: a contact within rounding
+ *      can go either way, as with rayTriangleCollision's EPSILON.  It is the same answer on every tree.
+ * The list is empty, and there is no walk, for a box with a non-finite bound or with !(qlo_k <= qhi_k) on any axis.
+ * A point box (qlo == qhi) and a flat box are valid; -0 and +0 bounds behave alike.  The set is exact, whatever the
+ * tree: (B) is monotone in the tree's box, so a walk that enters a child iff its box passes (B) reaches every member
+ * (DESIGN.md 5g).
+ * Order within a box's list: ascending by the triangle's position in the last build's sort order (tri_ids of
+ * rtbvh_read_sorted; a refit keeps it), as rtbvh_within_async's lists: reproducible down to the byte.
+ * Output in CSR form: dev_offsets[0] = 0, box k's ids are dev_ids[dev_offsets[k] .. dev_offsets[k + 1]), and
+ * dev_offsets[n] is the true total whatever `capacity` is.  An id whose index is >= capacity is not written:
+ * nothing is ever written past dev_ids + capacity, capacity may be 0 (dev_ids may then be NULL), and the caller
+ * compares dev_offsets[n] with capacity. */
+typedef struct {
+    float lo[3];
+    uint32_t reserved0; /* ignored */
+    float hi[3];
+    uint32_t reserved1; /* ignored */
+} rtbvh_box; /* 32 B: two 16-B words */
+enum {
+    RTBVH_OVERLAP_SORT = 1u << 1,     /* walk the boxes in the Morton order of their centres: same output */
+    RTBVH_OVERLAP_COUNT = 1u << 2,    /* count boxes, ids and steps for rtbvh_overlap_counts (slower) */
+    RTBVH_OVERLAP_TRIANGLE = 1u << 3, /* members must also pass the triangle-box test (T) above */
+    RTBVH_OVERLAP_SIZES = 1u << 4,    /* write dev_offsets only; dev_ids may be NULL */
+    RTBVH_OVERLAP_FILL = 1u << 5      /* dev_offsets is INPUT (from a SIZES call for the same boxes, tree and
+                                         TRIANGLE bit): write the ids only */
+    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG */
+};
+/* n boxes at dev_boxes (16-B aligned), n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` ids at
+ * dev_ids (device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the context stream).
+ * Mode 0 runs the sizes pass, a scan of the offsets on the device and the fill pass in one call, with no host round
+ * trip; RTBVH_OVERLAP_SIZES then RTBVH_OVERLAP_FILL is the two-call form for a caller who sizes dev_ids from
+ * dev_offsets[n].  A FILL over any non-decreasing offsets writes box k's ids only inside
+ * [dev_offsets[k], min(dev_offsets[k + 1], capacity)): offsets of another tree or of other boxes truncate lists, they
+ * never make a write go astray.  RTBVH_OVERLAP_SORT's key is the 30-bit Morton code, in the root box, of the box's
+ * centre (lo + hi) * 0.5f, as RTBVH_NEAREST_SORT's of its point; one permutation serves both passes.
+ * Everything else follows rtbvh_within_async one for one: the walk reads the tree the last build or refit wrote
+ * (node records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and
+ * only enqueues; the library orders it among all the other queries, and the next build waits for it.  The first
+ * RTBVH_OVERLAP_SORT query and each larger one grow the sort's buffers, and the first query that writes offsets and
+ * each larger one grow the scan's block sums: growing waits on the host for the outstanding queries.
+ * n == 0 returns RTBVH_OK and writes dev_offsets[0] = 0 only if dev_offsets is non-NULL; RTBVH_ERR_NOT_READY before
+ * a build and after a vertex update until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL boxes or offsets
+ * with n > 0, NULL ids with capacity > 0 outside RTBVH_OVERLAP_SIZES, bad mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit loses that subtree's ids -- both passes lose them identically, so
+ * offsets and ids stay consistent -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_overlap_async(rtbvh_ctx* ctx, const rtbvh_box* dev_boxes, uint64_t n, uint64_t* dev_offsets,
+                                 uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (n + 1) and ids are
+ * host arrays; ids receives min(total, capacity) entries.  With RTBVH_OVERLAP_FILL, offsets is read. */
+rtbvh_status rtbvh_overlap_host(rtbvh_ctx* ctx, const rtbvh_box* boxes, uint64_t n, uint64_t* offsets,
+                                uint32_t* ids, uint64_t capacity, uint32_t mode);
+/* The last RTBVH_OVERLAP_COUNT query (waits for it): boxes, ids (the true total, counted once), internal-node
+ * steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts keep theirs.
+ * RTBVH_ERR_NOT_READY before any counting box query. */
+rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

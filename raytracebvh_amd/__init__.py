@@ -3,16 +3,17 @@ Fierykev/RayTraceBVH) as hand-written HIP kernels for gfx950 behind a C ABI
 (include/rtbvh.h, librtbvh.so).  This package is the thin host-side mirror of the
 reference's Manager/Graphics + ObjLoader surface; all compute is in the HIP library.
 """
-from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALLHITS_SORT,
+from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALLHITS_SORT, BOX_DTYPE,
                    DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_FIRST, FLAG_REFRACT_RECORDS,
                    FLAG_SORT_BOUNCE, FLAG_TIMING, FLAG_AUTO_WALK, FLAG_PACKET_PRIMARY,
                    FLAG_REFILL_BOUNCE, FLAG_WIDE_BVH, FLAG_BINNED_PRIMARY, FLAG_CERTIFIED, FLAG_MULTI_KERNEL_BUILD, FLAG_SPLIT_SHIFT,
                    FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
                    NEAREST_SORT, NODE_DTYPE, PAIR_DTYPE, POINT_DTYPE, QUERY_ANY,
+                   OVERLAP_COUNT, OVERLAP_FILL, OVERLAP_SIZES, OVERLAP_SORT, OVERLAP_TRIANGLE,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
-from .graphics import (Context, Graphics, check_nearest_points, check_query_rays, check_vertex_array, comm_destroy,
-                       comm_unique_id, make_points, make_rays, save_bmp)
+from .graphics import (Context, Graphics, check_nearest_points, check_overlap_boxes, check_query_rays,
+                       check_vertex_array, comm_destroy, comm_unique_id, make_boxes, make_points, make_rays, save_bmp)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
                     camera_reference, load_npz, load_obj, synthetic)
 
@@ -28,4 +29,6 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "POINT_DTYPE", "NEAREST_DTYPE", "NEAREST_SORT", "NEAREST_COUNT", "make_points", "check_nearest_points",
            "PAIR_DTYPE", "WITHIN_SORT", "WITHIN_COUNT", "WITHIN_SIZES", "WITHIN_FILL",
            "ALLHITS_SORT", "ALLHITS_COUNT", "ALLHITS_BY_T", "ALLHITS_SIZES", "ALLHITS_FILL",
+           "BOX_DTYPE", "OVERLAP_SORT", "OVERLAP_COUNT", "OVERLAP_TRIANGLE", "OVERLAP_SIZES", "OVERLAP_FILL",
+           "make_boxes", "check_overlap_boxes",
            "check_query_rays", "check_vertex_array"]

@@ -305,11 +305,13 @@ struct rtbvh_ctx {
     // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
     // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
     DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts,
-                                             //   the radius queries' counts, the all-hits queries' counts
+                                             //   the radius queries' counts, the all-hits queries' counts, the box
+                                             //   queries' counts
     Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
     Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
     Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
-    Grown<unsigned long long> d_qscan;       // rtbvh_within_async, rtbvh_allhits_async: the offset scan's block sums
+    Grown<unsigned long long> d_qscan;       // rtbvh_within_async, rtbvh_allhits_async, rtbvh_overlap_async: the offset
+                                             //   scan's block sums
     Grown<uint32_t> d_qorder;                // RTBVH_ALLHITS_BY_T: 2 arrays of cap / 2 words (each ray's stored hits, the
                                              //   rays with long lists); grown on demand
     Event ev_query;
@@ -320,6 +322,7 @@ struct rtbvh_ctx {
     bool nearest_counted = false;            // the closest-point count block holds a RTBVH_NEAREST_COUNT query's counts
     bool within_counted = false;             // the radius queries' count block holds a RTBVH_WITHIN_COUNT query's counts
     bool allhits_counted = false;            // the all-hits count block holds a RTBVH_ALLHITS_COUNT query's counts
+    bool overlap_counted = false;            // the box queries' count block holds a RTBVH_OVERLAP_COUNT query's counts
 };
 
 namespace {
@@ -2756,6 +2759,139 @@ rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_ALLHITS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- box-overlap queries -------------------------------------------------------------------------------
+// rtbvh_within_async's rules, one for one, and its place in the ev_query chain; [keys + sort], then
+// [sizes + scan], then [fill], all on the caller's stream.  Its count block is QUERY_OVERLAP_AT.
+rtbvh_status rtbvh_overlap_async(rtbvh_ctx* c, const rtbvh_box* dev_boxes, uint64_t n, uint64_t* dev_offsets,
+                                 uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_OVERLAP_SORT | RTBVH_OVERLAP_COUNT | RTBVH_OVERLAP_TRIANGLE | RTBVH_OVERLAP_SIZES |
+                             RTBVH_OVERLAP_FILL;
+    constexpr uint32_t BOTH = RTBVH_OVERLAP_SIZES | RTBVH_OVERLAP_FILL;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: 2^31 boxes or more");
+    const bool sizes = !(mode & RTBVH_OVERLAP_FILL), fill = !(mode & RTBVH_OVERLAP_SIZES);
+    static_assert(sizeof(rtbvh_box) == 32 && sizeof(uint64_t) == sizeof(unsigned long long), "box query layouts");
+    if (n == 0) {
+        if (!dev_offsets || !sizes) return RTBVH_OK;
+        HIPC(c, hipSetDevice(c->cfg.device));
+        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+        return RTBVH_OK;
+    }
+    if (!dev_boxes || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: NULL boxes or offsets");
+    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: NULL ids");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "overlap before build");
+    if (c->stale) return fail_stale(c, "overlap");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_OVERLAP_SORT) != 0, count = (mode & RTBVH_OVERLAP_COUNT) != 0;
+    const bool tri = (mode & RTBVH_OVERLAP_TRIANGLE) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
+    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
+    if (grow_sort || grow_scan) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort and scan in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        if (grow_sort) {
+            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+        }
+        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_OVERLAP_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    OverlapArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.boxes = reinterpret_cast<const float4*>(dev_boxes);
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.ids = dev_ids;
+    a.capacity = capacity;
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_OVERLAP_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {   // one permutation for both passes
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_overlap_keys(a.boxes, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_ids = true;
+        launch_overlap(a, false, count, tri, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_ids = !sizes;
+        launch_overlap(a, true, count, tri, s);
+    }
+    rtbvh_status st = check_launch(c, "overlap kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->overlap_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_overlap_host(rtbvh_ctx* c, const rtbvh_box* boxes, uint64_t n, uint64_t* offsets, uint32_t* ids,
+                                uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_OVERLAP_FILL) != 0, sizes_only = (mode & RTBVH_OVERLAP_SIZES) != 0;
+    if (n == 0) {   // (nothing to stage)
+        const rtbvh_status st = rtbvh_overlap_async(c, boxes, 0, nullptr, ids, capacity, mode, nullptr);
+        if (!st && offsets && !fill_only) offsets[0] = 0;
+        return st;
+    }
+    if (n >= (1ull << 31) || !boxes || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
+        !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_overlap_async(c, boxes, n, offsets, ids, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // offsets, then boxes: 8- and 16-B aligned
+    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
+    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_box)));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
+    rtbvh_box* db = reinterpret_cast<rtbvh_box*>(d + off_bytes);
+    if (hipMemcpy(db, boxes, (size_t)n * sizeof(rtbvh_box), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "overlap_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "overlap_host: upload failed");
+    DevBuf<uint32_t> dids;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another tree or other boxes leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
+    TRY(rtbvh_overlap_async(c, db, n, doff, dids, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "overlap_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "overlap_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "overlap_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->overlap_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_OVERLAP_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_OVERLAP_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

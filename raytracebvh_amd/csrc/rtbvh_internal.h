@@ -423,7 +423,6 @@ struct AllhitsArgs {
 };
 // the all-hits queries' own count block, behind the radius queries'
 constexpr uint32_t QUERY_ALLHITS_AT = QUERY_WITHIN_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_ALLHITS_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_ALLHITS_AT % 2 == 0, "the count block's 8-byte words");
 void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s);
 // RTBVH_ALLHITS_BY_T: each ray's stored hits [offsets[r], offsets[r] + written[r]) ordered by (t, tri), in place.
@@ -440,5 +439,37 @@ void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s);
 constexpr uint32_t ALLHITS_LANE_MAX = RTBVH_ALLHITS_LANE_MAX, ALLHITS_LDS_MAX = RTBVH_ALLHITS_LDS_MAX;
 void launch_allhits_order(float4* hits, const unsigned long long* offsets, const uint32_t* written, uint32_t n,
                           uint32_t* list, uint32_t* list_n, hipStream_t s);
+
+// ---- box-overlap queries (trace.hip k_overlap; rtbvh_overlap_async) ----------
+// Query boxes (two float4 each: {lo.xyz, -}, {hi.xyz, -}) on the same tree forms, WithinArgs' CSR output with a
+// triangle id per entry: a sizes pass stores box r's count at offsets[r + 1], scan_offsets makes offsets of them, a
+// fill pass stores box r's ids at [offsets[r], min(offsets[r + 1], capacity)).
+struct OverlapArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* boxes;      // [2n]
+    unsigned long long* offsets;    // [n + 1]: the sizes pass writes [1, n], the fill pass reads
+    uint32_t* ids;            // the fill pass: [capacity] triangle ids
+    unsigned long long capacity;
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_OVERLAP_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_OVERLAP_COUNT: [4] boxes, ids, internal-node steps, leaf steps
+    bool count_ids;           // ... this pass adds the boxes and ids (one pass of a call does), not only steps
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the box queries' own count block, behind the all-hits queries'
+constexpr uint32_t QUERY_OVERLAP_AT = QUERY_ALLHITS_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_OVERLAP_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_OVERLAP_AT % 2 == 0, "the count block's 8-byte words");
+void launch_overlap(const OverlapArgs& a, bool fill, bool count, bool tri, hipStream_t s);
+// RTBVH_OVERLAP_SORT's keys (the box centres' 30-bit Morton codes in the root box) and vals[i] = i
+void launch_overlap_keys(const float4* boxes, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                         hipStream_t s);
 
 }  // namespace rtbvh

@@ -3147,7 +3147,199 @@ __global__ __launch_bounds__(BLOCK) void k_allhits_order_block(float4* hits, con
     }
 }
 
+// ---- box-overlap queries (rtbvh_overlap_async): caller boxes in, every triangle that meets the box out ----------
+// k_within's frame and CSR protocol with a triangle id per entry.  The node test (B) is comparisons only:
+// qlo <= hi && lo <= qhi on every axis, closed, false for a NaN.  It is monotone in the tree's box, so entering a
+// child iff its box passes reaches every member with no margin; the walk is left-first, which is the
+// order of a box's list.  A leaf tests its record's own box, then, under TRI, the triangle-box separating axes (T)
+// of include/rtbvh.h, operation for operation, fp32 without contraction.
+// (T): true iff one of the plane's axis and the nine edge axes separates the triangle {a, a + e1, a + e2} from the
+// box [qlo, qhi].  A NaN compares false everywhere: it does not separate.
+__device__ __forceinline__ bool tri_box_separated(f3 qlo, f3 qhi, f3 a, f3 e1, f3 e2) {
+    const f3 c = mk((qlo.x + qhi.x) * 0.5f, (qlo.y + qhi.y) * 0.5f, (qlo.z + qhi.z) * 0.5f);
+    const f3 h = mk((qhi.x - qlo.x) * 0.5f, (qhi.y - qlo.y) * 0.5f, (qhi.z - qlo.z) * 0.5f);
+    const f3 v0 = mk(a.x - c.x, a.y - c.y, a.z - c.z);
+    const f3 v1 = mk(v0.x + e1.x, v0.y + e1.y, v0.z + e1.z);
+    const f3 v2 = mk(v0.x + e2.x, v0.y + e2.y, v0.z + e2.z);
+    const f3 nn = mk(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+    const float d = (nn.x * v0.x + nn.y * v0.y) + nn.z * v0.z;
+    const float r = (h.x * fabsf(nn.x) + h.y * fabsf(nn.y)) + h.z * fabsf(nn.z);
+    if (d > r || d < -r) return true;
+    bool sep = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {   // unrolled: kept as a loop (unroll 1) it takes 15 registers more, to select f
+        const f3 f = k == 0 ? e1 : k == 1 ? mk(e2.x - e1.x, e2.y - e1.y, e2.z - e1.z) : e2;
+        const f3 g = mk(fabsf(f.x), fabsf(f.y), fabsf(f.z));
+        float p0 = v0.z * f.y - v0.y * f.z, p1 = v1.z * f.y - v1.y * f.z, p2 = v2.z * f.y - v2.y * f.z;   // x
+        float rr = h.y * g.z + h.z * g.y;
+        sep |= fminf(fminf(p0, p1), p2) > rr || fmaxf(fmaxf(p0, p1), p2) < -rr;
+        p0 = v0.x * f.z - v0.z * f.x, p1 = v1.x * f.z - v1.z * f.x, p2 = v2.x * f.z - v2.z * f.x;           // y
+        rr = h.x * g.z + h.z * g.x;
+        sep |= fminf(fminf(p0, p1), p2) > rr || fmaxf(fmaxf(p0, p1), p2) < -rr;
+        p0 = v0.y * f.x - v0.x * f.y, p1 = v1.y * f.x - v1.x * f.y, p2 = v2.y * f.x - v2.x * f.y;           // z
+        rr = h.x * g.y + h.y * g.x;
+        sep |= fminf(fminf(p0, p1), p2) > rr || fmaxf(fmaxf(p0, p1), p2) < -rr;
+    }
+    return sep;
+}
+
+// (B) on a box given as its corners
+__device__ __forceinline__ bool boxes_meet(f3 qlo, f3 qhi, f3 lo, f3 hi) {
+    return qlo.x <= hi.x && lo.x <= qhi.x && qlo.y <= hi.y && lo.y <= qhi.y && qlo.z <= hi.z && lo.z <= qhi.z;
+}
+
+// FILL = false counts a box's members and stores the count at offsets[r + 1]; FILL = true stores the ids at
+// offsets[r] + i while that is below min(offsets[r + 1], capacity), as k_within its pairs: whatever the offsets
+// hold, no store leaves the box's segment or the first `capacity` ids.
+// Every instance fits 64 registers without a spill at 8 waves per SIMD.
+template <bool FILL, bool COUNT, bool NB, bool TRI>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_overlap(OverlapArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nboxes = 0;
+    unsigned long long nids = 0;
+    bool has = false;
+    uint32_t r = 0, cnt = 0;
+    unsigned long long pos = 0, end = 0;   // FILL: the next id's index and the end of the box's segment
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    f3 qlo = mk(0.f, 0.f, 0.f), qhi = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th box of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 b0 = a.boxes[2 * (size_t)r], b1 = a.boxes[2 * (size_t)r + 1];
+            qlo = mk(b0.x, b0.y, b0.z);
+            qhi = mk(b1.x, b1.y, b1.z);
+            if (COUNT && a.count_ids) nboxes++;
+            const bool finite = fabsf(qlo.x) < INFINITY && fabsf(qlo.y) < INFINITY && fabsf(qlo.z) < INFINITY &&
+                                fabsf(qhi.x) < INFINITY && fabsf(qhi.y) < INFINITY && fabsf(qhi.z) < INFINITY;
+            if (!finite || !(qlo.x <= qhi.x && qlo.y <= qhi.y && qlo.z <= qhi.z)) {   // no walk: an empty list
+                if (!FILL) a.offsets[(size_t)r + 1] = 0;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[r];
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            bool in = boxes_meet(qlo, qhi, mk(q2.z, q2.w, q3.x), mk(q3.y, q3.z, q3.w));   // the leaf's own box first
+            if (TRI && in)
+                in = !tri_box_separated(qlo, qhi, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x));
+            if (in) {
+                if (!FILL || COUNT) cnt++;
+                if (FILL && pos < end) {
+                    a.ids[pos] = __float_as_uint(q2.y) & ~LEAF_BIT;
+                    pos++;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = boxes_meet(qlo, qhi, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const bool rh = boxes_meet(qlo, qhi, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            if (!FILL) a.offsets[(size_t)r + 1] = cnt;
+            if (COUNT && a.count_ids) nids += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nboxes, nids, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
+// RTBVH_OVERLAP_SORT's key: the 30-bit Morton code of the box's centre in the root box (k_nearest_keys' code)
+__global__ __launch_bounds__(BLOCK) void k_overlap_keys(const float4* __restrict__ boxes, uint32_t n,
+                                                        const float* __restrict__ box, uint32_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 lo = boxes[2 * (size_t)i], hi = boxes[2 * (size_t)i + 1];
+    keys[i] = spread9(q9((lo.x + hi.x) * 0.5f, box[0], box[3])) << 2 |
+              spread9(q9((lo.y + hi.y) * 0.5f, box[1], box[4])) << 1 | spread9(q9((lo.z + hi.z) * 0.5f, box[2], box[5]));
+    vals[i] = i;
+}
+
 }  // namespace
+
+void launch_overlap(const OverlapArgs& a, bool fill, bool count, bool tri, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto FILL, auto COUNT, auto NB, auto TRI) {
+        hipLaunchKernelGGL((k_overlap<FILL, COUNT, NB, TRI>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.nb, tri);
+}
+
+void launch_overlap_keys(const float4* boxes, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                         hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_overlap_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, boxes, n, box, keys, vals);
+}
 
 void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s) {
     if (a.n == 0) return;

@@ -134,6 +134,68 @@ def check_nearest_points(points, max_dist2=float("inf"), device=None):
     return "numpy", points.view(_L.POINT_DTYPE).reshape(-1)
 
 
+def make_boxes(lo, hi):
+    """Packs (N, 3) lower and upper corners as box queries: torch tensors give an (N, 8) float32 tensor on their
+    device, anything else a BOX_DTYPE array (include/rtbvh.h rtbvh_box).  The boxes live in the space the BVH was
+    built in."""
+    if _is_tensor(lo) or _is_tensor(hi):
+        import torch
+        dev = lo.device if _is_tensor(lo) else hi.device
+        a = torch.as_tensor(lo, dtype=torch.float32, device=dev).reshape(-1, 3)
+        b = torch.as_tensor(hi, dtype=torch.float32, device=dev).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError(f"make_boxes: {tuple(a.shape)} lower and {tuple(b.shape)} upper corners")
+        out = torch.zeros((a.shape[0], 8), dtype=torch.float32, device=dev)
+        out[:, 0:3] = a
+        out[:, 4:7] = b
+        return out
+    a = np.asarray(lo, np.float32).reshape(-1, 3)
+    b = np.asarray(hi, np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"make_boxes: {a.shape} lower and {b.shape} upper corners")
+    out = np.zeros(len(a), _L.BOX_DTYPE)
+    out["lo"] = a
+    out["hi"] = b
+    return out
+
+
+def check_overlap_boxes(boxes, hi=None, device=None):
+    """Context.overlap's input check: ("torch", boxes) for an (N, 8) float32 contiguous CUDA tensor (on `device`
+    when given), ("numpy", BOX_DTYPE array) for a C-contiguous BOX_DTYPE array or (N, 8) float32 array, or for
+    (N, 3) float32 lower corners with `hi` their (N, 3) float32 upper corners (packed with make_boxes); ValueError
+    for anything else, and for a `hi` given beside boxes that carry their own.  Calls nothing in the library."""
+    if _is_tensor(boxes):
+        import torch
+        if hi is not None:
+            raise ValueError("overlap: an (N, 8) tensor carries its upper corners (make_boxes)")
+        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 8:
+            raise ValueError(f"overlap: boxes must be an (N, 8) float32 tensor (make_boxes), got "
+                             f"{tuple(boxes.shape)} {boxes.dtype}")
+        if not boxes.is_cuda:
+            raise ValueError("overlap: a torch tensor of boxes must be on the context's GPU (numpy arrays take the "
+                             "host path)")
+        if device is not None and boxes.device.index != device:
+            raise ValueError(f"overlap: boxes on {boxes.device}, the context on device {device}")
+        if not boxes.is_contiguous():
+            raise ValueError("overlap: boxes must be contiguous")
+        return "torch", boxes
+    if not isinstance(boxes, np.ndarray):
+        raise ValueError("overlap: boxes must be a torch CUDA tensor or a numpy array")
+    if hi is not None:
+        if not isinstance(hi, np.ndarray) or boxes.dtype != np.float32 or hi.dtype != np.float32 or boxes.ndim != 2 or \
+                boxes.shape[1] != 3 or hi.shape != boxes.shape:
+            raise ValueError("overlap: lower and upper corners must be (N, 3) float32 arrays of one shape")
+        return "numpy", make_boxes(boxes, hi)
+    if boxes.dtype == _L.BOX_DTYPE:
+        if boxes.ndim != 1:
+            raise ValueError(f"overlap: a BOX_DTYPE array must be one-dimensional, got shape {boxes.shape}")
+    elif boxes.dtype != np.float32 or boxes.ndim != 2 or boxes.shape[1] != 8:
+        raise ValueError(f"overlap: boxes must be BOX_DTYPE or (N, 8) float32, got {boxes.shape} {boxes.dtype}")
+    if not boxes.flags["C_CONTIGUOUS"]:
+        raise ValueError("overlap: boxes must be C-contiguous")
+    return "numpy", boxes.view(_L.BOX_DTYPE).reshape(-1)
+
+
 def check_vertex_array(a, what="positions", device=None):
     """Context.update_vertices' input check: (kind, array, stride in floats) for an (n, 3) float32 torch CUDA
     tensor ("torch"; on `device` when given) or numpy array ("numpy") whose last dimension is contiguous and
@@ -585,6 +647,88 @@ class Context:
         out = np.zeros(4, np.uint64)
         self._check(_L.lib().rtbvh_allhits_counts(self._h, _L.ptr(out)))
         return dict(zip(("rays", "hits", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
+    # -- box-overlap queries --
+    def overlap(self, boxes, hi=None, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
+        """rtbvh_overlap_async / rtbvh_overlap_host: for each axis-aligned box every triangle whose leaf box meets it
+        (closed intervals) and, with OVERLAP_TRIANGLE, that also passes the header's triangle-box test, as
+        (offsets, ids) in CSR form: box k's triangle ids are ids[offsets[k]:offsets[k + 1]], in the last build's sort
+        order (read_sorted), and offsets[n] is the total.
+
+        `boxes`: make_boxes' output, or (N, 3) float32 lower corners with `hi` the upper ones (numpy).  A numpy input
+        goes through the synchronous host entry and returns a uint64 (n + 1,) array and a uint32 array of offsets[n]
+        ids (of min(offsets[n], capacity) when `capacity` is given).  A torch CUDA (N, 8) tensor goes to the device
+        entry, enqueued on `stream` as nearest's, and returns an int64 (n + 1,) device tensor and an int32
+        (capacity,) device tensor whose entries [0, min(total, capacity)) are written.  With `capacity` given that
+        is one call, with no host copy and no synchronisation -- compare offsets[-1] with it afterwards; with
+        capacity=None an OVERLAP_SIZES call, one .item() read of the total (the only synchronisation) and an
+        OVERLAP_FILL call.  sizes_only=True returns the offsets alone.  mode: OVERLAP_SORT, OVERLAP_COUNT,
+        OVERLAP_TRIANGLE (OVERLAP_SIZES and OVERLAP_FILL are this method's to set).  ValueError for a wrong shape,
+        dtype, device or layout."""
+        kind, bx = check_overlap_boxes(boxes, hi, getattr(self, "device", None))
+        if mode & (_L.OVERLAP_SIZES | _L.OVERLAP_FILL):
+            raise ValueError("overlap: OVERLAP_SIZES and OVERLAP_FILL are set by overlap itself")
+        if mode & ~(_L.OVERLAP_SORT | _L.OVERLAP_COUNT | _L.OVERLAP_TRIANGLE):
+            raise ValueError(f"overlap: unknown mode bits {mode:#x}")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"overlap: capacity must be a non-negative integer, got {capacity!r}")
+        if sizes_only and capacity is not None:
+            raise ValueError("overlap: sizes_only takes no capacity")
+        n = len(bx)
+        L = _L.lib()
+        if kind == "numpy":
+            offsets = np.zeros(n + 1, np.uint64)
+            p, o = ctypes.c_void_p(bx.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                ids = np.zeros(int(capacity), np.uint32)
+                self._check(L.rtbvh_overlap_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
+                return offsets, ids[:min(int(offsets[n]), len(ids))]
+            self._check(L.rtbvh_overlap_host(self._h, p, n, o, None, 0, mode | _L.OVERLAP_SIZES))
+            if sizes_only:
+                return offsets
+            ids = np.zeros(int(offsets[n]), np.uint32)
+            self._check(L.rtbvh_overlap_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
+                                             mode | _L.OVERLAP_FILL))
+            return offsets, ids
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=bx.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(bx.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(bx.device).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        p, o = ctypes.c_void_p(bx.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
+
+        def call(ids, m):
+            self._check(L.rtbvh_overlap_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
+                                              and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            ids = torch.empty(int(capacity), dtype=torch.int32, device=bx.device)
+            call(ids, mode)
+            return offsets, ids
+        call(None, mode | _L.OVERLAP_SIZES)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=bx.device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        ids = torch.empty(total, dtype=torch.int32, device=bx.device)
+        call(ids, mode | _L.OVERLAP_FILL)
+        return offsets, ids
+
+    def overlap_counts(self) -> dict:
+        """rtbvh_overlap_counts: boxes, ids (the total), internal-node and leaf steps (summed over the passes) of
+        the last OVERLAP_COUNT query (the other queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_overlap_counts(self._h, _L.ptr(out)))
+        return dict(zip(("boxes", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
