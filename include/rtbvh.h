@@ -347,8 +347,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
- * rtbvh_within_*, rtbvh_allhits_*, rtbvh_overlap_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the
- * rtbvh_read_* calls return the last build's tree.
+ * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY,
+ * and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -582,6 +582,48 @@ rtbvh_status rtbvh_within_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64
  * steps and leaf steps summed over the passes the call ran.  Its own words: the ray and closest-point counts keep
  * theirs.  RTBVH_ERR_NOT_READY before any counting radius query. */
 rtbvh_status rtbvh_within_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- k-nearest queries: the k closest triangles to points the caller chose ----------------------
+ * (No reference equivalent.)  Same points (rtbvh_point: {point.xyz, max_dist2}), same space and the same dist2 as
+ * the closest-point queries above -- a triangle's dist2 is that section's, from the leaf record, fp32, no
+ * contraction, with the clamp into the leaf's box.  The result for p with bound max_dist2 and k is the k
+ * lexicographically smallest (dist2, triangle id) among the triangles with dist2 <= max_dist2 (the id in triangle
+ * order, Node.index / 3), in ascending order.  The order is total, so the result is a function of the point and the
+ * triangles alone: whatever the tree, the walk order or the mode, down to the byte.  A NaN dist2 is never a member.
+ * There is no walk, and every slot holds "none", where the closest-point query has no walk: !(max_dist2 >= 0) (NaN
+ * included) or a non-finite coordinate.  -0 counts as +0; max_dist2 = +inf means no limit.  With k = 1 the pair is
+ * rtbvh_nearest's (tri, dist2).  The list is exact: dist2 is never below the distance to a box that contains the
+ * leaf box, and the walk prunes on box distance <= the dist2 of the worst of the k kept so far, which is never below
+ * the final one's.
+ * Output: n * k records of the radius queries' 8-B rtbvh_pair, point i's at [i * k, (i + 1) * k); a slot past the
+ * number found holds {0xFFFFFFFF, -1.0f}.  No CSR, no second pass, no capacity. */
+#define RTBVH_KNN_MAX_K 32
+enum {
+    RTBVH_KNN_SORT = 1u << 1,  /* walk the points in Morton order (as RTBVH_NEAREST_SORT): same output */
+    RTBVH_KNN_COUNT = 1u << 2  /* count for rtbvh_knn_counts (slower) */
+    /* (every other bit is rejected) */
+};
+/* n points at dev_points and room for n * k pairs at dev_pairs (device memory of the context's device, 8-B aligned),
+ * enqueued on `stream` (hipStream_t, NULL = the context stream).  k == 0 or k > RTBVH_KNN_MAX_K is
+ * RTBVH_ERR_INVALID_ARG.
+ * Everything else follows rtbvh_nearest_async one for one: the walk reads the tree the last build or refit wrote
+ * (node records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and
+ * only enqueues; the library orders it among all the other queries, and the next build waits for it.  The first
+ * RTBVH_KNN_SORT query and each larger one grow the sort's buffers (shared with the other queries' SORT), which
+ * waits on the host.  n == 0 returns RTBVH_OK and touches nothing, even before a build; RTBVH_ERR_NOT_READY before
+ * a build and after a vertex update until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL pointers with
+ * n > 0, bad mode bits, a bad k and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit ends with the best list found so far, and the next synchronising call
+ * returns RTBVH_ERR_STACK_OVERFLOW: every pair of that list is a genuine (tri, dist2), the list is ascending, and
+ * slot by slot it is never lexicographically below the true one. */
+rtbvh_status rtbvh_knn_async(rtbvh_ctx* ctx, const rtbvh_point* dev_points, uint64_t n, uint32_t k,
+                             rtbvh_pair* dev_pairs, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_knn_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64_t n, uint32_t k, rtbvh_pair* pairs,
+                            uint32_t mode);
+/* The last RTBVH_KNN_COUNT query (waits for it): points, pairs found, internal-node steps, leaf steps.  Its own
+ * words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting k-nearest query. */
+rtbvh_status rtbvh_knn_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- all-hits ray queries: every triangle a ray crosses within t_max ----------------------------
  * (No reference equivalent.)  Space, rays and hits are the ray queries' above: rtbvh_ray in, rtbvh_hit

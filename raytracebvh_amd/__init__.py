@@ -7,7 +7,7 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    DELTA_CLZ64, DELTA_CPUTESTS, FLAG_COUNT_VISITS, FLAG_NEAREST_FIRST, FLAG_REFRACT_RECORDS,
                    FLAG_SORT_BOUNCE, FLAG_TIMING, FLAG_AUTO_WALK, FLAG_PACKET_PRIMARY,
                    FLAG_REFILL_BOUNCE, FLAG_WIDE_BVH, FLAG_BINNED_PRIMARY, FLAG_CERTIFIED, FLAG_MULTI_KERNEL_BUILD, FLAG_SPLIT_SHIFT,
-                   FLAG_GRAPH, HIT_DTYPE, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
+                   FLAG_GRAPH, HIT_DTYPE, KNN_COUNT, KNN_MAX_K, KNN_SORT, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
                    NEAREST_SORT, NODE_DTYPE, PAIR_DTYPE, POINT_DTYPE, QUERY_ANY,
                    OVERLAP_COUNT, OVERLAP_FILL, OVERLAP_SIZES, OVERLAP_SORT, OVERLAP_TRIANGLE,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
@@ -28,6 +28,7 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "make_rays",
            "POINT_DTYPE", "NEAREST_DTYPE", "NEAREST_SORT", "NEAREST_COUNT", "make_points", "check_nearest_points",
            "PAIR_DTYPE", "WITHIN_SORT", "WITHIN_COUNT", "WITHIN_SIZES", "WITHIN_FILL",
+           "KNN_SORT", "KNN_COUNT", "KNN_MAX_K",
            "ALLHITS_SORT", "ALLHITS_COUNT", "ALLHITS_BY_T", "ALLHITS_SIZES", "ALLHITS_FILL",
            "BOX_DTYPE", "OVERLAP_SORT", "OVERLAP_COUNT", "OVERLAP_TRIANGLE", "OVERLAP_SIZES", "OVERLAP_FILL",
            "make_boxes", "check_overlap_boxes",

@@ -323,6 +323,7 @@ struct rtbvh_ctx {
     bool within_counted = false;             // the radius queries' count block holds a RTBVH_WITHIN_COUNT query's counts
     bool allhits_counted = false;            // the all-hits count block holds a RTBVH_ALLHITS_COUNT query's counts
     bool overlap_counted = false;            // the box queries' count block holds a RTBVH_OVERLAP_COUNT query's counts
+    bool knn_counted = false;                // the k-nearest queries' count block holds a RTBVH_KNN_COUNT query's counts
 };
 
 namespace {
@@ -2893,6 +2894,99 @@ rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_OVERLAP_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- k-nearest queries ---------------------------------------------------------------------------------
+// rtbvh_nearest_async's rules and its place in the ev_query chain; one walk, no second pass.  Its count block is
+// QUERY_KNN_AT.
+rtbvh_status rtbvh_knn_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, uint32_t k, rtbvh_pair* dev_pairs,
+                             uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_KNN_SORT | RTBVH_KNN_COUNT))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "knn: unknown mode bits");
+    if (k == 0 || k > RTBVH_KNN_MAX_K) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: k must be 1 .. RTBVH_KNN_MAX_K");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: 2^31 points or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_points || !dev_pairs) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: NULL points or pairs");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "knn before build");
+    if (c->stale) return fail_stale(c, "knn");
+    static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_pair) == 8, "k-nearest record layouts");
+    static_assert(RTBVH_KNN_MAX_K == KNN_MAX_K, "the largest list of k_knn");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_KNN_SORT) != 0, count = (mode & RTBVH_KNN_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_KNN_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    KnnArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.points = reinterpret_cast<const float4*>(dev_points);
+    a.pairs = reinterpret_cast<uint2*>(dev_pairs);
+    a.n = N;
+    a.k = k;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_KNN_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    launch_knn(a, count, s);
+    rtbvh_status st = check_launch(c, "knn kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->knn_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_knn_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, uint32_t k, rtbvh_pair* pairs,
+                            uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || k == 0 || k > RTBVH_KNN_MAX_K || !points || !pairs || !c->tree.built ||
+        c->stale)   // (nothing to stage: the query's checks)
+        return rtbvh_knn_async(c, points, n, k, pairs, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;
+    const size_t out_bytes = (size_t)n * k * sizeof(rtbvh_pair);
+    HIPC(c, d.alloc(out_bytes + (size_t)n * sizeof(rtbvh_point)));
+    rtbvh_pair* dk = reinterpret_cast<rtbvh_pair*>(d.h);
+    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + out_bytes);
+    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "knn_host: upload failed");
+    TRY(rtbvh_knn_async(c, dp, n, k, dk, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "knn_host: sync");
+    if (hipMemcpy(pairs, dk, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "knn_host: download failed");
+    return rtbvh_synchronize(c);   // (the lists are the best found when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_knn_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->knn_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_KNN_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_KNN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS, hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 

@@ -465,11 +465,38 @@ struct OverlapArgs {
 };
 // the box queries' own count block, behind the all-hits queries'
 constexpr uint32_t QUERY_OVERLAP_AT = QUERY_ALLHITS_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_OVERLAP_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_OVERLAP_AT % 2 == 0, "the count block's 8-byte words");
 void launch_overlap(const OverlapArgs& a, bool fill, bool count, bool tri, hipStream_t s);
 // RTBVH_OVERLAP_SORT's keys (the box centres' 30-bit Morton codes in the root box) and vals[i] = i
 void launch_overlap_keys(const float4* boxes, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
                          hipStream_t s);
+
+// ---- k-nearest queries (trace.hip k_knn; rtbvh_knn_async) --------------------
+// NearestArgs' points on the same tree forms; point r's k (triangle, dist2) pairs, ascending in (dist2, triangle),
+// at pairs[r * k .. r * k + k), the slots past the number found {0xFFFFFFFF, -1.0f}.
+struct KnnArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* points;     // [n]
+    uint2* pairs;             // [n * k] {triangle, dist2 bits}
+    uint32_t n;
+    uint32_t k;               // 1 .. KNN_MAX_K
+    const uint32_t* perm;     // walk order (RTBVH_KNN_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_KNN_COUNT: [4] points, pairs found, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+constexpr uint32_t KNN_MAX_K = 32;
+// the k-nearest queries' own count block, behind the box queries'
+constexpr uint32_t QUERY_KNN_AT = QUERY_OVERLAP_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_KNN_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_KNN_AT % 2 == 0, "the count block's 8-byte words");
+// the instance whose list capacity (4, 8, 16 or 32 slots a lane) is the smallest that holds k
+void launch_knn(const KnnArgs& a, bool count, hipStream_t s);
 
 }  // namespace rtbvh

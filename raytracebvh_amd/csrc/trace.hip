@@ -2882,6 +2882,178 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_within(WithinArgs a) {
     }
 }
 
+// ---- k-nearest queries (rtbvh_knn_async): caller points in, the k smallest (dist2, triangle) within max_dist2 out --
+// k_nearest's frame with a list in place of the single key.  Each lane keeps k u64 keys (dist2 bits << 32 | id) in
+// ascending order, all started at k_nearest's sentinel (max_dist2 bits, 0xFFFFFFFF): the bound is max_dist2 until the
+// list is full, dist2 == max_dist2 is accepted, a NaN dist2 is above every key, and the slots never filled still hold
+// the sentinel at the end.  `worst` caches slot k - 1; a candidate below it is inserted by shifting the larger keys
+// one slot up (the old worst falls out), and a box -- a child's, or a leaf's own -- is entered iff its distance is <=
+// the worst key's dist2, non-strict, the nearer child first.  DESIGN.md 5h: 5d's lemma with the bound read as the
+// worst key's dist2, which only falls, so a member of the final list was never pruned.
+// The list lives in LDS beside the stack, [slot][lane]: 8 B a lane in one 2 KB row a slot, so a wave's lanes are on
+// distinct banks whatever slot each one touches.  CAP (the slots allocated: 4, 8, 16 or 32) is the smallest tier
+// that holds k, so a small k does not pay the LDS of 32; the loops run to k.  knn_blocks(CAP) blocks fit a CU's
+// 160 KB, which is also what the launch bound asks for: the registers follow the occupancy the LDS allows.
+// The insertion is bound by LDS latency, not traffic: it fetches ROUND keys together and then decides, which took 29%
+// off k = 32 against a key a round.  (In scratch at 8 waves per SIMD, or unordered with a tracked worst slot and a
+// final sort, the walk was slower: DESIGN.md 5h, profiles/knn_ab.json.)
+constexpr int knn_blocks(int cap) {   // blocks (= waves per SIMD) of 16 KB of stack and cap * 2 KB of list in 160 KB
+    const int b = 160 / (16 + 2 * cap);
+    return b < (int)BOUNCE_WAVES ? b : (int)BOUNCE_WAVES;
+}
+struct KnnList {
+    unsigned long long* col;   // this lane's LDS column, slot j at col[j * BLOCK]
+    __device__ __forceinline__ void store(int j, uint64_t v) { col[j * BLOCK] = v; }
+    __device__ __forceinline__ uint64_t load(int j) const { return col[j * BLOCK]; }
+};
+template <int CAP, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, knn_blocks(CAP)) void k_knn(KnnArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const int k = (int)a.k;   // 1 .. CAP
+    constexpr int ROUND = CAP >= 16 ? 8 : 4;   // keys an insertion fetches together
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t npoints = 0, nfound = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    uint64_t worst = 0;   // the list's slot k - 1
+    f3 p = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    __shared__ unsigned long long s_lst[CAP][BLOCK];
+    KnnList lst{&s_lst[0][threadIdx.x]};
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    const uint2 none = make_uint2(INVALID, __float_as_uint(-1.f));
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t i) {   // this lane takes the i-th point of the walk order
+            r = a.perm ? a.perm[i] : i;
+            const float4 pt = a.points[r];
+            p = mk(pt.x, pt.y, pt.z);
+            const float bound = pt.w + 0.f;   // (-0 -> +0: the key's bits order as the floats)
+            if (COUNT) npoints++;
+            const bool finite = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;
+            if (!(bound >= 0.f) || !finite) {   // no walk: every slot none
+                for (int j = 0; j < k; j++) a.pairs[(size_t)r * k + j] = none;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                worst = (uint64_t)__float_as_uint(bound) << 32 | 0xFFFFFFFFull;
+                for (int j = 0; j < k; j++) lst.store(j, worst);
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const float bound = key_t(worst);
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            const f3 lo = mk(q2.z, q2.w, q3.x), hi = mk(q3.y, q3.z, q3.w);   // the leaf's own box first
+            if (box_dist2(p, lo, hi) <= bound) {
+                float u, v;
+                f3 q;
+                const float d = triangle_dist2(p, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), lo,
+                                               hi, u, v, q);
+                const uint64_t cand = (uint64_t)__float_as_uint(d) << 32 | (__float_as_uint(q2.y) & ~LEAF_BIT);
+                if (cand < worst) {   // into its place: the keys above it move one slot up, the worst falls out
+                    // ROUND keys a round, fetched together: one LDS latency a round, not one a key
+                    int j = k - 1;
+                    uint64_t top = cand;   // slot k - 1 afterwards: the candidate, or what slot k - 2 held
+                    for (bool go = j > 0, first = true; go; first = false) {
+                        uint64_t b[ROUND];
+#pragma unroll
+                        for (int i = 0; i < ROUND; i++) b[i] = lst.load(j - 1 - i > 0 ? j - 1 - i : 0);
+                        if (first && !(b[0] < cand)) top = b[0];
+#pragma unroll
+                        for (int i = 0; i < ROUND; i++)   // (step i: j is the round's first j minus i, b[i] slot j - 1)
+                            if (go) {
+                                if (b[i] < cand) {
+                                    go = false;
+                                } else {
+                                    lst.store(j, b[i]);
+                                    go = --j > 0;
+                                }
+                            }
+                    }
+                    lst.store(j, cand);
+                    worst = top;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const float bdl = box_dist2(p, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const float bdr = box_dist2(p, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            const bool lh = bdl <= bound, rh = bdr <= bound;
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                const bool swap = lh && rh && bdr < bdl;   // the nearer child first
+                if (lh && rh) {
+                    st.store(w.sp, w.top);   // push the other
+                    w.sp++;
+                    w.top = swap ? cl : cr;
+                }
+                w.node = swap ? cr : (lh ? cl : cr);
+            }
+            done = w.sp == -1;
+        }
+        if (done) {   // the list is in order: the sentinels, all at its end, become "none"
+            for (int j = 0; j < k; j++) {
+                const uint64_t key = lst.load(j);
+                const bool found = (uint32_t)key != 0xFFFFFFFFu;
+                a.pairs[(size_t)r * k + j] = found ? make_uint2((uint32_t)key, (uint32_t)(key >> 32)) : none;
+                if (COUNT) nfound += found;
+            }
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {npoints, nfound, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int i = 0; i < 4; i++) atomicAdd(&a.counts[i], v[i]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 // ---- all-hits ray queries (rtbvh_allhits_async): caller rays in, every (t, u, v, triangle) with t <= t_max out ----
 // k_within's frame and CSR protocol with k_query's rays.  The bound never shrinks: a child is entered iff its box
 // passes the any-hit rule query_box<true> with the ray's t_max, left first, and a leaf's triangle is a member iff
@@ -3357,6 +3529,21 @@ void launch_allhits_order(float4* hits, const unsigned long long* offsets, const
     // (the list's length is on the device: the workgroups past it leave at once)
     hipLaunchKernelGGL(k_allhits_order_block, dim3(n < 1024u ? n : 1024u), dim3(BLOCK), 0, s, hits, offsets, written,
                        list, list_n);
+}
+
+void launch_knn(const KnnArgs& a, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK;
+    auto tier = [&](auto CAP) {   // the persistent grid of the tier's occupancy, or a workgroup per 256 points
+        const uint32_t full = 256 * (uint32_t)knn_blocks(CAP), blocks = need < full ? need : full;
+        with_bools([&](auto COUNT, auto NB) {
+            hipLaunchKernelGGL((k_knn<CAP, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+        }, count, a.nb);
+    };
+    if (a.k <= 4) tier(std::integral_constant<int, 4>{});
+    else if (a.k <= 8) tier(std::integral_constant<int, 8>{});
+    else if (a.k <= 16) tier(std::integral_constant<int, 16>{});
+    else tier(std::integral_constant<int, 32>{});
 }
 
 void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s) {

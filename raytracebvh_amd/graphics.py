@@ -567,6 +567,57 @@ class Context:
         self._check(_L.lib().rtbvh_within_counts(self._h, _L.ptr(out)))
         return dict(zip(("points", "pairs", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- k-nearest queries --
+    def knn(self, points, k, max_dist2=float("inf"), mode: int = 0, out=None, stream=None):
+        """rtbvh_knn_async / rtbvh_knn_host: for each point the k triangles with the smallest (dist2, triangle id)
+        among those whose dist2 (Context.nearest's) is <= max_dist2, ascending; a slot past the number found holds
+        tri = 0xFFFFFFFF, dist2 = -1.  k: 1 .. KNN_MAX_K.
+
+        `points` as Context.nearest takes them.  A numpy input goes through the synchronous host entry and returns
+        an (n, k) PAIR_DTYPE array.  A torch CUDA (N, 4) tensor goes to the device entry with no host copy and no
+        synchronisation, enqueued on `stream` as nearest's, and returns an (n, k, 2) float32 device tensor
+        {tri, dist2}, as Context.within's pairs: read the ids with out[..., 0].view(torch.int32) (none: -1).  `out`
+        receives the lists when given.  mode: KNN_SORT, KNN_COUNT.  ValueError for a bad k and for a wrong shape,
+        dtype, device or layout."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _L.KNN_MAX_K:
+            raise ValueError(f"knn: k must be an integer from 1 to {_L.KNN_MAX_K}, got {k!r}")
+        k = int(k)
+        kind, pts = check_nearest_points(points, max_dist2, getattr(self, "device", None))
+        n = len(pts)
+        if kind == "numpy":
+            if out is None:
+                out = np.zeros((n, k), _L.PAIR_DTYPE)
+            elif not (isinstance(out, np.ndarray) and out.dtype == _L.PAIR_DTYPE and out.shape == (n, k) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"knn: out must be a contiguous ({n}, {k}) PAIR_DTYPE array")
+            self._check(_L.lib().rtbvh_knn_host(self._h, ctypes.c_void_p(pts.ctypes.data), n, k,
+                                                ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty((n, k, 2), dtype=torch.float32, device=pts.device)
+        elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, k, 2) and
+                  out.device == pts.device and out.is_contiguous()):
+            raise ValueError(f"knn: out must be a contiguous ({n}, {k}, 2) float32 tensor on {pts.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(pts.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(pts.device).synchronize()
+        self._check(_L.lib().rtbvh_knn_async(self._h, ctypes.c_void_p(pts.data_ptr()), n, k,
+                                             ctypes.c_void_p(out.data_ptr()), mode,
+                                             ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def knn_counts(self) -> dict:
+        """rtbvh_knn_counts: points, pairs found, internal-node and leaf steps of the last KNN_COUNT query (the other
+        queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_knn_counts(self._h, _L.ptr(out)))
+        return dict(zip(("points", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- all-hits ray queries --
     def allhits(self, rays, mode: int = 0, capacity=None, stream=None, sizes_only: bool = False):
         """rtbvh_allhits_async / rtbvh_allhits_host: for each ray every triangle it crosses at t <= t_max, as
