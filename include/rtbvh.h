@@ -347,8 +347,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
- * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_* and rtbvh_verify_walk return RTBVH_ERR_NOT_READY,
- * and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_* and rtbvh_verify_walk return
+ * RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -770,6 +770,68 @@ rtbvh_status rtbvh_overlap_host(rtbvh_ctx* ctx, const rtbvh_box* boxes, uint64_t
  * steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts keep theirs.
  * RTBVH_ERR_NOT_READY before any counting box query. */
 rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- signed-distance queries: the nearest triangle, and on which side of the surface the point is ----
+ * (No reference equivalent.)  Same points (rtbvh_point: {point.xyz, max_dist2}) and the same space as the
+ * closest-point queries above.  For each point: rtbvh_nearest's fields, and the number of triangles crossed by one
+ * or three fixed rays that start at the point -- for a closed surface, an odd count means inside.
+ *
+ * Rays: ray j starts at the point p; its direction is a constant, exactly representable, with no zero component, so
+ * inv = 1 / d is finite:
+ *     D0 = ( 0.75,    0.5,   0.4375)
+ *     D1 = (-0.5,     0.75, -0.4375)
+ *     D2 = ( 0.4375, -0.5,  -0.75)
+ * and t_max = +inf.
+ * Crossing: triangle x is crossed by ray j iff (B) and (X) hold, both evaluated on the floats of its leaf record --
+ * p0, e1 = fl(p1 - p0), e2 = fl(p2 - p0) and the leaf box [lo, hi] -- in fp32 without contraction, dots as
+ * (x*x' + y*y') + z*z':
+ *   (B) the leaf box passes the any-hit box rule of the all-hits section with t_max = +inf:
+ *       0 <= mx && mn <= mx && !(mn > t_max);
+ *   (X) rayTriangleCollision's arithmetic in its operation order, without its division and its EPSILON:
+ *       tmp = cross(d, e2);  det = dot(e1, tmp);  rt = p - p0
+ *       U = dot(rt, tmp);  tmp2 = cross(rt, e1);  V = dot(d, tmp2);  N = dot(e2, tmp2)
+ *       if det < 0: negate det, U, V and N (exact)
+ *       crossed iff det > 0 && U >= 0 && V >= 0 && U + V <= det && N > 0.
+ * A NaN makes a comparison false: the triangle is not crossed.  There is no epsilon anywhere, so scaling the mesh and
+ * the points by a power of two changes no decision (short of overflow and underflow).
+ * The counts are exact, whatever the tree: (B) is monotone in the box, so a walk that enters a child
+ * iff its box passes the rule reaches every crossed triangle.  A one-triangle tree has no parent that
+ * tests the leaf's box: it is tested at the leaf.
+ *
+ * flags, with c_j the number of triangles ray j crosses, over all triangles (0 for a ray not cast):
+ *     bit 0        inside: c_0 odd, or with RTBVH_SIGNED_VOTE3 at least two of the three c_j odd
+ *     bits 1..3    c_j & 1 for j = 0..2 (the parity of the true count, not of the saturated byte)
+ *     bits 4..7    0
+ *     bits 8..15, 16..23, 24..31    min(c_j, 255) for j = 0, 1, 2
+ * The nearest fields are exactly what rtbvh_nearest_* returns for the same point and bound: the lexicographic minimum
+ * of (dist2, tri), the same bits; "no result" is dist2 = -1, point = u = v = 0, tri = 0xFFFFFFFF.
+ * No walk: a non-finite coordinate gives no rays and no closest-point walk -- the "no result" fields and flags = 0.
+ * !(max_dist2 >= 0) (NaN included), or RTBVH_SIGNED_INSIDE_ONLY, gives the "no result" nearest fields, and the rays
+ * are still cast: a bound makes a narrow band, max_dist2 = -1 an occupancy query.  -0 counts as +0. */
+typedef struct {
+    float point[3]; float dist2;      /* rtbvh_nearest's fields, the same bits */
+    float u, v; uint32_t tri;
+    uint32_t flags;                   /* see above */
+} rtbvh_signed;
+enum { RTBVH_SIGNED_SORT = 1u << 1, RTBVH_SIGNED_COUNT = 1u << 2,
+       RTBVH_SIGNED_VOTE3 = 1u << 3,        /* three rays, majority; default: ray 0 alone */
+       RTBVH_SIGNED_INSIDE_ONLY = 1u << 4   /* no closest-point walk: the nearest fields are "no result" */
+       /* (every other bit is rejected) */ };
+/* n points at dev_points and n records at dev_out (device memory of the context's device, 16-B aligned), record k
+ * for point k, enqueued on `stream` (hipStream_t, NULL = the context stream).  Status, ordering, the sharing of the
+ * query scratch and of the sort's buffers (RTBVH_SIGNED_SORT: the order of RTBVH_NEAREST_SORT, the same output),
+ * n == 0, n >= 2^31, NULL pointers and unknown mode bits are rtbvh_nearest_async's rules, one for one.
+ * A walk that hits rtbvh_config.stack_limit may lose crossings, and the next synchronising call returns
+ * RTBVH_ERR_STACK_OVERFLOW; the nearest fields keep rtbvh_nearest's guarantee (the best found so far). */
+rtbvh_status rtbvh_signed_async(rtbvh_ctx* ctx, const rtbvh_point* dev_points, uint64_t n, rtbvh_signed* dev_out,
+                                uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_signed_host(rtbvh_ctx* ctx, const rtbvh_point* points, uint64_t n, rtbvh_signed* out,
+                               uint32_t mode);
+/* The last RTBVH_SIGNED_COUNT query (waits for it): points, points inside, internal-node steps and leaf steps summed
+ * over all its walks.  Its own words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any
+ * counting signed-distance query. */
+rtbvh_status rtbvh_signed_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- outputs --------------------------------------------------------------- */
 /* reflectRay[].color, the framebuffer of record (RayTraceBVHPS.hlsl:13-16): W*H*4 floats, row y at y*W. */

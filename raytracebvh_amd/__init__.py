@@ -10,6 +10,7 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    FLAG_GRAPH, HIT_DTYPE, KNN_COUNT, KNN_MAX_K, KNN_SORT, MATERIAL_DTYPE, MORTON_CPUTESTS, MORTON_HLSL, NEAREST_COUNT, NEAREST_DTYPE,
                    NEAREST_SORT, NODE_DTYPE, PAIR_DTYPE, POINT_DTYPE, QUERY_ANY,
                    OVERLAP_COUNT, OVERLAP_FILL, OVERLAP_SIZES, OVERLAP_SORT, OVERLAP_TRIANGLE,
+                   SIGNED_COUNT, SIGNED_DTYPE, SIGNED_INSIDE_ONLY, SIGNED_SORT, SIGNED_VOTE3,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, check_nearest_points, check_overlap_boxes, check_query_rays,
@@ -32,4 +33,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "ALLHITS_SORT", "ALLHITS_COUNT", "ALLHITS_BY_T", "ALLHITS_SIZES", "ALLHITS_FILL",
            "BOX_DTYPE", "OVERLAP_SORT", "OVERLAP_COUNT", "OVERLAP_TRIANGLE", "OVERLAP_SIZES", "OVERLAP_FILL",
            "make_boxes", "check_overlap_boxes",
+           "SIGNED_DTYPE", "SIGNED_SORT", "SIGNED_COUNT", "SIGNED_VOTE3", "SIGNED_INSIDE_ONLY",
            "check_query_rays", "check_vertex_array"]

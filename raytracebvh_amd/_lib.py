@@ -51,6 +51,7 @@ EXPORTS = [
     "rtbvh_knn_async", "rtbvh_knn_host", "rtbvh_knn_counts",
     "rtbvh_allhits_async", "rtbvh_allhits_host", "rtbvh_allhits_counts",
     "rtbvh_overlap_async", "rtbvh_overlap_host", "rtbvh_overlap_counts",
+    "rtbvh_signed_async", "rtbvh_signed_host", "rtbvh_signed_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -85,6 +86,11 @@ ALLHITS_SORT, ALLHITS_COUNT, ALLHITS_BY_T, ALLHITS_SIZES, ALLHITS_FILL = 2, 4, 8
 BOX_DTYPE = np.dtype([("lo", "<f4", (3,)), ("reserved0", "<u4"), ("hi", "<f4", (3,)), ("reserved1", "<u4")])
 assert BOX_DTYPE.itemsize == 32
 OVERLAP_SORT, OVERLAP_COUNT, OVERLAP_TRIANGLE, OVERLAP_SIZES, OVERLAP_FILL = 2, 4, 8, 16, 32   # RTBVH_OVERLAP_*
+# rtbvh_signed (32 B): NEAREST_DTYPE's fields and the crossing counts (include/rtbvh.h: inside, parities, bytes)
+SIGNED_DTYPE = np.dtype([("point", "<f4", (3,)), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"),
+                         ("flags", "<u4")])
+assert SIGNED_DTYPE.itemsize == 32
+SIGNED_SORT, SIGNED_COUNT, SIGNED_VOTE3, SIGNED_INSIDE_ONLY = 2, 4, 8, 16   # RTBVH_SIGNED_*
 
 
 class Config(ctypes.Structure):
@@ -251,6 +257,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_knn_async": (i32, [vp, vp, u64, u32, vp, u32, vp]),
         "rtbvh_knn_host": (i32, [vp, vp, u64, u32, vp, u32]),
         "rtbvh_knn_counts": (i32, [vp, vp]),
+        "rtbvh_signed_async": (i32, [vp, vp, u64, vp, u32, vp]),
+        "rtbvh_signed_host": (i32, [vp, vp, u64, vp, u32]),
+        "rtbvh_signed_counts": (i32, [vp, vp]),
         "rtbvh_allhits_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_allhits_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_allhits_counts": (i32, [vp, vp]),

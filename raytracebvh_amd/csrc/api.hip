@@ -324,6 +324,7 @@ struct rtbvh_ctx {
     bool allhits_counted = false;            // the all-hits count block holds a RTBVH_ALLHITS_COUNT query's counts
     bool overlap_counted = false;            // the box queries' count block holds a RTBVH_OVERLAP_COUNT query's counts
     bool knn_counted = false;                // the k-nearest queries' count block holds a RTBVH_KNN_COUNT query's counts
+    bool signed_counted = false;             // the signed-distance queries' count block holds a RTBVH_SIGNED_COUNT query's counts
 };
 
 namespace {
@@ -2987,6 +2988,120 @@ rtbvh_status rtbvh_knn_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_KNN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS, hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- signed-distance queries ---------------------------------------------------------------------------
+// rtbvh_nearest_async's rules and its place in the ev_query chain, as one link: the closest-point pass (k_nearest,
+// unless RTBVH_SIGNED_INSIDE_ONLY) and the ray pass (k_signed) over the same walk order, on the same stream.  Its count
+// blocks are QUERY_SIGNED_AT (the ray pass) and QUERY_SIGNED_NEAR_AT (the closest-point pass).
+rtbvh_status rtbvh_signed_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, rtbvh_signed* dev_out,
+                                uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_SIGNED_SORT | RTBVH_SIGNED_COUNT | RTBVH_SIGNED_VOTE3 | RTBVH_SIGNED_INSIDE_ONLY))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "signed: unknown mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "signed: 2^31 points or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_points || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "signed: NULL points or results");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "signed before build");
+    if (c->stale) return fail_stale(c, "signed");
+    static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_signed) == 32, "signed-distance record layouts");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_SIGNED_SORT) != 0, count = (mode & RTBVH_SIGNED_COUNT) != 0;
+    const bool vote3 = (mode & RTBVH_SIGNED_VOTE3) != 0, near = !(mode & RTBVH_SIGNED_INSIDE_ONLY);
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
+        // (as RTBVH_KNN_SORT: earlier queries sort in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (count)   // both passes' blocks (INSIDE_ONLY: the closest-point pass's stays zero)
+        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_SIGNED_AT, 0, sizeof(uint64_t) * 2 * QUERY_COUNT_WORDS, s));
+    SignedArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.points = reinterpret_cast<const float4*>(dev_points);
+    a.out = reinterpret_cast<float4*>(dev_out);
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_SIGNED_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    if (near) {   // the closest-point pass: rtbvh_nearest's kernel into the same records, in the same order
+        NearestArgs na{};
+        na.inner = a.inner;
+        na.topo = a.topo;
+        na.nbox = a.nbox;
+        na.nb = a.nb;
+        na.leaf = a.leaf;
+        na.T = a.T;
+        na.points = a.points;
+        na.out = a.out;
+        na.n = N;
+        na.perm = a.perm;
+        na.next = a.next;
+        na.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_SIGNED_NEAR_AT);
+        na.overflow = a.overflow;
+        na.stack_limit = a.stack_limit;
+        launch_nearest(na, count, s);
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters, again
+    }
+    launch_signed(a, count, near, vote3, s);
+    rtbvh_status st = check_launch(c, "signed kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->signed_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_signed_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, rtbvh_signed* out, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || !points || !out || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
+        return rtbvh_signed_async(c, points, n, out, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;
+    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_point) + sizeof(rtbvh_signed))));
+    rtbvh_signed* dn = reinterpret_cast<rtbvh_signed*>(d.h);
+    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + (size_t)n * sizeof(rtbvh_signed));
+    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "signed_host: upload failed");
+    TRY(rtbvh_signed_async(c, dp, n, dn, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "signed_host: sync");
+    if (hipMemcpy(out, dn, (size_t)n * sizeof(rtbvh_signed), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "signed_host: download failed");
+    return rtbvh_synchronize(c);   // (the records are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_signed_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->signed_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_SIGNED_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    uint64_t w[2 * QUERY_COUNT_WORDS];   // {points, inside, steps} of the ray pass, {points, found, steps} of the other
+    HIPC(c, hipMemcpy(w, c->d_qscratch + QUERY_SIGNED_AT, sizeof(w), hipMemcpyDeviceToHost));
+    out[0] = w[0];
+    out[1] = w[1];
+    out[2] = w[2] + w[QUERY_COUNT_WORDS + 2];
+    out[3] = w[3] + w[QUERY_COUNT_WORDS + 3];
     return RTBVH_OK;
 }
 

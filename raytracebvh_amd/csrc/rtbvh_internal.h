@@ -494,9 +494,38 @@ struct KnnArgs {
 constexpr uint32_t KNN_MAX_K = 32;
 // the k-nearest queries' own count block, behind the box queries'
 constexpr uint32_t QUERY_KNN_AT = QUERY_OVERLAP_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_KNN_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_KNN_AT % 2 == 0, "the count block's 8-byte words");
 // the instance whose list capacity (4, 8, 16 or 32 slots a lane) is the smallest that holds k
 void launch_knn(const KnnArgs& a, bool count, hipStream_t s);
+
+// ---- signed-distance queries (trace.hip k_signed; rtbvh_signed_async) --------
+// NearestArgs' points on the same tree forms; one rtbvh_signed (two float4: {point, dist2}, {u, v, tri, flags}) per
+// point at its own index.  The nearest fields come from launch_nearest into the same records (an rtbvh_nearest's last
+// word is 0); launch_signed is the ray pass: the crossing counts of one or three fixed rays, into `flags`.
+struct SignedArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* points;     // [n]
+    float4* out;              // [2n]
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_SIGNED_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_SIGNED_COUNT: [4] points, points inside, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the signed-distance queries' own count blocks, behind the k-nearest queries': the ray pass's, then the
+// closest-point pass's (launch_nearest's words: points, found, internal-node steps, leaf steps)
+constexpr uint32_t QUERY_SIGNED_AT = QUERY_KNN_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_SIGNED_NEAR_AT = QUERY_SIGNED_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_SIGNED_NEAR_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_SIGNED_AT % 2 == 0, "the count block's 8-byte words");
+// near: launch_nearest stored the nearest fields of these records before (else this pass stores "no result");
+// vote3: three rays, else ray 0 alone
+void launch_signed(const SignedArgs& a, bool count, bool near, bool vote3, hipStream_t s);
 
 }  // namespace rtbvh

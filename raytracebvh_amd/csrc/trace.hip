@@ -3497,7 +3497,178 @@ __global__ __launch_bounds__(BLOCK) void k_overlap_keys(const float4* __restrict
     vals[i] = i;
 }
 
+// ---- signed-distance queries (rtbvh_signed_async): caller points in, rtbvh_nearest's fields and crossing counts out --
+// Two passes over the same walk order.  The closest-point pass is k_nearest itself, storing into the record: an
+// rtbvh_signed is an rtbvh_nearest whose last word (0 there) holds the flags.  k_signed is the ray pass on the same
+// frame: a lane owns one point and takes it through the ray phases j = 0 .. R - 1 (R = 1, or 3 with VOTE3), each a
+// walk from the root that counts the triangles ray j crosses -- origin the point, direction the constant D_j,
+// t_max = +inf.  A child is entered iff its box passes the any-hit rule query_box<true>, left first; the rule is
+// monotone in the box, so every leaf whose own box passes is reached, and a leaf -- its box tested
+// at its parent with the same floats, or here when the root is the leaf -- counts iff signed_cross holds.  A finished
+// phase folds its count into `flags` (parity bit j + 1, the saturated byte j + 1); the last one adds `inside` and
+// stores the word.  NEAR: the closest-point pass ran before and the nearest fields are left alone; otherwise
+// (RTBVH_SIGNED_INSIDE_ONLY) this pass stores "no result" there.
+// One fused kernel -- the closest-point walk as a phase 0 of the same lane -- gave the same bits and was 2.6-6.4%
+// slower in eleven cases of sixteen, never more than 1.4% faster (profiles/signed_ab.json): the passes stay apart.
+// The directions have no zero component and are exact in fp32; their inverses are the compile-time IEEE quotients.
+__device__ __forceinline__ f3 signed_dir(uint32_t j) {
+    return j == 0 ? mk(0.75f, 0.5f, 0.4375f) : j == 1 ? mk(-0.5f, 0.75f, -0.4375f) : mk(0.4375f, -0.5f, -0.75f);
+}
+__device__ __forceinline__ f3 signed_inv(uint32_t j) {
+    return j == 0   ? mk(1.f / 0.75f, 1.f / 0.5f, 1.f / 0.4375f)
+           : j == 1 ? mk(1.f / -0.5f, 1.f / 0.75f, 1.f / -0.4375f)
+                    : mk(1.f / 0.4375f, 1.f / -0.5f, 1.f / -0.75f);
+}
+// rayTriangleCollision's arithmetic in its order, without its division and its EPSILON: u, v and t are compared as
+// numerators against the determinant, made positive by an exact negation of all four.  A NaN fails a comparison.
+__device__ __forceinline__ bool signed_cross(f3 p, f3 d, f3 p0, f3 e1, f3 e2) {
+    f3 tmp = cross(d, e2);
+    float det = dot(e1, tmp);
+    const f3 rt = sub(p, p0);
+    float U = dot(rt, tmp);
+    tmp = cross(rt, e1);
+    float V = dot(d, tmp), N = dot(e2, tmp);
+    if (det < 0.f) {
+        det = -det;
+        U = -U;
+        V = -V;
+        N = -N;
+    }
+    return det > 0.f && U >= 0.f && V >= 0.f && U + V <= det && N > 0.f;
+}
+template <bool COUNT, bool NB, bool NEAR, bool VOTE3>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_signed(SignedArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    constexpr uint32_t LAST = VOTE3 ? 2 : 0;
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t npoints = 0, ninside = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    uint32_t j = 0, cnt = 0, flags = 0;            // the ray, its crossings so far, the finished rays' bits
+    f3 p = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th point of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 pt = a.points[r];
+            p = mk(pt.x, pt.y, pt.z);
+            if (COUNT) npoints++;
+            const bool finite = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;
+            if (!NEAR) {   // no closest-point pass: no result, and flags = 0 until the last ray ends (or for good:
+                           // a point that casts no ray).  With NEAR k_nearest stored the record, flags = 0 included.
+                a.out[2 * (size_t)r] = make_float4(0.f, 0.f, 0.f, -1.f);
+                a.out[2 * (size_t)r + 1] = make_float4(0.f, 0.f, __uint_as_float(INVALID), 0.f);
+            }
+            if (finite) {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                j = 0;
+                cnt = 0;
+                flags = 0;
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;   // this ray's walk is over
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const f3 inv = signed_inv(VOTE3 ? j : 0u);
+        float mn;
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            // (T == 1: the root is the leaf, and no parent tested its box -- words 10..15 of the record)
+            if (T > 1 || query_box<true>(p, inv, f2v{q2.z, q2.w}, f2v{q3.y, q3.z}, q3.x, q3.w, false, 0.f, INFINITY, mn))
+                cnt += signed_cross(p, signed_dir(VOTE3 ? j : 0u), mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y),
+                                    mk(q1.z, q1.w, q2.x));
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = query_box<true>(p, inv, q0.xy, q0.zw, q2.x, q2.y, false, 0.f, INFINITY, mn);
+            const bool rh = query_box<true>(p, inv, q1.xy, q1.zw, q2.z, q2.w, false, 0.f, INFINITY, mn);
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            flags |= (cnt & 1u) << (j + 1) | (cnt < 255u ? cnt : 255u) << (8 * (j + 1));
+            if (j == LAST) {
+                const uint32_t odd = flags >> 1 & 7u;
+                const uint32_t inside = VOTE3 ? (uint32_t)(__popc(odd) >= 2) : odd & 1u;
+                reinterpret_cast<uint32_t*>(a.out + 2 * (size_t)r + 1)[3] = flags | inside;
+                if (COUNT) ninside += inside;
+                has = false;
+            } else {   // the next ray, from the root
+                j++;
+                cnt = 0;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+            }
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {npoints, ninside, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_signed(const SignedArgs& a, bool count, bool near, bool vote3, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto COUNT, auto NB, auto NEAR, auto VOTE3) {
+        hipLaunchKernelGGL((k_signed<COUNT, NB, NEAR, VOTE3>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, count, a.nb, near, vote3);
+}
 
 void launch_overlap(const OverlapArgs& a, bool fill, bool count, bool tri, hipStream_t s) {
     if (a.n == 0) return;

@@ -781,6 +781,112 @@ class Context:
         self._check(_L.lib().rtbvh_overlap_counts(self._h, _L.ptr(out)))
         return dict(zip(("boxes", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- signed-distance queries --
+    def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
+        """rtbvh_signed_async / rtbvh_signed_host: for each point Context.nearest's fields and `flags`, the crossing
+        counts of one ray from the point (three with SIGNED_VOTE3) along fixed directions: bit 0 inside (an odd
+        count; with VOTE3 two of three), bits 1..3 each ray's parity, bytes 1..3 each ray's count saturated at 255
+        (include/rtbvh.h).  The rays are cast whatever the bound: max_dist2 limits the nearest fields only, and
+        SIGNED_INSIDE_ONLY skips the closest-point walk (the nearest fields are then "no result").
+
+        `points` as Context.nearest takes them (max_dist2 None: no limit).  A numpy input goes through the
+        synchronous host entry and returns a SIGNED_DTYPE array.  A torch CUDA (N, 4) tensor goes to the device
+        entry with no host copy and no synchronisation, enqueued on `stream` as nearest's, and returns an (N, 8)
+        float32 device tensor {point, dist2, u, v, tri, flags}: read the flags with out[:, 7].view(torch.int32).
+        `out` receives the records when given.  mode: SIGNED_SORT, SIGNED_COUNT, SIGNED_VOTE3, SIGNED_INSIDE_ONLY.
+        ValueError for a wrong shape, dtype, device or layout."""
+        kind, pts = check_nearest_points(points, float("inf") if max_dist2 is None else max_dist2,
+                                         getattr(self, "device", None))
+        n = len(pts)
+        if kind == "numpy":
+            if out is None:
+                out = np.zeros(n, _L.SIGNED_DTYPE)
+            elif not (isinstance(out, np.ndarray) and out.dtype == _L.SIGNED_DTYPE and out.shape == (n,) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"signed: out must be a contiguous SIGNED_DTYPE array of {n} records")
+            self._check(_L.lib().rtbvh_signed_host(self._h, ctypes.c_void_p(pts.ctypes.data), n,
+                                                   ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=pts.device)
+        elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and
+                  out.device == pts.device and out.is_contiguous()):
+            raise ValueError(f"signed: out must be a contiguous ({n}, 8) float32 tensor on {pts.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(pts.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(pts.device).synchronize()
+        self._check(_L.lib().rtbvh_signed_async(self._h, ctypes.c_void_p(pts.data_ptr()), n,
+                                                ctypes.c_void_p(out.data_ptr()), mode,
+                                                ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    @staticmethod
+    def _torch_stream(stream, device):
+        """`stream` as a torch stream: itself, a raw handle wrapped, or (None) the current stream."""
+        import torch
+        if stream is None:
+            return torch.cuda.current_stream(device)
+        if hasattr(stream, "cuda_stream"):
+            return stream
+        return torch.cuda.ExternalStream(int(stream), device=device) if int(stream) else torch.cuda.default_stream(device)
+
+    def _signed_on_stream(self, pts, mode, stream, read):
+        """signed() of checked device points into a record tensor that lives on `stream`, and read(record) there.
+        The temporary is allocated under the stream it is used on, so torch's allocator hands its block to nothing
+        that could run before the work enqueued here is done."""
+        import torch
+        ts = self._torch_stream(stream, pts.device)
+        with torch.cuda.stream(ts):
+            rec = torch.empty((len(pts), 8), dtype=torch.float32, device=pts.device)
+            self.signed(pts, None, mode, out=rec, stream=ts)
+            return read(rec)
+
+    def signed_distance(self, points, max_dist2=None, mode: int = 0, stream=None):
+        """The signed distance of each point, float32: sqrt(dist2) of Context.signed's record, negative where its
+        `inside` bit is set, NaN where there is no nearest result.  A numpy array for numpy points; for a CUDA
+        tensor an (N,) device tensor computed on `stream`, with no synchronisation.  Distances are object-space
+        distances under an identity WVP only (Context.nearest)."""
+        mode = mode & ~_L.SIGNED_INSIDE_ONLY
+        if _is_tensor(points):
+            import torch
+            _, pts = check_nearest_points(points, float("inf") if max_dist2 is None else max_dist2,
+                                          getattr(self, "device", None))
+
+            def read(rec):
+                d2 = rec[:, 3]
+                d = torch.where(d2 < 0, torch.full_like(d2, float("nan")), torch.sqrt(d2.clamp(min=0)))
+                inside = (rec[:, 7].contiguous().view(torch.int32) & 1) != 0
+                return torch.where(inside, -d, d)
+            return self._signed_on_stream(pts, mode, stream, read)
+        rec = self.signed(points, max_dist2, mode)
+        with np.errstate(invalid="ignore"):
+            d = np.where(rec["tri"] == 0xFFFFFFFF, np.float32(np.nan), np.sqrt(rec["dist2"]))
+        return np.where(rec["flags"] & 1, -d, d).astype(np.float32)
+
+    def inside(self, points, vote3: bool = False, mode: int = 0, stream=None):
+        """Whether each point is inside the (closed) surface: the `inside` bit of a SIGNED_INSIDE_ONLY query, one
+        ray, or the majority of three with vote3.  A bool array for numpy points, a bool device tensor for a CUDA
+        tensor (on `stream`, no synchronisation)."""
+        mode = mode | _L.SIGNED_INSIDE_ONLY | (_L.SIGNED_VOTE3 if vote3 else 0)
+        if _is_tensor(points):
+            import torch
+            _, pts = check_nearest_points(points, float("inf"), getattr(self, "device", None))
+            return self._signed_on_stream(pts, mode, stream,
+                                          lambda rec: (rec[:, 7].contiguous().view(torch.int32) & 1) != 0)
+        return (self.signed(points, None, mode)["flags"] & 1).astype(bool)
+
+    def signed_counts(self) -> dict:
+        """rtbvh_signed_counts: points, points inside, internal-node and leaf steps (summed over all the walks) of
+        the last SIGNED_COUNT query (the other queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_signed_counts(self._h, _L.ptr(out)))
+        return dict(zip(("points", "inside", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
         out = np.zeros((self.height, self.width, 4), np.float32)
