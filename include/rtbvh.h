@@ -347,8 +347,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * run on `stream`.
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
- * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_* and rtbvh_verify_walk return
- * RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_*, rtbvh_khits_* and
+ * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -694,6 +694,58 @@ rtbvh_status rtbvh_allhits_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t 
  * steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts keep theirs.
  * RTBVH_ERR_NOT_READY before any counting all-hits query. */
 rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- first-k ray queries: a ray's k nearest crossings (multi-hit traversal) ---------------------
+ * (No reference equivalent.)  Rays, space, hits and MEMBERS are the all-hits queries' above: triangle x is a member
+ * of a ray iff (B) and (T) of that section hold, there is no walk under the same rules (a non-finite component of o
+ * or d, d all zero, !(t_max > 0)), and t_max = +inf means no limit.
+ * Key of a member x: with t_x the t of (T) and mn_x the slab entry `mn` of x's own leaf box, computed exactly as in
+ * (B), tk_x = fmaxf(t_x, mn_x) (fmaxf drops a NaN).  t_x > EPSILON > 0 and tk_x <= t_max, so tk's bits order as the
+ * floats, and the 64-bit key tk bits << 32 | tri is a total order.  The box is in the key because a triangle's t is
+ * often a few ulps BELOW the slab entry of its own leaf box: "the first k by t" cannot be walked with pruning,
+ * this can, as the closest-point queries clamp into the leaf box.
+ * The result for a ray and k is its k members with the smallest keys, in ascending key order, each reported as
+ * {t, u, v, tri}: the genuine t, u, v that rtbvh_query_* and rtbvh_allhits_* report for that triangle -- not tk.  It
+ * is a function of the ray and the triangles alone: whatever the tree, the walk order or the mode, down to the byte.
+ *  - t within a list is ascending except where an entry's key was clamped (tk = mn > t): those entries are within
+ *    rounding of their neighbours.
+ *  - Exactly coplanar crossings whose leaf boxes start at the same mn order by triangle id, whatever their t's
+ *    last bits say.
+ *  - Slot 0 is a hit iff the closest-hit query rtbvh_query_* hits.
+ *  - With k at least the length of the ray's all-hits list, the list is that set.
+ * The list is exact: every box around x's leaf box passes the first two slab conditions when the leaf box does, and
+ * starts at mn <= mn_x <= tk_x; the walk enters a box -- a child's, or a leaf's own at the leaf -- iff
+ * 0 <= mx && mn <= mx && !(mn > bound), where bound is the tk of the worst of the k kept so far (t_max until k are
+ * kept), which only falls and is never below the final one's.
+ * Output: n * k rtbvh_hit records, ray i's at [i * k, (i + 1) * k); a slot past the number found holds the miss
+ * record {-1, 0, 0, 0xFFFFFFFF}, and a ray with no walk gets k of them.  No CSR, no second pass, no capacity. */
+#define RTBVH_KHITS_MAX_K 16
+enum {
+    RTBVH_KHITS_SORT = 1u << 1,  /* walk the rays in RTBVH_QUERY_SORT's order: same output */
+    RTBVH_KHITS_COUNT = 1u << 2  /* count for rtbvh_khits_counts (slower) */
+    /* (every other bit is rejected) */
+};
+/* n rays at dev_rays and room for n * k hits at dev_hits (device memory of the context's device, 16-B aligned),
+ * enqueued on `stream` (hipStream_t, NULL = the context stream).  k == 0 or k > RTBVH_KHITS_MAX_K is
+ * RTBVH_ERR_INVALID_ARG (a ray that needs more layers has rtbvh_allhits_*).
+ * Everything else follows rtbvh_knn_async one for one: the walk reads the tree the last build or refit wrote (node
+ * records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and only
+ * enqueues; the library orders it among all the other queries, and the next build waits for it.  The first
+ * RTBVH_KHITS_SORT query and each larger one grow the sort's buffers (shared with the other queries' SORT), which
+ * waits on the host.  n == 0 returns RTBVH_OK and touches nothing, even before a build; RTBVH_ERR_NOT_READY before
+ * a build and after a vertex update until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL pointers with
+ * n > 0, bad mode bits, a bad k and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit ends with the best list found so far, and the next synchronising call
+ * returns RTBVH_ERR_STACK_OVERFLOW: every listed hit is a genuine member's, the list is ascending by key, and slot
+ * by slot its key is never below the true one's. */
+rtbvh_status rtbvh_khits_async(rtbvh_ctx* ctx, const rtbvh_ray* dev_rays, uint64_t n, uint32_t k,
+                               rtbvh_hit* dev_hits, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_khits_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t n, uint32_t k, rtbvh_hit* hits,
+                              uint32_t mode);
+/* The last RTBVH_KHITS_COUNT query (waits for it): rays, hits found, internal-node steps, leaf steps.  Its own
+ * words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting first-k query. */
+rtbvh_status rtbvh_khits_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
  * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The

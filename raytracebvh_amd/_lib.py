@@ -52,6 +52,7 @@ EXPORTS = [
     "rtbvh_allhits_async", "rtbvh_allhits_host", "rtbvh_allhits_counts",
     "rtbvh_overlap_async", "rtbvh_overlap_host", "rtbvh_overlap_counts",
     "rtbvh_signed_async", "rtbvh_signed_host", "rtbvh_signed_counts",
+    "rtbvh_khits_async", "rtbvh_khits_host", "rtbvh_khits_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -91,6 +92,8 @@ SIGNED_DTYPE = np.dtype([("point", "<f4", (3,)), ("dist2", "<f4"), ("u", "<f4"),
                          ("flags", "<u4")])
 assert SIGNED_DTYPE.itemsize == 32
 SIGNED_SORT, SIGNED_COUNT, SIGNED_VOTE3, SIGNED_INSIDE_ONLY = 2, 4, 8, 16   # RTBVH_SIGNED_*
+KHITS_SORT, KHITS_COUNT = 2, 4   # RTBVH_KHITS_*; its lists are HIT_DTYPE, a slot past the number found a miss
+KHITS_MAX_K = 16                 # RTBVH_KHITS_MAX_K
 
 
 class Config(ctypes.Structure):
@@ -260,6 +263,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_signed_async": (i32, [vp, vp, u64, vp, u32, vp]),
         "rtbvh_signed_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_signed_counts": (i32, [vp, vp]),
+        "rtbvh_khits_async": (i32, [vp, vp, u64, u32, vp, u32, vp]),
+        "rtbvh_khits_host": (i32, [vp, vp, u64, u32, vp, u32]),
+        "rtbvh_khits_counts": (i32, [vp, vp]),
         "rtbvh_allhits_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_allhits_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_allhits_counts": (i32, [vp, vp]),

@@ -325,6 +325,7 @@ struct rtbvh_ctx {
     bool overlap_counted = false;            // the box queries' count block holds a RTBVH_OVERLAP_COUNT query's counts
     bool knn_counted = false;                // the k-nearest queries' count block holds a RTBVH_KNN_COUNT query's counts
     bool signed_counted = false;             // the signed-distance queries' count block holds a RTBVH_SIGNED_COUNT query's counts
+    bool khits_counted = false;              // the first-k queries' count block holds a RTBVH_KHITS_COUNT query's counts
 };
 
 namespace {
@@ -3102,6 +3103,99 @@ rtbvh_status rtbvh_signed_counts(rtbvh_ctx* c, uint64_t out[4]) {
     out[1] = w[1];
     out[2] = w[2] + w[QUERY_COUNT_WORDS + 2];
     out[3] = w[3] + w[QUERY_COUNT_WORDS + 3];
+    return RTBVH_OK;
+}
+
+// ---- first-k ray queries -------------------------------------------------------------------------------
+// rtbvh_knn_async's rules, one for one, with the ray queries' rays and sort keys; one walk, no second pass.  Its
+// count block is QUERY_KHITS_AT.
+rtbvh_status rtbvh_khits_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, uint32_t k, rtbvh_hit* dev_hits,
+                               uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_KHITS_SORT | RTBVH_KHITS_COUNT))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "khits: unknown mode bits");
+    if (k == 0 || k > RTBVH_KHITS_MAX_K) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: k must be 1 .. RTBVH_KHITS_MAX_K");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: 2^31 rays or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: NULL rays or hits");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "khits before build");
+    if (c->stale) return fail_stale(c, "khits");
+    static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "first-k record layouts");
+    static_assert(RTBVH_KHITS_MAX_K == KHITS_MAX_K, "the largest list of k_khits");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_KHITS_SORT) != 0, count = (mode & RTBVH_KHITS_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
+        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
+        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_KHITS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    KhitsArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.rays = reinterpret_cast<const float4*>(dev_rays);
+    a.hits = reinterpret_cast<float4*>(dev_hits);
+    a.n = N;
+    a.k = k;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_KHITS_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    launch_khits(a, count, s);
+    rtbvh_status st = check_launch(c, "khits kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->khits_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_khits_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, uint32_t k, rtbvh_hit* hits,
+                              uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || k == 0 || k > RTBVH_KHITS_MAX_K || !rays || !hits || !c->tree.built ||
+        c->stale)   // (nothing to stage: the query's checks)
+        return rtbvh_khits_async(c, rays, n, k, hits, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // hits, then rays: both 16-B aligned
+    const size_t out_bytes = (size_t)n * k * sizeof(rtbvh_hit);
+    HIPC(c, d.alloc(out_bytes + (size_t)n * sizeof(rtbvh_ray)));
+    rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d.h);
+    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d + out_bytes);
+    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "khits_host: upload failed");
+    TRY(rtbvh_khits_async(c, dr, n, k, dh, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "khits_host: sync");
+    if (hipMemcpy(hits, dh, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "khits_host: download failed");
+    return rtbvh_synchronize(c);   // (the lists are the best found when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_khits_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->khits_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_KHITS_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_KHITS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS, hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }
 

@@ -522,10 +522,38 @@ struct SignedArgs {
 // closest-point pass's (launch_nearest's words: points, found, internal-node steps, leaf steps)
 constexpr uint32_t QUERY_SIGNED_AT = QUERY_KNN_AT + 2 * QUERY_COUNT_WORDS;
 constexpr uint32_t QUERY_SIGNED_NEAR_AT = QUERY_SIGNED_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_SIGNED_NEAR_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_SIGNED_AT % 2 == 0, "the count block's 8-byte words");
 // near: launch_nearest stored the nearest fields of these records before (else this pass stores "no result");
 // vote3: three rays, else ray 0 alone
 void launch_signed(const SignedArgs& a, bool count, bool near, bool vote3, hipStream_t s);
+
+// ---- first-k ray queries (trace.hip k_khits; rtbvh_khits_async) --------------
+// AllhitsArgs' rays on the same tree forms; ray r's k hits (float4: t, u, v, tri), ascending in the key
+// (max(t, the leaf box's slab entry), tri), at hits[r * k .. r * k + k), the slots past the number found
+// {-1, 0, 0, 0xFFFFFFFF}.
+struct KhitsArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* rays;       // [2n]
+    float4* hits;             // [n * k]
+    uint32_t n;
+    uint32_t k;               // 1 .. KHITS_MAX_K
+    const uint32_t* perm;     // walk order (RTBVH_KHITS_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_KHITS_COUNT: [4] rays, hits found, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+constexpr uint32_t KHITS_MAX_K = 16;
+// the first-k queries' own count block, behind the signed-distance queries'
+constexpr uint32_t QUERY_KHITS_AT = QUERY_SIGNED_NEAR_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_KHITS_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_KHITS_AT % 2 == 0, "the count block's 8-byte words");
+// the instance whose list capacity (4, 8 or 16 slots a lane) is the smallest that holds k
+void launch_khits(const KhitsArgs& a, bool count, hipStream_t s);
 
 }  // namespace rtbvh

@@ -3211,6 +3211,200 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_allhits(AllhitsArgs a) 
     }
 }
 
+// ---- first-k ray queries (rtbvh_khits_async): caller rays in, each ray's k members with the smallest keys out ----
+// k_knn's frame with k_allhits' rays.  A member is k_allhits' (the leaf's own box passes the any-hit rule with t_max,
+// ray_triangle_tuv accepts at t <= t_max); its key is (tk bits << 32 | id) with tk = fmaxf(t, mn), mn the slab entry
+// of its own leaf box: t is often a few ulps below mn, and with the box in the key no box around the leaf box starts
+// above tk (the slab test is monotone in the box).  Each lane keeps k keys in ascending order, all
+// started at the sentinel (t_max bits, 0xFFFFFFFF); `worst` caches slot k - 1, and a box -- a child's, or a leaf's
+// own, tested at the leaf with the current bound -- is entered iff it passes the first two slab conditions and
+// !(mn > the worst key's tk), the nearer child first by mn, left on a tie.  The bound only falls and is never below
+// the final worst key's tk, so no member of the final list is pruned.
+// The list lives in LDS beside the stack as k_knn's, [slot][lane]: an 8-B key column and a 4-B column with the
+// leaf's slot in the leaf records, so the finished list's (t, u, v) are recomputed by the same ray_triangle_tuv on the
+// same inputs -- the same bits -- instead of carried.  CAP (4, 8 or 16 slots) is the smallest tier that holds k;
+// khits_blocks(CAP) blocks fit a CU's 160 KB and the launch bound asks for as many.
+constexpr int khits_blocks(int cap) {   // blocks of 16 KB of stack and cap * 3 KB of list in 160 KB
+    const int b = 160 / (16 + 3 * cap);
+    return b < (int)BOUNCE_WAVES ? b : (int)BOUNCE_WAVES;
+}
+struct KhitsList {
+    unsigned long long* key;   // this lane's LDS columns, slot j at [j * BLOCK]
+    uint32_t* leaf;
+    __device__ __forceinline__ void store(int j, uint64_t v, uint32_t l) {
+        key[j * BLOCK] = v;
+        leaf[j * BLOCK] = l;
+    }
+    __device__ __forceinline__ uint64_t load(int j) const { return key[j * BLOCK]; }
+    __device__ __forceinline__ uint32_t load_leaf(int j) const { return leaf[j * BLOCK]; }
+};
+template <int CAP, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, khits_blocks(CAP)) void k_khits(KhitsArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const int k = (int)a.k;   // 1 .. CAP
+    constexpr int ROUND = CAP >= 16 ? 8 : 4;   // keys an insertion fetches together
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nrays = 0, nfound = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    uint64_t worst = 0;   // the list's slot k - 1
+    float tmax = 0.f;
+    f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    __shared__ unsigned long long s_key[CAP][BLOCK];
+    __shared__ uint32_t s_leaf[CAP][BLOCK];
+    KhitsList lst{&s_key[0][threadIdx.x], &s_leaf[0][threadIdx.x]};
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    const float4 none = make_float4(-1.f, 0.f, 0.f, __uint_as_float(INVALID));
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t p) {   // this lane takes the p-th ray of the walk order
+            r = a.perm ? a.perm[p] : p;
+            const float4 q0 = a.rays[2 * (size_t)r], q1 = a.rays[2 * (size_t)r + 1];
+            o = mk(q0.x, q0.y, q0.z);
+            tmax = q0.w;
+            d = mk(q1.x, q1.y, q1.z);
+            inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            if (COUNT) nrays++;
+            const bool finite = fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY &&
+                                fabsf(d.x) < INFINITY && fabsf(d.y) < INFINITY && fabsf(d.z) < INFINITY;
+            const bool zero = d.x == 0.f && d.y == 0.f && d.z == 0.f;
+            if (!finite || zero || !(tmax > 0.f)) {   // no walk: every slot a miss
+                for (int j = 0; j < k; j++) a.hits[(size_t)r * k + j] = none;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                worst = (uint64_t)__float_as_uint(tmax) << 32 | 0xFFFFFFFFull;
+                for (int j = 0; j < k; j++) lst.store(j, worst, 0u);
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_query)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const float bound = key_t(worst);   // t_max until the list is full
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            float mn;   // the leaf's own box first, with the current bound (words 10..15 of the record)
+            if (query_box<true>(o, inv, f2v{q2.z, q2.w}, f2v{q3.y, q3.z}, q3.x, q3.w, false, 0.f, bound, mn)) {
+                float u = 0.f, v = 0.f;
+                const float t = ray_triangle_tuv(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y),
+                                                 mk(q1.z, q1.w, q2.x), u, v);
+                const uint64_t cand = (uint64_t)__float_as_uint(fmaxf(t, mn)) << 32 | (__float_as_uint(q2.y) & ~LEAF_BIT);
+                if (t != -1.f && t <= tmax && cand < worst) {   // into its place: the keys above it move one slot up
+                    const uint32_t here = w.node & ~LEAF_BIT;
+                    int j = k - 1;
+                    uint64_t top = cand;   // slot k - 1 afterwards: the candidate, or what slot k - 2 held
+                    for (bool go = j > 0, first = true; go; first = false) {
+                        uint64_t b[ROUND];
+                        uint32_t bl[ROUND];
+#pragma unroll
+                        for (int i = 0; i < ROUND; i++) {
+                            const int at = j - 1 - i > 0 ? j - 1 - i : 0;
+                            b[i] = lst.load(at);
+                            bl[i] = lst.load_leaf(at);
+                        }
+                        if (first && !(b[0] < cand)) top = b[0];
+#pragma unroll
+                        for (int i = 0; i < ROUND; i++)   // (step i: j is the round's first j minus i, b[i] slot j - 1)
+                            if (go) {
+                                if (b[i] < cand) {
+                                    go = false;
+                                } else {
+                                    lst.store(j, b[i], bl[i]);
+                                    go = --j > 0;
+                                }
+                            }
+                    }
+                    lst.store(j, cand, here);
+                    worst = top;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            float ml, mr;
+            const bool lh = query_box<true>(o, inv, q0.xy, q0.zw, q2.x, q2.y, false, 0.f, bound, ml);
+            const bool rh = query_box<true>(o, inv, q1.xy, q1.zw, q2.z, q2.w, false, 0.f, bound, mr);
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                const bool swap = lh && rh && mr < ml;   // the nearer child first, left on a tie
+                if (lh && rh) {
+                    st.store(w.sp, w.top);   // push the other
+                    w.sp++;
+                    w.top = swap ? cl : cr;
+                }
+                w.node = swap ? cr : (lh ? cl : cr);
+            }
+            done = w.sp == -1;
+        }
+        if (done) {   // the list is in order, the sentinels all at its end: the listed leaves' hits, then misses
+            for (int j = 0; j < k; j++) {
+                const uint64_t key = lst.load(j);
+                const bool found = (uint32_t)key != 0xFFFFFFFFu;
+                float4 h = none;
+                if (found) {
+                    const v4f* rr = reinterpret_cast<const v4f*>(leaf + 4 * (size_t)lst.load_leaf(j));
+                    const v4f l0 = rr[0], l1 = rr[1], l2 = rr[2];
+                    float u = 0.f, v = 0.f;
+                    const float t = ray_triangle_tuv(o, d, mk(l0.x, l0.y, l0.z), mk(l0.w, l1.x, l1.y),
+                                                     mk(l1.z, l1.w, l2.x), u, v);
+                    h = make_float4(t, u, v, __uint_as_float((uint32_t)key));
+                }
+                a.hits[(size_t)r * k + j] = h;
+                if (COUNT) nfound += found;
+            }
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nrays, nfound, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int i = 0; i < 4; i++) atomicAdd(&a.counts[i], v[i]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 // ---- RTBVH_ALLHITS_BY_T: each ray's stored hits ordered by (t, tri), in place ---------------------------------
 // t > EPSILON > 0, so the floats order as their bits and (t, tri) is the u64 key t bits << 32 | tri: a total order
 // (a ray's list holds a triangle once).  A hit moves as one 16-B word.
@@ -3715,6 +3909,20 @@ void launch_knn(const KnnArgs& a, bool count, hipStream_t s) {
     else if (a.k <= 8) tier(std::integral_constant<int, 8>{});
     else if (a.k <= 16) tier(std::integral_constant<int, 16>{});
     else tier(std::integral_constant<int, 32>{});
+}
+
+void launch_khits(const KhitsArgs& a, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK;
+    auto tier = [&](auto CAP) {   // the persistent grid of the tier's occupancy, or a workgroup per 256 rays
+        const uint32_t full = 256 * (uint32_t)khits_blocks(CAP), blocks = need < full ? need : full;
+        with_bools([&](auto COUNT, auto NB) {
+            hipLaunchKernelGGL((k_khits<CAP, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+        }, count, a.nb);
+    };
+    if (a.k <= 4) tier(std::integral_constant<int, 4>{});
+    else if (a.k <= 8) tier(std::integral_constant<int, 8>{});
+    else tier(std::integral_constant<int, 16>{});
 }
 
 void launch_within(const WithinArgs& a, bool fill, bool count, hipStream_t s) {

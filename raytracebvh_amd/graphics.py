@@ -699,6 +699,58 @@ class Context:
         self._check(_L.lib().rtbvh_allhits_counts(self._h, _L.ptr(out)))
         return dict(zip(("rays", "hits", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- first-k ray queries --
+    def khits(self, rays, k, mode: int = 0, out=None, stream=None):
+        """rtbvh_khits_async / rtbvh_khits_host: for each ray its k nearest crossings -- of the members
+        Context.allhits lists, the k with the smallest (max(t, the leaf box's slab entry), triangle id), ascending,
+        each as the genuine {t, u, v, tri}; a slot past the number found holds the miss t = -1, tri = 0xFFFFFFFF.
+        k: 1 .. KHITS_MAX_K.
+
+        `rays` as Context.query takes them.  A numpy input goes through the synchronous host entry and returns an
+        (n, k) HIT_DTYPE array.  A torch CUDA (N, 8) tensor goes to the device entry with no host copy and no
+        synchronisation, enqueued on `stream` as query's, and returns an (n, k, 4) float32 device tensor
+        {t, u, v, tri}: read the ids with out[..., 3].view(torch.int32) (a miss: -1).  `out` receives the lists when
+        given.  mode: KHITS_SORT, KHITS_COUNT.  ValueError for a bad k and for a wrong shape, dtype, device or
+        layout."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _L.KHITS_MAX_K:
+            raise ValueError(f"khits: k must be an integer from 1 to {_L.KHITS_MAX_K}, got {k!r}")
+        k = int(k)
+        kind, rays = check_query_rays(rays, getattr(self, "device", None))
+        n = len(rays)
+        if kind == "numpy":
+            if out is None:
+                out = np.zeros((n, k), _L.HIT_DTYPE)
+            elif not (isinstance(out, np.ndarray) and out.dtype == _L.HIT_DTYPE and out.shape == (n, k) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"khits: out must be a contiguous ({n}, {k}) HIT_DTYPE array")
+            self._check(_L.lib().rtbvh_khits_host(self._h, ctypes.c_void_p(rays.ctypes.data), n, k,
+                                                  ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty((n, k, 4), dtype=torch.float32, device=rays.device)
+        elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, k, 4) and
+                  out.device == rays.device and out.is_contiguous()):
+            raise ValueError(f"khits: out must be a contiguous ({n}, {k}, 4) float32 tensor on {rays.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(rays.device).synchronize()
+        self._check(_L.lib().rtbvh_khits_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, k,
+                                               ctypes.c_void_p(out.data_ptr()), mode,
+                                               ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def khits_counts(self) -> dict:
+        """rtbvh_khits_counts: rays, hits found, internal-node and leaf steps of the last KHITS_COUNT query (the other
+        queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_khits_counts(self._h, _L.ptr(out)))
+        return dict(zip(("rays", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- box-overlap queries --
     def overlap(self, boxes, hi=None, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
         """rtbvh_overlap_async / rtbvh_overlap_host: for each axis-aligned box every triangle whose leaf box meets it
