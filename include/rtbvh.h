@@ -348,7 +348,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
  * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_*, rtbvh_khits_* and
- * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, as do rtbvh_collide_async and rtbvh_collide_host, and the
+ * rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -746,6 +747,77 @@ rtbvh_status rtbvh_khits_host(rtbvh_ctx* ctx, const rtbvh_ray* rays, uint64_t n,
 /* The last RTBVH_KHITS_COUNT query (waits for it): rays, hits found, internal-node steps, leaf steps.  Its own
  * words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting first-k query. */
 rtbvh_status rtbvh_khits_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- self-collision queries: the pairs of the mesh's own triangles that cross each other --------
+ * (No reference equivalent; Embree's rtcCollide of a scene with itself.)  No shapes come from the caller: the
+ * query is the built mesh against itself, in the space the BVH was built in.  The result is the set of MEMBER pairs,
+ * specified independently of the tree and of the walk.  All floats come from the leaf records of the last build or
+ * refit: for a triangle x its a = p0, e1 = fl(p1 - p0), e2 = fl(p2 - p0) and leaf box [lo, hi].  Arithmetic is fp32
+ * without contraction, every product rounded, with dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z and
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).  The three edge segments (P, D) of x
+ * are, in this order, S0 = (a, e1), S1 = (a, e2), S2 = (fl(a + e1), fl(e2 - e1)), componentwise.
+ * A pair {x, y} of different triangles is a member iff
+ *  (N) they are not neighbours: no vertex index of x equals a vertex index of y -- nine integer comparisons on the
+ *      scene's index buffer, indices[3x .. 3x + 2] against indices[3y .. 3y + 2].  Triangles that share a vertex
+ *      always touch there; listing them would bury the real contacts.
+ *  (B) their leaf boxes meet: lo_x <= hi_y && lo_y <= hi_x on every axis.  Closed intervals (touching counts), the
+ *      box queries' comparisons, no arithmetic; a NaN fails it.
+ *  (X) with RTBVH_COLLIDE_TRIANGLE only: at least one of the six tests "segment S_k(x) crosses triangle y",
+ *      "segment S_k(y) crosses triangle x", k = 0 .. 2, holds.  "Segment (P, D) crosses the triangle (p0, e1, e2)"
+ *      is the signed-distance queries' rule (X) with the segment's far end added:
+ *        tmp = cross(D, e2);  det = dot(e1, tmp);  rt = P - p0
+ *        U = dot(rt, tmp);  tmp2 = cross(rt, e1);  V = dot(D, tmp2);  N = dot(e2, tmp2)
+ *        if det < 0: negate det, U, V and N (exact)
+ *        crosses iff det > 0 && U >= 0 && V >= 0 && U + V <= det && N >= 0 && N <= det
+ *      No division, no epsilon; a NaN compares false; touching counts, as in the box queries.  Both orders of a
+ *      pair evaluate the same six tests: the rule is symmetric in x and y by construction.
+ * Limits: coplanar triangles have det = 0 in every test and are not reported.  A contact within rounding can go
+ * either way, but the same way on every tree.  A mesh with unwelded duplicate vertices reports the faces that touch
+ * along the duplicated vertices, because (N) looks at indices, not positions.
+ * The set is exact whatever the tree: (B) is monotone in the tree's box, so a walk that enters a child iff its box
+ * meets x's leaf box reaches every partner of x (the box queries' argument).
+ * Output in CSR form over TRIANGLES, indexed by triangle id (triangle order, Node.index / 3): dev_offsets has T + 1
+ * entries, dev_offsets[0] = 0, triangle i's partners are dev_ids[dev_offsets[i] .. dev_offsets[i + 1]), and
+ * dev_offsets[T] is the true total whatever `capacity` is.  Each list is ascending by the partner's position in the
+ * last build's sort order (tri_ids of rtbvh_read_sorted; a refit keeps it).  By default a pair appears once, in the
+ * list of the triangle that comes earlier in that sort order; with RTBVH_COLLIDE_SYMMETRIC it appears in both
+ * triangles' lists, and a sizes pass alone is then the per-triangle contact count.  An id whose index is >= capacity
+ * is not written: nothing is ever written past dev_ids + capacity, capacity may be 0 (dev_ids may then be NULL), and
+ * the caller compares dev_offsets[T] with capacity. */
+enum {
+    RTBVH_COLLIDE_COUNT = 1u << 2,     /* count triangles, entries and steps for rtbvh_collide_counts (slower) */
+    RTBVH_COLLIDE_TRIANGLE = 1u << 3,  /* rule (X) as well: the triangles cross, not only their leaf boxes */
+    RTBVH_COLLIDE_SIZES = 1u << 4,     /* write dev_offsets only; dev_ids may be NULL */
+    RTBVH_COLLIDE_FILL = 1u << 5,      /* dev_offsets is INPUT (from a SIZES call of the same mode and tree): write
+                                          the ids only */
+    RTBVH_COLLIDE_SYMMETRIC = 1u << 6  /* a pair is listed by both of its triangles */
+    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG.  There is no SORT bit: the queries are the
+       leaves, walked in sort order, which is the coherent order already. */
+};
+/* T + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` ids at dev_ids (device memory of the context's
+ * device), enqueued on `stream` (hipStream_t, NULL = the context stream).  Mode 0 runs the sizes pass, a scan of the
+ * offsets on the device and the fill pass in one call, with no host round trip; RTBVH_COLLIDE_SIZES then
+ * RTBVH_COLLIDE_FILL is the two-call form.  A FILL over any non-decreasing offsets writes triangle i's ids only
+ * inside [dev_offsets[i], min(dev_offsets[i + 1], capacity)): offsets of another mode or tree truncate lists to
+ * their first ids, they never make a write go astray.
+ * Everything else follows rtbvh_overlap_async one for one: the walk reads the tree the last build or refit wrote
+ * (node records, or the topology and node boxes; never the quantized nodes); the call waits for the last build and
+ * only enqueues; the library orders it among all other queries, and the next build waits for it.  The first query
+ * that writes offsets and each larger one grow the scan's block sums, which waits on the host for the outstanding
+ * queries.  A scene of one triangle gives offsets {0, 0}.
+ * RTBVH_ERR_NOT_READY before a build and after a vertex update until the next build or refit;
+ * RTBVH_ERR_INVALID_ARG for NULL offsets, NULL ids with capacity > 0 outside RTBVH_COLLIDE_SIZES, and bad mode bits.
+ * A walk that hits rtbvh_config.stack_limit loses that subtree's ids -- both passes lose them identically, so
+ * offsets and ids stay consistent -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_collide_async(rtbvh_ctx* ctx, uint64_t* dev_offsets, uint32_t* dev_ids, uint64_t capacity,
+                                 uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (T + 1) and ids are
+ * host arrays; ids receives min(total, capacity) entries.  With RTBVH_COLLIDE_FILL, offsets is read. */
+rtbvh_status rtbvh_collide_host(rtbvh_ctx* ctx, uint64_t* offsets, uint32_t* ids, uint64_t capacity, uint32_t mode);
+/* The last RTBVH_COLLIDE_COUNT query (waits for it): triangles (T), entries (the true total, counted once),
+ * internal-node steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts
+ * keep theirs.  RTBVH_ERR_NOT_READY before any counting self-collision query. */
+rtbvh_status rtbvh_collide_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
  * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The

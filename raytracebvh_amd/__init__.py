@@ -12,6 +12,7 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    OVERLAP_COUNT, OVERLAP_FILL, OVERLAP_SIZES, OVERLAP_SORT, OVERLAP_TRIANGLE,
                    SIGNED_COUNT, SIGNED_DTYPE, SIGNED_INSIDE_ONLY, SIGNED_SORT, SIGNED_VOTE3,
                    KHITS_COUNT, KHITS_MAX_K, KHITS_SORT,
+                   COLLIDE_COUNT, COLLIDE_FILL, COLLIDE_SIZES, COLLIDE_SYMMETRIC, COLLIDE_TRIANGLE,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, check_nearest_points, check_overlap_boxes, check_query_rays,
@@ -36,4 +37,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "make_boxes", "check_overlap_boxes",
            "SIGNED_DTYPE", "SIGNED_SORT", "SIGNED_COUNT", "SIGNED_VOTE3", "SIGNED_INSIDE_ONLY",
            "KHITS_SORT", "KHITS_COUNT", "KHITS_MAX_K",
+           "COLLIDE_COUNT", "COLLIDE_TRIANGLE", "COLLIDE_SIZES", "COLLIDE_FILL", "COLLIDE_SYMMETRIC",
            "check_query_rays", "check_vertex_array"]

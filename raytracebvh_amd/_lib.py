@@ -53,6 +53,7 @@ EXPORTS = [
     "rtbvh_overlap_async", "rtbvh_overlap_host", "rtbvh_overlap_counts",
     "rtbvh_signed_async", "rtbvh_signed_host", "rtbvh_signed_counts",
     "rtbvh_khits_async", "rtbvh_khits_host", "rtbvh_khits_counts",
+    "rtbvh_collide_async", "rtbvh_collide_host", "rtbvh_collide_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -94,6 +95,8 @@ assert SIGNED_DTYPE.itemsize == 32
 SIGNED_SORT, SIGNED_COUNT, SIGNED_VOTE3, SIGNED_INSIDE_ONLY = 2, 4, 8, 16   # RTBVH_SIGNED_*
 KHITS_SORT, KHITS_COUNT = 2, 4   # RTBVH_KHITS_*; its lists are HIT_DTYPE, a slot past the number found a miss
 KHITS_MAX_K = 16                 # RTBVH_KHITS_MAX_K
+# RTBVH_COLLIDE_*; its lists hold triangle ids (uint32), indexed by triangle
+COLLIDE_COUNT, COLLIDE_TRIANGLE, COLLIDE_SIZES, COLLIDE_FILL, COLLIDE_SYMMETRIC = 4, 8, 16, 32, 64
 
 
 class Config(ctypes.Structure):
@@ -272,6 +275,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_overlap_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_overlap_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_overlap_counts": (i32, [vp, vp]),
+        "rtbvh_collide_async": (i32, [vp, vp, vp, u64, u32, vp]),
+        "rtbvh_collide_host": (i32, [vp, vp, vp, u64, u32]),
+        "rtbvh_collide_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

@@ -326,6 +326,7 @@ struct rtbvh_ctx {
     bool knn_counted = false;                // the k-nearest queries' count block holds a RTBVH_KNN_COUNT query's counts
     bool signed_counted = false;             // the signed-distance queries' count block holds a RTBVH_SIGNED_COUNT query's counts
     bool khits_counted = false;              // the first-k queries' count block holds a RTBVH_KHITS_COUNT query's counts
+    bool collide_counted = false;            // the self-collision queries' count block holds a RTBVH_COLLIDE_COUNT query's counts
 };
 
 namespace {
@@ -2895,6 +2896,108 @@ rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_OVERLAP_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- self-collision queries ----------------------------------------------------------------------------
+// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain, with the tree's T leaves for
+// queries: [sizes + scan], then [fill], all on the caller's stream.  Its count block is QUERY_COLLIDE_AT.
+rtbvh_status rtbvh_collide_async(rtbvh_ctx* c, uint64_t* dev_offsets, uint32_t* dev_ids, uint64_t capacity,
+                                 uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_COLLIDE_COUNT | RTBVH_COLLIDE_TRIANGLE | RTBVH_COLLIDE_SIZES | RTBVH_COLLIDE_FILL |
+                             RTBVH_COLLIDE_SYMMETRIC;
+    constexpr uint32_t BOTH = RTBVH_COLLIDE_SIZES | RTBVH_COLLIDE_FILL;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: bad mode bits");
+    const bool sizes = !(mode & RTBVH_COLLIDE_FILL), fill = !(mode & RTBVH_COLLIDE_SIZES);
+    if (!dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: NULL offsets");
+    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: NULL ids");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "collide before build");
+    if (c->stale) return fail_stale(c, "collide");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool count = (mode & RTBVH_COLLIDE_COUNT) != 0, tri = (mode & RTBVH_COLLIDE_TRIANGLE) != 0;
+    const bool sym = (mode & RTBVH_COLLIDE_SYMMETRIC) != 0;
+    const uint32_t N = c->T;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (sizes && !c->d_qscan.has(scan_sums_words(N))) {
+        // (as rtbvh_overlap_async: earlier queries scan in the old buffer)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_COLLIDE_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    CollideArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = N;
+    a.idx = c->d_idx;
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.ids = dev_ids;
+    a.capacity = capacity;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_COLLIDE_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_ids = true;
+        launch_collide(a, false, count, tri, sym, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_ids = !sizes;
+        launch_collide(a, true, count, tri, sym, s);
+    }
+    rtbvh_status st = check_launch(c, "collide kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->collide_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_collide_host(rtbvh_ctx* c, uint64_t* offsets, uint32_t* ids, uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_COLLIDE_FILL) != 0, sizes_only = (mode & RTBVH_COLLIDE_SIZES) != 0;
+    if (!offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) || !c->tree.built ||
+        c->stale)   // (the query's checks)
+        return rtbvh_collide_async(c, offsets, ids, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    const uint64_t n = c->T;
+    DevBuf<uint64_t> doff;
+    HIPC(c, doff.alloc((size_t)(n + 1)));
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "collide_host: upload failed");
+    DevBuf<uint32_t> dids;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another mode or tree leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
+    TRY(rtbvh_collide_async(c, doff, dids, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "collide_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "collide_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "collide_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_collide_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->collide_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_COLLIDE_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_COLLIDE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

@@ -551,9 +551,37 @@ struct KhitsArgs {
 constexpr uint32_t KHITS_MAX_K = 16;
 // the first-k queries' own count block, behind the signed-distance queries'
 constexpr uint32_t QUERY_KHITS_AT = QUERY_SIGNED_NEAR_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_KHITS_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_KHITS_AT % 2 == 0, "the count block's 8-byte words");
 // the instance whose list capacity (4, 8 or 16 slots a lane) is the smallest that holds k
 void launch_khits(const KhitsArgs& a, bool count, hipStream_t s);
+
+// ---- self-collision queries (trace.hip k_collide; rtbvh_collide_async) -------
+// No caller shapes: query k is the leaf at sorted position k, walked against the tree it lies in.  OverlapArgs'
+// CSR output indexed by TRIANGLE id: a sizes pass stores the count of the triangle at position k at
+// offsets[id + 1], scan_offsets makes offsets of them, a fill pass stores its partners' ids at
+// [offsets[id], min(offsets[id + 1], capacity)).
+struct CollideArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const uint32_t* idx;      // [3T] BuildArgs::idx: rule (N)'s vertex indices, in triangle order
+    unsigned long long* offsets;    // [T + 1]: the sizes pass writes [1, T], the fill pass reads
+    uint32_t* ids;            // the fill pass: [capacity] triangle ids
+    unsigned long long capacity;
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_COLLIDE_COUNT: [4] triangles, entries, internal-node steps, leaf steps
+    bool count_ids;           // ... this pass adds the triangles and entries (one pass of a call does), not only steps
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the self-collision queries' own count block, behind the first-k queries'
+constexpr uint32_t QUERY_COLLIDE_AT = QUERY_KHITS_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_COLLIDE_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_COLLIDE_AT % 2 == 0, "the count block's 8-byte words");
+// tri: rule (X), the six segment-triangle tests; sym: both triangles of a pair list it
+void launch_collide(const CollideArgs& a, bool fill, bool count, bool tri, bool sym, hipStream_t s);
 
 }  // namespace rtbvh

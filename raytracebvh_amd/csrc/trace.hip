@@ -3715,20 +3715,27 @@ __device__ __forceinline__ f3 signed_inv(uint32_t j) {
 }
 // rayTriangleCollision's arithmetic in its order, without its division and its EPSILON: u, v and t are compared as
 // numerators against the determinant, made positive by an exact negation of all four.  A NaN fails a comparison.
-__device__ __forceinline__ bool signed_cross(f3 p, f3 d, f3 p0, f3 e1, f3 e2) {
+// cross_line: the line through p along d meets the triangle's plane inside the triangle (edges included); det > 0 and
+// N, the distance's numerator, go back to the caller, whose rule on N is its own (k_signed's ray, k_collide's segment).
+__device__ __forceinline__ bool cross_line(f3 p, f3 d, f3 p0, f3 e1, f3 e2, float& det, float& N) {
     f3 tmp = cross(d, e2);
-    float det = dot(e1, tmp);
+    det = dot(e1, tmp);
     const f3 rt = sub(p, p0);
     float U = dot(rt, tmp);
     tmp = cross(rt, e1);
-    float V = dot(d, tmp), N = dot(e2, tmp);
+    float V = dot(d, tmp);
+    N = dot(e2, tmp);
     if (det < 0.f) {
         det = -det;
         U = -U;
         V = -V;
         N = -N;
     }
-    return det > 0.f && U >= 0.f && V >= 0.f && U + V <= det && N > 0.f;
+    return det > 0.f && U >= 0.f && V >= 0.f && U + V <= det;
+}
+__device__ __forceinline__ bool signed_cross(f3 p, f3 d, f3 p0, f3 e1, f3 e2) {
+    float det, N;
+    return cross_line(p, d, p0, e1, e2, det, N) && N > 0.f;
 }
 template <bool COUNT, bool NB, bool NEAR, bool VOTE3>
 __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_signed(SignedArgs a) {
@@ -3854,7 +3861,183 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_signed(SignedArgs a) {
     }
 }
 
+// ---- self-collision queries (rtbvh_collide_async): the crossing pairs of the mesh's own triangles ---------------
+// k_overlap's frame and CSR protocol with the tree's own leaves for queries: the lane that claims k takes the leaf at
+// sorted position k -- its box is the query box, the claims come in sort order, which is the coherent order -- and
+// lists the leaves it is paired with under include/rtbvh.h's rules: the position filter (partner position > k: a
+// pair is listed by its earlier triangle; SYM: != k, by both), (B) on the two leaf boxes, (N) no common vertex
+// index -- one gather of the partner's three indices, only behind (B) -- and, under TRI, (X): one of the six
+// segment-triangle tests holds, cross_line's arithmetic with both ends of the segment checked.  The node test is
+// k_overlap's (B), so the walk reaches every member, left first: a list is in sort order.
+// The half a triangle does not own is pruned by leaf range (!SYM).  Karras node i splits its range [lo, hi] at g:
+// its left child is node or leaf g over [lo, g], its right one g + 1 over [g + 1, hi].  So the left child's range
+// ends at its own id, which the step holds in either tree form, and it is skipped iff g <= k; the right child's
+// range ends where its parent's does, past k by induction from the root's T - 1 (position T - 1 owns nothing and
+// is not walked).  No fetch is added, and the lists are the same with and without: a skipped subtree holds
+// positions <= k only, all of which the position filter drops.
+__device__ __forceinline__ bool segment_cross(f3 p, f3 d, f3 p0, f3 e1, f3 e2) {
+    float det, N;
+    return cross_line(p, d, p0, e1, e2, det, N) && N >= 0.f && N <= det;
+}
+// the segments S0 = (a, e1), S1 = (a, e2), S2 = (fl(a + e1), fl(e2 - e1)) of one triangle against the other
+__device__ __forceinline__ bool edges_cross(f3 a, f3 e1, f3 e2, f3 p0, f3 f1, f3 f2) {
+    return segment_cross(a, e1, p0, f1, f2) || segment_cross(a, e2, p0, f1, f2) ||
+           segment_cross(add(a, e1), sub(e2, e1), p0, f1, f2);
+}
+// Every instance fits 64 registers without a spill at 8 waves per SIMD, the TRI ones too: the six tests run one
+// after the other on the 16 floats of the query and the 9 of the partner (DESIGN.md 5k has each instance's count).
+template <bool FILL, bool COUNT, bool NB, bool TRI, bool SYM>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_collide(CollideArgs a) {
+    const uint32_t T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const uint32_t* __restrict__ idx = a.idx;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t ntris = 0;
+    unsigned long long nids = 0;
+    bool has = false;
+    uint32_t k = 0, id = 0, cnt = 0;          // the query leaf's position and triangle, its partners so far
+    uint32_t i0 = 0, i1 = 0, i2 = 0;          // its vertex indices
+    unsigned long long pos = 0, end = 0;      // FILL: the next id's index and the end of the triangle's segment
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    f3 qlo = mk(0.f, 0.f, 0.f), qhi = mk(0.f, 0.f, 0.f);
+    f3 qa = mk(0.f, 0.f, 0.f), qe1 = mk(0.f, 0.f, 0.f), qe2 = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, T, has, [&](uint32_t p) {   // this lane takes the leaf at sorted position p
+            k = p;
+            const float4* r = leaf + 4 * (size_t)p;
+            const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+            id = __float_as_uint(r2.y) & ~LEAF_BIT;
+            qlo = mk(r2.z, r2.w, r3.x);
+            qhi = mk(r3.y, r3.z, r3.w);
+            if (TRI) {
+                qa = mk(r0.x, r0.y, r0.z);
+                qe1 = mk(r0.w, r1.x, r1.y);
+                qe2 = mk(r1.z, r1.w, r2.x);
+            }
+            if (COUNT && a.count_ids) ntris++;
+            // no walk: a NaN in the leaf box fails (B) with every box; the last position owns no pair
+            if (!(qlo.x <= qhi.x && qlo.y <= qhi.y && qlo.z <= qhi.z) || (!SYM && p + 1 == T)) {
+                if (!FILL) a.offsets[(size_t)id + 1] = 0;
+            } else {
+                has = true;
+                i0 = idx[3 * (size_t)id];
+                i1 = idx[3 * (size_t)id + 1];
+                i2 = idx[3 * (size_t)id + 2];
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[id];
+                    const unsigned long long e = a.offsets[(size_t)id + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0, gl = 0;   // gl: the left child's Karras id, where its leaf range ends
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                gl = __float_as_uint(q3.x) & ~LEAF_BIT;
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            gl = ch.cl & ~LEAF_BIT;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            const uint32_t j = w.node & ~LEAF_BIT;
+            const uint32_t y = __float_as_uint(q2.y) & ~LEAF_BIT;
+            bool in = (SYM ? j != k : j > k) && boxes_meet(qlo, qhi, mk(q2.z, q2.w, q3.x), mk(q3.y, q3.z, q3.w));
+            if (in) {   // (N): the partner's three indices
+                const uint32_t y0 = idx[3 * (size_t)y], y1 = idx[3 * (size_t)y + 1], y2 = idx[3 * (size_t)y + 2];
+                in = i0 != y0 && i0 != y1 && i0 != y2 && i1 != y0 && i1 != y1 && i1 != y2 && i2 != y0 && i2 != y1 &&
+                     i2 != y2;
+            }
+            if (TRI && in) {
+                const f3 p0 = mk(q0.x, q0.y, q0.z), f1 = mk(q0.w, q1.x, q1.y), f2 = mk(q1.z, q1.w, q2.x);
+                in = edges_cross(qa, qe1, qe2, p0, f1, f2) || edges_cross(p0, f1, f2, qa, qe1, qe2);
+            }
+            if (in) {
+                if (!FILL || COUNT) cnt++;
+                if (FILL && pos < end) {
+                    a.ids[pos] = y;
+                    pos++;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = (SYM || gl > k) && boxes_meet(qlo, qhi, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const bool rh = boxes_meet(qlo, qhi, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            if (!FILL) a.offsets[(size_t)id + 1] = cnt;
+            if (COUNT && a.count_ids) nids += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {ntris, nids, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int i = 0; i < 4; i++) atomicAdd(&a.counts[i], v[i]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_collide(const CollideArgs& a, bool fill, bool count, bool tri, bool sym, hipStream_t s) {
+    if (a.T == 0) return;
+    const uint32_t need = (a.T + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto FILL, auto COUNT, auto NB, auto TRI, auto SYM) {
+        hipLaunchKernelGGL((k_collide<FILL, COUNT, NB, TRI, SYM>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.nb, tri, sym);
+}
 
 void launch_signed(const SignedArgs& a, bool count, bool near, bool vote3, hipStream_t s) {
     if (a.n == 0) return;

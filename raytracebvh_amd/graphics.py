@@ -833,6 +833,96 @@ class Context:
         self._check(_L.lib().rtbvh_overlap_counts(self._h, _L.ptr(out)))
         return dict(zip(("boxes", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- self-collision queries --
+    def collide(self, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None, device: bool = False):
+        """rtbvh_collide_async / rtbvh_collide_host: the pairs of the built mesh's own triangles whose leaf boxes meet
+        and that share no vertex index and, with COLLIDE_TRIANGLE, that cross each other (the header's six
+        segment-triangle tests), as (offsets, ids) in CSR form over the T triangles: triangle i's partners are
+        ids[offsets[i]:offsets[i + 1]], in the last build's sort order (read_sorted), and offsets[T] is the total.  A
+        pair is listed once, by the triangle that comes earlier in that order; with COLLIDE_SYMMETRIC by both.
+
+        device=False goes through the synchronous host entry and returns a uint64 (T + 1,) array and a uint32 array
+        of offsets[T] ids (of min(offsets[T], capacity) when `capacity` is given).  device=True goes to the device
+        entry, enqueued on `stream` as overlap's, and returns an int64 (T + 1,) device tensor and an int32
+        (capacity,) device tensor whose entries [0, min(total, capacity)) are written.  With `capacity` given that
+        is one call, with no host copy and no synchronisation -- compare offsets[-1] with it afterwards; with
+        capacity=None a COLLIDE_SIZES call, one .item() read of the total (the only synchronisation) and a
+        COLLIDE_FILL call.  sizes_only=True returns the offsets alone.  mode: COLLIDE_COUNT, COLLIDE_TRIANGLE,
+        COLLIDE_SYMMETRIC (COLLIDE_SIZES and COLLIDE_FILL are this method's to set)."""
+        if mode & (_L.COLLIDE_SIZES | _L.COLLIDE_FILL):
+            raise ValueError("collide: COLLIDE_SIZES and COLLIDE_FILL are set by collide itself")
+        if mode & ~(_L.COLLIDE_COUNT | _L.COLLIDE_TRIANGLE | _L.COLLIDE_SYMMETRIC):
+            raise ValueError(f"collide: unknown mode bits {mode:#x}")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"collide: capacity must be a non-negative integer, got {capacity!r}")
+        if sizes_only and capacity is not None:
+            raise ValueError("collide: sizes_only takes no capacity")
+        n = self.num_tris
+        L = _L.lib()
+        if not device:
+            if stream is not None:
+                raise ValueError("collide: a stream goes with device=True")
+            offsets = np.zeros(n + 1, np.uint64)
+            o = ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                ids = np.zeros(int(capacity), np.uint32)
+                self._check(L.rtbvh_collide_host(self._h, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
+                return offsets, ids[:min(int(offsets[n]), len(ids))]
+            self._check(L.rtbvh_collide_host(self._h, o, None, 0, mode | _L.COLLIDE_SIZES))
+            if sizes_only:
+                return offsets
+            ids = np.zeros(int(offsets[n]), np.uint32)
+            self._check(L.rtbvh_collide_host(self._h, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
+                                             mode | _L.COLLIDE_FILL))
+            return offsets, ids
+        import torch
+        dev = torch.device("cuda", self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(dev).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        o = ctypes.c_void_p(offsets.data_ptr())
+
+        def call(ids, m):
+            self._check(L.rtbvh_collide_async(self._h, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
+                                              and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            ids = torch.empty(int(capacity), dtype=torch.int32, device=dev)
+            call(ids, mode)
+            return offsets, ids
+        call(None, mode | _L.COLLIDE_SIZES)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=dev)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        ids = torch.empty(total, dtype=torch.int32, device=dev)
+        call(ids, mode | _L.COLLIDE_FILL)
+        return offsets, ids
+
+    def collide_pairs(self, triangle: bool = True) -> np.ndarray:
+        """The member pairs as a (P, 2) uint32 array of triangle ids (i, j), expanded from collide()'s default CSR
+        form: row by row the owner i (the earlier triangle in the build's sort order) and one of its partners j."""
+        offsets, ids = self.collide(_L.COLLIDE_TRIANGLE if triangle else 0)
+        owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.uint32), np.diff(offsets).astype(np.int64))
+        return np.stack([owner, ids], 1)
+
+    def collide_counts(self) -> dict:
+        """rtbvh_collide_counts: triangles, entries (the total), internal-node and leaf steps (summed over the
+        passes) of the last COLLIDE_COUNT query (the other queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_collide_counts(self._h, _L.ptr(out)))
+        return dict(zip(("triangles", "entries", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- signed-distance queries --
     def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
         """rtbvh_signed_async / rtbvh_signed_host: for each point Context.nearest's fields and `flags`, the crossing
