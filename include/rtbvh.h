@@ -348,7 +348,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * After an update the built tree is not of the geometry: until the next rtbvh_build*, rtbvh_refit* or
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
  * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_*, rtbvh_khits_* and
- * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, as do rtbvh_collide_async and rtbvh_collide_host, and the
+ * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, as do rtbvh_collide_async, rtbvh_collide_host, rtbvh_cross_async,
+ * rtbvh_cross_host, rtbvh_cross_first_async and rtbvh_cross_first_host, and the
  * rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
@@ -818,6 +819,89 @@ rtbvh_status rtbvh_collide_host(rtbvh_ctx* ctx, uint64_t* offsets, uint32_t* ids
  * internal-node steps and leaf steps summed over the passes the call ran.  Its own words: the other queries' counts
  * keep theirs.  RTBVH_ERR_NOT_READY before any counting self-collision query. */
 rtbvh_status rtbvh_collide_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- triangle queries: the scene triangles that a caller's triangle crosses --------
+ * (No reference equivalent; Embree's rtcCollide of a second mesh with the built one.)  The query triangles live in
+ * the space the BVH was built in, as every other query's input.  The result of query triangle q is the list of the
+ * ids (in triangle order, Node.index / 3) of exactly the scene triangles that are MEMBERS of it, specified operation
+ * for operation, independently of the tree and of the walk.  From q's vertices, in fp32 without contraction:
+ *     a = v0,  e1 = fl(v1 - v0),  e2 = fl(v2 - v0),
+ *     qlo = fminf(fminf(v0, v1), v2),  qhi = fmaxf(fmaxf(v0, v1), v2), per component
+ * -- the floats a leaf record would hold if q were a scene triangle.  For a scene triangle x its leaf record's p0,
+ * e1, e2 and its leaf box [lo, hi], as in the self-collision section.  x is a member of q iff
+ *  (B) on every axis k: qlo_k <= hi_k && lo_k <= qhi_k.  Closed intervals (touching counts), no arithmetic; a NaN
+ *      fails it.
+ *  (X) at least one of the six tests "segment S_k(q) crosses triangle x", "segment S_k(x) crosses triangle q",
+ *      k = 0 .. 2, holds: the self-collision section's segments S0, S1, S2 and its rule "segment (P, D) crosses the
+ *      triangle (p0, e1, e2)", unchanged, with q's (a, e1, e2) in the place of a leaf record's.
+ * There is no rule (N): the caller's mesh has no indices in common with the scene's.
+ * Limits: coplanar pairs have det = 0 in every test and are not listed.  A contact within rounding can go either
+ * way, but the same way on every tree.  A query triangle that lies entirely inside a closed mesh crosses nothing: its
+ * list is empty (containment is rtbvh_signed_*'s question).  A scene triangle queried with its own floats may or may
+ * not list itself (rounding in det).
+ * The list is empty, and there is no walk, for a query triangle with a non-finite component in any vertex.
+ * Degenerate triangles (a point, a needle) are valid queries and follow the rules above.
+ * The set is exact whatever the tree: (B) is monotone in the tree's box, so a walk that enters a child iff its box
+ * meets [qlo, qhi] reaches every member (the box queries' argument).
+ * Order and output are rtbvh_overlap_async's, word for word: each list ascends by the member's position in the last
+ * build's sort order (tri_ids of rtbvh_read_sorted; a refit keeps it); CSR form, dev_offsets[0] = 0, query k's ids
+ * are dev_ids[dev_offsets[k] .. dev_offsets[k + 1]), and dev_offsets[n] is the true total whatever `capacity` is.  An
+ * id whose index is >= capacity is not written: nothing is ever written at or past dev_ids + capacity, capacity may
+ * be 0 (dev_ids may then be NULL), and the caller compares dev_offsets[n] with capacity. */
+typedef struct {
+    float v0[3];
+    uint32_t reserved0; /* ignored */
+    float v1[3];
+    uint32_t reserved1; /* ignored */
+    float v2[3];
+    uint32_t reserved2; /* ignored */
+} rtbvh_tri; /* 48 B: three 16-B words */
+enum {
+    RTBVH_CROSS_SORT = 1u << 1,  /* walk the queries in the Morton order of their box centres: same output */
+    RTBVH_CROSS_COUNT = 1u << 2, /* count queries, ids and steps for rtbvh_cross_counts (slower) */
+    RTBVH_CROSS_SIZES = 1u << 4, /* write dev_offsets only; dev_ids may be NULL */
+    RTBVH_CROSS_FILL = 1u << 5   /* dev_offsets is INPUT (from a SIZES call for the same triangles and tree): write
+                                    the ids only */
+    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG */
+};
+/* n triangles at dev_tris (16-B aligned), n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` ids at
+ * dev_ids (device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the context stream).
+ * Mode 0 runs the sizes pass, a scan of the offsets on the device and the fill pass in one call, with no host round
+ * trip; RTBVH_CROSS_SIZES then RTBVH_CROSS_FILL is the two-call form.  A FILL over any non-decreasing offsets writes
+ * query k's ids only inside [dev_offsets[k], min(dev_offsets[k + 1], capacity)): offsets of another tree or of other
+ * triangles truncate lists, they never make a write go astray.  RTBVH_CROSS_SORT's key is the 30-bit Morton code, in
+ * the root box, of (qlo + qhi) * 0.5f, as RTBVH_OVERLAP_SORT's; one permutation serves both passes.
+ * Everything else follows rtbvh_overlap_async one for one: the tree forms read, the waits, the place among the other
+ * queries, the growing of the sort's buffers and the scan's block sums.  n == 0 returns RTBVH_OK and writes
+ * dev_offsets[0] = 0 only if dev_offsets is non-NULL; RTBVH_ERR_NOT_READY before a build and after a vertex update
+ * until the next build or refit; RTBVH_ERR_INVALID_ARG for NULL triangles or offsets with n > 0, NULL ids with
+ * capacity > 0 outside RTBVH_CROSS_SIZES, bad mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit loses that subtree's ids -- both passes lose the same ids, so offsets and
+ * ids stay consistent -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_cross_async(rtbvh_ctx* ctx, const rtbvh_tri* dev_tris, uint64_t n, uint64_t* dev_offsets,
+                               uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (n + 1) and ids are
+ * host arrays; ids receives min(total, capacity) entries.  With RTBVH_CROSS_FILL, offsets is read. */
+rtbvh_status rtbvh_cross_host(rtbvh_ctx* ctx, const rtbvh_tri* tris, uint64_t n, uint64_t* offsets, uint32_t* ids,
+                              uint64_t capacity, uint32_t mode);
+/* "Does it touch anything, and what first": dev_first[k] (n uint32, 4-B aligned) = the first id of query k's list
+ * -- the member at the lowest sort position -- or 0xFFFFFFFF for an empty list.  One pass, no CSR; the walk of a
+ * query ends at its first member.  Exactly the head of rtbvh_cross_async's list on every tree: a left-first
+ * depth-first walk meets the leaves in ascending sort position, which the list order above already relies on.
+ * mode: RTBVH_CROSS_SORT and RTBVH_CROSS_COUNT only.  n == 0 returns RTBVH_OK and touches nothing; NULL triangles
+ * or dev_first with n > 0, other mode bits and n >= 2^31 are RTBVH_ERR_INVALID_ARG; RTBVH_ERR_NOT_READY as above.
+ * A walk that hits rtbvh_config.stack_limit returns the head of the shortened list, and the next synchronising call
+ * returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_cross_first_async(rtbvh_ctx* ctx, const rtbvh_tri* dev_tris, uint64_t n, uint32_t* dev_first,
+                                     uint32_t mode, void* stream);
+/* Host-memory wrapper of the above (synchronous, on the context stream): first receives n entries. */
+rtbvh_status rtbvh_cross_first_host(rtbvh_ctx* ctx, const rtbvh_tri* tris, uint64_t n, uint32_t* first,
+                                    uint32_t mode);
+/* The last RTBVH_CROSS_COUNT query of either entry (waits for it): queries, ids (the true total, counted once; for
+ * rtbvh_cross_first_* the queries with a member), internal-node steps and leaf steps summed over the passes the call
+ * ran.  Its own words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting triangle
+ * query. */
+rtbvh_status rtbvh_cross_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
  * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The

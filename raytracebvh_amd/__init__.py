@@ -13,10 +13,11 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    SIGNED_COUNT, SIGNED_DTYPE, SIGNED_INSIDE_ONLY, SIGNED_SORT, SIGNED_VOTE3,
                    KHITS_COUNT, KHITS_MAX_K, KHITS_SORT,
                    COLLIDE_COUNT, COLLIDE_FILL, COLLIDE_SIZES, COLLIDE_SYMMETRIC, COLLIDE_TRIANGLE,
+                   CROSS_COUNT, CROSS_FILL, CROSS_SIZES, CROSS_SORT, TRI_DTYPE,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
-from .graphics import (Context, Graphics, check_nearest_points, check_overlap_boxes, check_query_rays,
-                       check_vertex_array, comm_destroy, comm_unique_id, make_boxes, make_points, make_rays, save_bmp)
+from .graphics import (Context, Graphics, check_cross_tris, check_nearest_points, check_overlap_boxes, check_query_rays,
+                       check_vertex_array, comm_destroy, comm_unique_id, make_boxes, make_points, make_rays, make_tris, save_bmp)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
                     camera_reference, load_npz, load_obj, synthetic)
 
@@ -38,4 +39,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "SIGNED_DTYPE", "SIGNED_SORT", "SIGNED_COUNT", "SIGNED_VOTE3", "SIGNED_INSIDE_ONLY",
            "KHITS_SORT", "KHITS_COUNT", "KHITS_MAX_K",
            "COLLIDE_COUNT", "COLLIDE_TRIANGLE", "COLLIDE_SIZES", "COLLIDE_FILL", "COLLIDE_SYMMETRIC",
+           "TRI_DTYPE", "CROSS_SORT", "CROSS_COUNT", "CROSS_SIZES", "CROSS_FILL", "make_tris", "check_cross_tris",
            "check_query_rays", "check_vertex_array"]

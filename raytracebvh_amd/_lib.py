@@ -54,6 +54,7 @@ EXPORTS = [
     "rtbvh_signed_async", "rtbvh_signed_host", "rtbvh_signed_counts",
     "rtbvh_khits_async", "rtbvh_khits_host", "rtbvh_khits_counts",
     "rtbvh_collide_async", "rtbvh_collide_host", "rtbvh_collide_counts",
+    "rtbvh_cross_async", "rtbvh_cross_host", "rtbvh_cross_first_async", "rtbvh_cross_first_host", "rtbvh_cross_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -97,6 +98,11 @@ KHITS_SORT, KHITS_COUNT = 2, 4   # RTBVH_KHITS_*; its lists are HIT_DTYPE, a slo
 KHITS_MAX_K = 16                 # RTBVH_KHITS_MAX_K
 # RTBVH_COLLIDE_*; its lists hold triangle ids (uint32), indexed by triangle
 COLLIDE_COUNT, COLLIDE_TRIANGLE, COLLIDE_SIZES, COLLIDE_FILL, COLLIDE_SYMMETRIC = 4, 8, 16, 32, 64
+# rtbvh_tri: a query triangle of the triangle queries, three 16-byte words
+TRI_DTYPE = np.dtype([("v0", "<f4", (3,)), ("reserved0", "<u4"), ("v1", "<f4", (3,)), ("reserved1", "<u4"),
+                      ("v2", "<f4", (3,)), ("reserved2", "<u4")])
+assert TRI_DTYPE.itemsize == 48
+CROSS_SORT, CROSS_COUNT, CROSS_SIZES, CROSS_FILL = 2, 4, 16, 32   # RTBVH_CROSS_*; its lists hold triangle ids (uint32)
 
 
 class Config(ctypes.Structure):
@@ -278,6 +284,11 @@ def lib() -> ctypes.CDLL:
         "rtbvh_collide_async": (i32, [vp, vp, vp, u64, u32, vp]),
         "rtbvh_collide_host": (i32, [vp, vp, vp, u64, u32]),
         "rtbvh_collide_counts": (i32, [vp, vp]),
+        "rtbvh_cross_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
+        "rtbvh_cross_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
+        "rtbvh_cross_first_async": (i32, [vp, vp, u64, vp, u32, vp]),
+        "rtbvh_cross_first_host": (i32, [vp, vp, u64, vp, u32]),
+        "rtbvh_cross_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

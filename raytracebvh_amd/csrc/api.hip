@@ -327,6 +327,7 @@ struct rtbvh_ctx {
     bool signed_counted = false;             // the signed-distance queries' count block holds a RTBVH_SIGNED_COUNT query's counts
     bool khits_counted = false;              // the first-k queries' count block holds a RTBVH_KHITS_COUNT query's counts
     bool collide_counted = false;            // the self-collision queries' count block holds a RTBVH_COLLIDE_COUNT query's counts
+    bool cross_counted = false;              // the triangle queries' count block holds a RTBVH_CROSS_COUNT query's counts
 };
 
 namespace {
@@ -2998,6 +2999,190 @@ rtbvh_status rtbvh_collide_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_COLLIDE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- triangle queries ----------------------------------------------------------------------------------
+// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain; [keys + sort], then
+// [sizes + scan], then [fill], all on the caller's stream.  rtbvh_cross_first_async is [keys + sort] and one launch,
+// with no scan.  Their count block is QUERY_CROSS_AT.
+namespace {
+// the tree, the queries, the walk order (sort: grows the shared sort buffers) and the counters of a k_cross launch
+rtbvh_status cross_args(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint32_t N, bool sort, bool grow_scan, bool count,
+                        hipStream_t s, CrossArgs& a) {
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)N) && c->d_qsort_scratch.has(sort_scratch_words(N)));
+    if (grow_sort || grow_scan) {
+        // (as rtbvh_overlap_async: earlier queries sort and scan in the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        if (grow_sort) {
+            HIPC(c, c->d_qsort.reserve(6 * (size_t)N));
+            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
+        }
+        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_CROSS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.tris = reinterpret_cast<const float4*>(dev_tris);
+    a.n = N;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_CROSS_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sort) {   // one permutation for every pass of the call
+        uint32_t* q = c->d_qsort;
+        const size_t m = c->d_qsort.cap / 6;
+        launch_cross_keys(a.tris, N, c->d_rootbox, q, q + m, s);
+        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    }
+    return RTBVH_OK;
+}
+}  // namespace
+
+rtbvh_status rtbvh_cross_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, uint64_t* dev_offsets,
+                               uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT | RTBVH_CROSS_SIZES | RTBVH_CROSS_FILL;
+    constexpr uint32_t BOTH = RTBVH_CROSS_SIZES | RTBVH_CROSS_FILL;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: 2^31 triangles or more");
+    const bool sizes = !(mode & RTBVH_CROSS_FILL), fill = !(mode & RTBVH_CROSS_SIZES);
+    static_assert(sizeof(rtbvh_tri) == 48 && sizeof(uint64_t) == sizeof(unsigned long long), "triangle query layouts");
+    if (n == 0) {
+        if (!dev_offsets || !sizes) return RTBVH_OK;
+        HIPC(c, hipSetDevice(c->cfg.device));
+        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+        return RTBVH_OK;
+    }
+    if (!dev_tris || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: NULL triangles or offsets");
+    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: NULL ids");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "cross before build");
+    if (c->stale) return fail_stale(c, "cross");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_CROSS_SORT) != 0, count = (mode & RTBVH_CROSS_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    CrossArgs a{};
+    TRY(cross_args(c, dev_tris, N, sort, sizes && !c->d_qscan.has(scan_sums_words(N)), count, s, a));
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.ids = dev_ids;
+    a.capacity = capacity;
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_ids = true;
+        launch_cross(a, CROSS_PASS_SIZES, count, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_ids = !sizes;
+        launch_cross(a, CROSS_PASS_FILL, count, s);
+    }
+    rtbvh_status st = check_launch(c, "cross kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->cross_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_cross_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, uint64_t* offsets, uint32_t* ids,
+                              uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_CROSS_FILL) != 0, sizes_only = (mode & RTBVH_CROSS_SIZES) != 0;
+    if (n == 0) {   // (nothing to stage)
+        const rtbvh_status st = rtbvh_cross_async(c, tris, 0, nullptr, ids, capacity, mode, nullptr);
+        if (!st && offsets && !fill_only) offsets[0] = 0;
+        return st;
+    }
+    if (n >= (1ull << 31) || !tris || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
+        !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_cross_async(c, tris, n, offsets, ids, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // offsets, then triangles: 8- and 16-B aligned
+    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
+    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_tri)));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
+    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d + off_bytes);
+    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_host: upload failed");
+    DevBuf<uint32_t> dids;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another tree or other triangles leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
+    TRY(rtbvh_cross_async(c, dt, n, doff, dids, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "cross_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_cross_first_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, uint32_t* dev_first,
+                                     uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: 2^31 triangles or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_tris || !dev_first) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: NULL triangles or output");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "cross_first before build");
+    if (c->stale) return fail_stale(c, "cross_first");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_CROSS_SORT) != 0, count = (mode & RTBVH_CROSS_COUNT) != 0;
+    CrossArgs a{};
+    TRY(cross_args(c, dev_tris, (uint32_t)n, sort, false, count, s, a));
+    a.first = dev_first;
+    a.count_ids = true;
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    launch_cross(a, CROSS_PASS_FIRST, count, s);
+    rtbvh_status st = check_launch(c, "cross_first kernel");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->cross_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_cross_first_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, uint32_t* first, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || !tris || !first || !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_cross_first_async(c, tris, n, first, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // triangles, then the output
+    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_tri) + sizeof(uint32_t))));
+    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d.h);
+    uint32_t* df = reinterpret_cast<uint32_t*>(d + (size_t)n * sizeof(rtbvh_tri));
+    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_first_host: upload failed");
+    TRY(rtbvh_cross_first_async(c, dt, n, df, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "cross_first_host: sync");
+    if (hipMemcpy(first, df, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "cross_first_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_cross_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->cross_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_CROSS_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CROSS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

@@ -579,9 +579,42 @@ struct CollideArgs {
 };
 // the self-collision queries' own count block, behind the first-k queries'
 constexpr uint32_t QUERY_COLLIDE_AT = QUERY_KHITS_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_COLLIDE_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_COLLIDE_AT % 2 == 0, "the count block's 8-byte words");
 // tri: rule (X), the six segment-triangle tests; sym: both triangles of a pair list it
 void launch_collide(const CollideArgs& a, bool fill, bool count, bool tri, bool sym, hipStream_t s);
+
+// ---- triangle queries (trace.hip k_cross; rtbvh_cross_async, rtbvh_cross_first_async) -------
+// Query triangles (three float4 each: {v0.xyz, -}, {v1.xyz, -}, {v2.xyz, -}) on the same tree forms.  The sizes
+// and fill passes are OverlapArgs' CSR output indexed by query; the first pass stores at first[r] the id of the
+// first member its walk meets, or 0xFFFFFFFF, and ends the walk there.
+enum CrossPass { CROSS_PASS_SIZES = 0, CROSS_PASS_FILL = 1, CROSS_PASS_FIRST = 2 };
+struct CrossArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* tris;       // [3n]
+    unsigned long long* offsets;    // [n + 1]: the sizes pass writes [1, n], the fill pass reads
+    uint32_t* ids;            // the fill pass: [capacity] triangle ids
+    uint32_t* first;          // the first pass: [n]
+    unsigned long long capacity;
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_CROSS_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_CROSS_COUNT: [4] queries, ids, internal-node steps, leaf steps
+    bool count_ids;           // ... this pass adds the queries and ids (one pass of a call does), not only steps
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the triangle queries' own count block, behind the self-collision queries'
+constexpr uint32_t QUERY_CROSS_AT = QUERY_COLLIDE_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_CROSS_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_CROSS_AT % 2 == 0, "the count block's 8-byte words");
+void launch_cross(const CrossArgs& a, CrossPass pass, bool count, hipStream_t s);
+// RTBVH_CROSS_SORT's keys (the 30-bit Morton codes, in the root box, of the query boxes' centres) and vals[i] = i
+void launch_cross_keys(const float4* tris, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                       hipStream_t s);
 
 }  // namespace rtbvh

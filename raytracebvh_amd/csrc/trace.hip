@@ -4029,7 +4029,189 @@ __global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_collide(CollideArgs a) 
     }
 }
 
+// ---- triangle queries (rtbvh_cross_async, rtbvh_cross_first_async): what a caller's triangle crosses -------------
+// k_overlap's frame and CSR protocol with a caller's triangle for the query: the claiming lane loads its three 16-B
+// words and keeps what a leaf record would hold of it -- a, e1 = v1 - v0, e2 = v2 - v0 and the box [qlo, qhi] of the
+// three vertices, 15 floats -- and lists the leaves that pass include/rtbvh.h's rules: (B) on the leaf's own box,
+// then (X), k_collide's six segment-triangle tests through edges_cross.  The node test is k_overlap's (B), so the
+// walk reaches every member, left first: a list is in sort order.
+// PASS: CROSS_PASS_SIZES and CROSS_PASS_FILL are k_overlap's two passes.  CROSS_PASS_FIRST stores the first member
+// met at first[r] and ends the walk there -- left first, that is the member at the lowest sort position, the head of
+// the list -- and 0xFFFFFFFF when the walk ends without one.
+// The four record loads are not pinned (k_collide's choice, not k_overlap's): every instance fits 64 registers
+// without a spill at 8 waves per SIMD as it is, and pinned each of the twelve took the same registers (DESIGN.md 5l
+// has each instance's count).
+template <int PASS, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, BOUNCE_WAVES) void k_cross(CrossArgs a) {
+    constexpr bool SIZES = PASS == CROSS_PASS_SIZES, FILL = PASS == CROSS_PASS_FILL, FIRST = PASS == CROSS_PASS_FIRST;
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nqueries = 0;
+    unsigned long long nids = 0;
+    bool has = false;
+    uint32_t r = 0, cnt = 0;
+    unsigned long long pos = 0, end = 0;   // FILL: the next id's index and the end of the query's segment
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    f3 qlo = mk(0.f, 0.f, 0.f), qhi = mk(0.f, 0.f, 0.f);
+    f3 qa = mk(0.f, 0.f, 0.f), qe1 = mk(0.f, 0.f, 0.f), qe2 = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th triangle of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 t0 = a.tris[3 * (size_t)r], t1 = a.tris[3 * (size_t)r + 1], t2 = a.tris[3 * (size_t)r + 2];
+            const f3 v0 = mk(t0.x, t0.y, t0.z), v1 = mk(t1.x, t1.y, t1.z), v2 = mk(t2.x, t2.y, t2.z);
+            if (COUNT && a.count_ids) nqueries++;
+            const bool finite = fabsf(v0.x) < INFINITY && fabsf(v0.y) < INFINITY && fabsf(v0.z) < INFINITY &&
+                                fabsf(v1.x) < INFINITY && fabsf(v1.y) < INFINITY && fabsf(v1.z) < INFINITY &&
+                                fabsf(v2.x) < INFINITY && fabsf(v2.y) < INFINITY && fabsf(v2.z) < INFINITY;
+            if (!finite) {   // no walk: an empty list
+                if (SIZES) a.offsets[(size_t)r + 1] = 0;
+                if (FIRST) a.first[r] = INVALID;
+            } else {
+                has = true;
+                qa = v0;
+                qe1 = sub(v1, v0);
+                qe2 = sub(v2, v0);
+                qlo = mk(fminf(fminf(v0.x, v1.x), v2.x), fminf(fminf(v0.y, v1.y), v2.y), fminf(fminf(v0.z, v1.z), v2.z));
+                qhi = mk(fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z));
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[r];
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            bool in = boxes_meet(qlo, qhi, mk(q2.z, q2.w, q3.x), mk(q3.y, q3.z, q3.w));   // the leaf's own box first
+            if (in) {
+                const f3 p0 = mk(q0.x, q0.y, q0.z), f1 = mk(q0.w, q1.x, q1.y), f2 = mk(q1.z, q1.w, q2.x);
+                in = edges_cross(qa, qe1, qe2, p0, f1, f2) || edges_cross(p0, f1, f2, qa, qe1, qe2);
+            }
+            if (in) {
+                if (!FILL || COUNT) cnt++;
+                if (FILL && pos < end) {
+                    a.ids[pos] = __float_as_uint(q2.y) & ~LEAF_BIT;
+                    pos++;
+                }
+                if (FIRST) a.first[r] = __float_as_uint(q2.y) & ~LEAF_BIT;
+            }
+            if (FIRST && in) {   // the head of the list: the walk ends here
+                done = true;
+            } else {
+                walk_pop(w, st);
+                done = w.sp == -1;
+            }
+        } else {
+            if (COUNT) c.internal++;
+            const bool lh = boxes_meet(qlo, qhi, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const bool rh = boxes_meet(qlo, qhi, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                if (lh && rh) {   // left first: push the right child
+                    st.store(w.sp, w.top);
+                    w.sp++;
+                    w.top = cr;
+                }
+                w.node = lh ? cl : cr;
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            if (SIZES) a.offsets[(size_t)r + 1] = cnt;
+            if (FIRST && cnt == 0) a.first[r] = INVALID;
+            if (COUNT && a.count_ids) nids += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nqueries, nids, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
+// RTBVH_CROSS_SORT's key: the 30-bit Morton code, in the root box, of the centre of the query triangle's box
+// (k_overlap_keys' code)
+__global__ __launch_bounds__(BLOCK) void k_cross_keys(const float4* __restrict__ tris, uint32_t n,
+                                                      const float* __restrict__ box, uint32_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 v0 = tris[3 * (size_t)i], v1 = tris[3 * (size_t)i + 1], v2 = tris[3 * (size_t)i + 2];
+    const f3 lo = mk(fminf(fminf(v0.x, v1.x), v2.x), fminf(fminf(v0.y, v1.y), v2.y), fminf(fminf(v0.z, v1.z), v2.z));
+    const f3 hi = mk(fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z));
+    keys[i] = spread9(q9((lo.x + hi.x) * 0.5f, box[0], box[3])) << 2 |
+              spread9(q9((lo.y + hi.y) * 0.5f, box[1], box[4])) << 1 | spread9(q9((lo.z + hi.z) * 0.5f, box[2], box[5]));
+    vals[i] = i;
+}
+
 }  // namespace
+
+void launch_cross(const CrossArgs& a, CrossPass pass, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * BOUNCE_WAVES ? need : 256 * BOUNCE_WAVES;
+    with_bools([&](auto COUNT, auto NB) {
+        if (pass == CROSS_PASS_SIZES)
+            hipLaunchKernelGGL((k_cross<CROSS_PASS_SIZES, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+        else if (pass == CROSS_PASS_FILL)
+            hipLaunchKernelGGL((k_cross<CROSS_PASS_FILL, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_cross<CROSS_PASS_FIRST, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, count, a.nb);
+}
+
+void launch_cross_keys(const float4* tris, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
+                       hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_cross_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, tris, n, box, keys, vals);
+}
 
 void launch_collide(const CollideArgs& a, bool fill, bool count, bool tri, bool sym, hipStream_t s) {
     if (a.T == 0) return;

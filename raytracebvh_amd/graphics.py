@@ -196,6 +196,56 @@ def check_overlap_boxes(boxes, hi=None, device=None):
     return "numpy", boxes.view(_L.BOX_DTYPE).reshape(-1)
 
 
+def make_tris(vertices):
+    """Packs (N, 3, 3) or (N, 9) triangle vertices {v0, v1, v2} as triangle queries: a torch tensor gives an (N, 12)
+    float32 tensor on its device, anything else a TRI_DTYPE array (include/rtbvh.h rtbvh_tri).  The triangles live
+    in the space the BVH was built in."""
+    if _is_tensor(vertices):
+        import torch
+        v = vertices.to(torch.float32)
+        if not ((v.dim() == 3 and tuple(v.shape[1:]) == (3, 3)) or (v.dim() == 2 and v.shape[1] == 9)):
+            raise ValueError(f"make_tris: vertices must be (N, 3, 3) or (N, 9), got {tuple(v.shape)}")
+        out = torch.zeros((v.shape[0], 3, 4), dtype=torch.float32, device=v.device)
+        out[:, :, 0:3] = v.reshape(-1, 3, 3)
+        return out.reshape(-1, 12)
+    v = np.asarray(vertices, np.float32)
+    if not ((v.ndim == 3 and v.shape[1:] == (3, 3)) or (v.ndim == 2 and v.shape[1] == 9)):
+        raise ValueError(f"make_tris: vertices must be (N, 3, 3) or (N, 9), got {v.shape}")
+    v = v.reshape(-1, 3, 3)
+    out = np.zeros(len(v), _L.TRI_DTYPE)
+    out["v0"], out["v1"], out["v2"] = v[:, 0], v[:, 1], v[:, 2]
+    return out
+
+
+def check_cross_tris(tris, device=None):
+    """Context.cross's input check: ("torch", tris) for an (N, 12) float32 contiguous CUDA tensor (on `device` when
+    given), ("numpy", TRI_DTYPE array) for a C-contiguous TRI_DTYPE array or (N, 12) float32 array (make_tris packs
+    either from vertices); ValueError for anything else.  Calls nothing in the library."""
+    if _is_tensor(tris):
+        import torch
+        if tris.dtype != torch.float32 or tris.dim() != 2 or tris.shape[1] != 12:
+            raise ValueError(f"cross: tris must be an (N, 12) float32 tensor (make_tris), got "
+                             f"{tuple(tris.shape)} {tris.dtype}")
+        if not tris.is_cuda:
+            raise ValueError("cross: a torch tensor of triangles must be on the context's GPU (numpy arrays take the "
+                             "host path)")
+        if device is not None and tris.device.index != device:
+            raise ValueError(f"cross: tris on {tris.device}, the context on device {device}")
+        if not tris.is_contiguous():
+            raise ValueError("cross: tris must be contiguous")
+        return "torch", tris
+    if not isinstance(tris, np.ndarray):
+        raise ValueError("cross: tris must be a torch CUDA tensor or a numpy array")
+    if tris.dtype == _L.TRI_DTYPE:
+        if tris.ndim != 1:
+            raise ValueError(f"cross: a TRI_DTYPE array must be one-dimensional, got shape {tris.shape}")
+    elif tris.dtype != np.float32 or tris.ndim != 2 or tris.shape[1] != 12:
+        raise ValueError(f"cross: tris must be TRI_DTYPE or (N, 12) float32 (make_tris), got {tris.shape} {tris.dtype}")
+    if not tris.flags["C_CONTIGUOUS"]:
+        raise ValueError("cross: tris must be C-contiguous")
+    return "numpy", tris.view(_L.TRI_DTYPE).reshape(-1)
+
+
 def check_vertex_array(a, what="positions", device=None):
     """Context.update_vertices' input check: (kind, array, stride in floats) for an (n, 3) float32 torch CUDA
     tensor ("torch"; on `device` when given) or numpy array ("numpy") whose last dimension is contiguous and
@@ -922,6 +972,139 @@ class Context:
         out = np.zeros(4, np.uint64)
         self._check(_L.lib().rtbvh_collide_counts(self._h, _L.ptr(out)))
         return dict(zip(("triangles", "entries", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
+    # -- triangle queries --
+    def cross(self, tris, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
+        """rtbvh_cross_async / rtbvh_cross_host: for each query triangle every scene triangle whose leaf box meets the
+        query's box (closed intervals) and that crosses it (the header's six segment-triangle tests), as
+        (offsets, ids) in CSR form: query k's triangle ids are ids[offsets[k]:offsets[k + 1]], in the last build's sort
+        order (read_sorted), and offsets[n] is the total.
+
+        `tris`: make_tris' output.  A numpy input goes through the synchronous host entry and returns a uint64
+        (n + 1,) array and a uint32 array of offsets[n] ids (of min(offsets[n], capacity) when `capacity` is given).
+        A torch CUDA (N, 12) tensor goes to the device entry, enqueued on `stream` as nearest's, and returns an int64
+        (n + 1,) device tensor and an int32 (capacity,) device tensor whose entries [0, min(total, capacity)) are
+        written.  With `capacity` given that is one call, with no host copy and no synchronisation -- compare
+        offsets[-1] with it afterwards; with capacity=None a CROSS_SIZES call, one .item() read of the total (the
+        only synchronisation) and a CROSS_FILL call.  sizes_only=True returns the offsets alone.  mode: CROSS_SORT,
+        CROSS_COUNT (CROSS_SIZES and CROSS_FILL are this method's to set).  ValueError for a wrong shape, dtype,
+        device or layout."""
+        kind, tr = check_cross_tris(tris, getattr(self, "device", None))
+        if mode & (_L.CROSS_SIZES | _L.CROSS_FILL):
+            raise ValueError("cross: CROSS_SIZES and CROSS_FILL are set by cross itself")
+        if mode & ~(_L.CROSS_SORT | _L.CROSS_COUNT):
+            raise ValueError(f"cross: unknown mode bits {mode:#x}")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"cross: capacity must be a non-negative integer, got {capacity!r}")
+        if sizes_only and capacity is not None:
+            raise ValueError("cross: sizes_only takes no capacity")
+        n = len(tr)
+        L = _L.lib()
+        if kind == "numpy":
+            if stream is not None:
+                raise ValueError("cross: a stream goes with a torch tensor of triangles")
+            offsets = np.zeros(n + 1, np.uint64)
+            p, o = ctypes.c_void_p(tr.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                ids = np.zeros(int(capacity), np.uint32)
+                self._check(L.rtbvh_cross_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
+                return offsets, ids[:min(int(offsets[n]), len(ids))]
+            self._check(L.rtbvh_cross_host(self._h, p, n, o, None, 0, mode | _L.CROSS_SIZES))
+            if sizes_only:
+                return offsets
+            ids = np.zeros(int(offsets[n]), np.uint32)
+            self._check(L.rtbvh_cross_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
+                                           mode | _L.CROSS_FILL))
+            return offsets, ids
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=tr.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(tr.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(tr.device).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        p, o = ctypes.c_void_p(tr.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
+
+        def call(ids, m):
+            self._check(L.rtbvh_cross_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
+                                            and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            ids = torch.empty(int(capacity), dtype=torch.int32, device=tr.device)
+            call(ids, mode)
+            return offsets, ids
+        call(None, mode | _L.CROSS_SIZES)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=tr.device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        ids = torch.empty(total, dtype=torch.int32, device=tr.device)
+        call(ids, mode | _L.CROSS_FILL)
+        return offsets, ids
+
+    def cross_first(self, tris, mode: int = 0, out=None, stream=None):
+        """rtbvh_cross_first_async / rtbvh_cross_first_host: for each query triangle the first id of its cross() list
+        -- the member at the lowest position of the build's sort order -- or 0xFFFFFFFF (-1 in a tensor) when it
+        crosses nothing; one pass whose walks end at their first member.  `tris` as cross takes them: a numpy input
+        returns a uint32 (N,) array through the synchronous host entry, a torch CUDA tensor an int32 (N,) device
+        tensor, enqueued on `stream` as nearest's with no synchronisation.  `out` receives the results when given.
+        mode: CROSS_SORT, CROSS_COUNT."""
+        kind, tr = check_cross_tris(tris, getattr(self, "device", None))
+        if mode & ~(_L.CROSS_SORT | _L.CROSS_COUNT):
+            raise ValueError(f"cross_first: mode takes CROSS_SORT and CROSS_COUNT only, got {mode:#x}")
+        n = len(tr)
+        if kind == "numpy":
+            if stream is not None:
+                raise ValueError("cross_first: a stream goes with a torch tensor of triangles")
+            if out is None:
+                out = np.zeros(n, np.uint32)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.shape == (n,) and
+                      out.flags["C_CONTIGUOUS"]):
+                raise ValueError(f"cross_first: out must be a contiguous uint32 array of {n} ids")
+            self._check(_L.lib().rtbvh_cross_first_host(self._h, ctypes.c_void_p(tr.ctypes.data), n,
+                                                        ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=tr.device)
+        elif not (_is_tensor(out) and out.dtype == torch.int32 and tuple(out.shape) == (n,) and
+                  out.device == tr.device and out.is_contiguous()):
+            raise ValueError(f"cross_first: out must be a contiguous ({n},) int32 tensor on {tr.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(tr.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(tr.device).synchronize()
+        self._check(_L.lib().rtbvh_cross_first_async(self._h, ctypes.c_void_p(tr.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), mode,
+                                                     ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def cross_pairs(self, tris) -> np.ndarray:
+        """The members as a (P, 2) uint32 array of rows (query, triangle id), expanded from cross()'s CSR form: query
+        by query, each list in the build's sort order (a CUDA tensor of triangles is read back)."""
+        offsets, ids = self.cross(tris)
+        if _is_tensor(offsets):
+            offsets, ids = offsets.cpu().numpy().astype(np.uint64), ids.cpu().numpy().view(np.uint32)
+        owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.uint32), np.diff(offsets).astype(np.int64))
+        return np.stack([owner, ids], 1)
+
+    def cross_counts(self) -> dict:
+        """rtbvh_cross_counts: queries, ids (the total; for cross_first the queries with a member), internal-node and
+        leaf steps (summed over the passes) of the last CROSS_COUNT query (the other queries' counts are kept
+        apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_cross_counts(self._h, _L.ptr(out)))
+        return dict(zip(("queries", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
     # -- signed-distance queries --
     def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
