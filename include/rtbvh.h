@@ -455,6 +455,34 @@ rtbvh_status rtbvh_query_counts(rtbvh_ctx* ctx, uint64_t out[4]);
  * re-traces' visits; rays and hits stay exact.  RTBVH_ERR_NOT_READY before any counting query. */
 rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
+/* ---- Degenerate and non-finite scene triangles ---------------------------------------------------
+ * Every build, refit, trace and query kind takes any scene.  A triangle is what its leaf record holds, and each
+ * kind's answer stays the brute force of the kind's own formulas over those records, bit for bit, whatever the tree
+ * (tests/test_hostile_gpu.py: points, needles, collinear and repeated-index triangles, duplicates, one-ulp slivers,
+ * denormal and 1e25 coordinates, NaN and infinite vertices, mixed into a mesh).  What the formulas give:
+ *  - Boxes.  A leaf box is fminf / fmaxf over the three vertices, which drop a NaN: a box is NaN on an axis only
+ *    when all three vertices are, and a node's box is NaN iff every leaf below it is.  An infinite coordinate makes
+ *    the boxes up to the root infinite.  (The WVP product spreads a non-finite component over its vertex: x * 0 is
+ *    NaN.)  A refit back to finite positions leaves no NaN or infinity behind.
+ *  - Rays (trace, query, allhits, khits, the signed rays).  A triangle without area (|det| < EPSILON: a point, a
+ *    needle, a collinear or repeated-index triangle, a sliver, a denormal one) is never hit.  Nor is one with a NaN
+ *    or infinite vertex, or whose products overflow: its t is a NaN or 0, and EPSILON < t is false.
+ *  - Points (nearest, within, knn, the signed distance).  A triangle without area answers through `u, v: NaN -> 0`
+ *    and the clamp: a point of its leaf box.  A non-finite vertex makes q a NaN, which the clamp fminf(hi, q) turns
+ *    into hi: the triangle stands at the max corner of its leaf box, and can be an answer; all three vertices NaN:
+ *    dist2 is a NaN, never an answer.  dist2 = +inf (a point or a triangle 1e19 away) satisfies
+ *    dist2 <= max_dist2 = +inf: such a triangle is listed by within, returned by nearest when nothing is nearer,
+ *    and stands in knn's list before the "none" slots.
+ *  - Boxes and triangles (overlap, cross, collide).  (B) compares the leaf box: a NaN fails it, an infinity meets.
+ *    In RTBVH_OVERLAP_TRIANGLE a NaN separates nothing, so a non-finite triangle whose box meets the query box is
+ *    listed, and a needle is decided by its edge axes.  In collide a triangle with one non-finite vertex keeps a
+ *    finite edge, which can cross others: it is listed, while the same triangle as a cross QUERY is not walked.
+ *  - The certified walks.  A subtree that holds a non-finite triangle carries E = inf and tcap = -1 and is never
+ *    pruned by distance; a node whose boxes are non-finite or beyond 2^100 has no QNode frame, and a ray that
+ *    reaches it is re-traced in the reference order.  With an infinite root box that is every covered ray:
+ *    rtbvh_query_walk_counts reports certified = 0, and a certified trace re-traces every bounce ray (redo_rays[1];
+ *    the binned primary pass is not affected).  The answers are the same. */
+
 /* ---- closest-point queries: the nearest triangle to points the caller chose ---------------------
  * (No reference equivalent.)  For each point: which triangle is nearest, where on it, and how far away.
  *

@@ -36,7 +36,8 @@ class _Scene(ctypes.Structure):
 _lib = None
 
 
-def build() -> str:
+def build_lib() -> str:
+    """Makes liboracle.so (lib() calls it when the library is missing)."""
     subprocess.run(["make", "-s", "-C", HERE, "liboracle.so"], check=True)
     return LIB_PATH
 
@@ -45,7 +46,7 @@ def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
-            build()
+            build_lib()
         L = ctypes.CDLL(LIB_PATH)
         u32p = ctypes.c_void_p
         L.orc_expand_bits.restype = ctypes.c_uint32

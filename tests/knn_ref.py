@@ -31,8 +31,12 @@ def select_k(d, finite, k, max_dist2=np.inf):
     with np.errstate(all="ignore"):
         bound = np.broadcast_to(np.asarray(max_dist2, np.float32), (n,)) + np.float32(0)
         ok = (d <= bound[:, None]) & ((bound >= 0) & finite)[:, None]      # (a NaN dist2 is never a member)
-    order = np.argsort(np.where(ok, d, np.float32(np.inf)), axis=1, kind="stable")[:, :k]
     rows = np.arange(n)[:, None]
+    order = np.argsort(np.where(ok, d, np.float32(np.inf)), axis=1, kind="stable")
+    # (a member at dist2 = +inf, under max_dist2 = +inf, goes before every non-member, whatever their ids)
+    if (ok & np.isinf(d)).any():
+        order = order[rows, np.argsort(~ok[rows, order], axis=1, kind="stable")]
+    order = order[:, :k]
     found = ok[rows, order]
     assert (found[:, :-1] >= found[:, 1:]).all()   # the members come first (no member at +inf behind a non-member)
     tri = np.full((n, k), NONE, np.uint32)
