@@ -349,8 +349,8 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
  * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_*, rtbvh_khits_* and
  * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, as do rtbvh_collide_async, rtbvh_collide_host, rtbvh_cross_async,
- * rtbvh_cross_host, rtbvh_cross_first_async and rtbvh_cross_first_host, and the
- * rtbvh_read_* calls return the last build's tree.
+ * rtbvh_cross_host, rtbvh_cross_first_async, rtbvh_cross_first_host, rtbvh_clearance_async and
+ * rtbvh_clearance_host, and the rtbvh_read_* calls return the last build's tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -473,6 +473,11 @@ rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* ctx, uint64_t out[4]);
  *    dist2 is a NaN, never an answer.  dist2 = +inf (a point or a triangle 1e19 away) satisfies
  *    dist2 <= max_dist2 = +inf: such a triangle is listed by within, returned by nearest when nothing is nearer,
  *    and stands in knn's list before the "none" slots.
+ *  - Triangles by distance (clearance).  The same through both clamps: every candidate point is clamped into its own
+ *    triangle's box, so a scene triangle with a non-finite vertex stands at a corner of its leaf box and can be an
+ *    answer; all three vertices NaN: every candidate's d is a NaN, dist2 is a NaN, never an answer.  dist2 = +inf
+ *    satisfies max_dist2 = +inf.  A point or a needle is a valid query, and a valid scene triangle: a zero-length
+ *    segment has A or E = 0, its quotients are NaN or infinite, and clamp01 and the box clamps make points of them.
  *  - Boxes and triangles (overlap, cross, collide).  (B) compares the leaf box: a NaN fails it, an infinity meets.
  *    In RTBVH_OVERLAP_TRIANGLE a NaN separates nothing, so a non-finite triangle whose box meets the query box is
  *    listed, and a needle is decided by its edge axes.  In collide a triangle with one non-finite vertex keeps a
@@ -930,6 +935,77 @@ rtbvh_status rtbvh_cross_first_host(rtbvh_ctx* ctx, const rtbvh_tri* tris, uint6
  * ran.  Its own words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting triangle
  * query. */
 rtbvh_status rtbvh_cross_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- clearance queries: the nearest scene triangle to a caller's triangle --------
+ * (No reference equivalent; the distance query of FCL or PQP for a second mesh against the built one.)  For each
+ * query triangle: which scene triangle is nearest, how far, and between which two points.  Specified operation for
+ * operation, in fp32 without contraction, dots as (x*x' + y*y') + z*z', independently of the tree and of the walk: the
+ * answer is the brute force over all scene triangles, byte for byte.
+ * Inputs.  A query triangle q is an rtbvh_tri, reduced as in the triangle queries above to (qa, qe1, qe2, [qlo, qhi]);
+ * a scene triangle x is its leaf record (a, e1, e2, [lo, hi]).  The vertices of a record are V0 = a, V1 = fl(a + e1),
+ * V2 = fl(a + e2); its segments S0, S1, S2 are the self-collision section's.  One bound max_dist2 serves the call.
+ * dist2(q, x) comes from fifteen candidate point pairs (cq, cx), in this order:
+ *   0..2   cq = Vi(q);  cx = the closest-point section's q of triangle x for the point Vi(q): that section's formulas
+ *          unchanged, its clamp into [lo, hi] included.
+ *   3..5   cx = Vj(x);  cq = the same formulas of triangle q and its box [qlo, qhi] for the point Vj(x).
+ *   6..14  the segment pairs (Si(q), Sj(x)), i major, (P1, D1) = Si(q), (P2, D2) = Sj(x); a division is the IEEE
+ *          quotient and clamp01(x) = fminf(fmaxf(x, 0), 1), which makes 0 of a NaN:
+ *              r = P1 - P2;  A = dot(D1,D1);  E = dot(D2,D2);  F = dot(D2,r);  C = dot(D1,r);  B = dot(D1,D2)
+ *              den = A*E - B*B
+ *              s = den > 0 ? clamp01((B*F - C*E) / den) : 0
+ *              t = (B*s + F) / E
+ *              if t < 0: s = clamp01(-C / A)   else if t > 1: s = clamp01((B - C) / A)
+ *              t = clamp01(t)
+ *              cq = P1 + D1*s;  cx = P2 + D2*t
+ * Every candidate then gets, per component, cq = fmaxf(qlo, fminf(qhi, cq)) and cx = fmaxf(lo, fminf(hi, cx)), then
+ * e = cq - cx and d = dot(e, e).  The pair's dist2 and its witness points (point_q, point_x) are those of the FIRST
+ * candidate with the smallest d: a later one replaces an earlier one only if its d is strictly smaller, and a NaN d
+ * never wins (all fifteen NaN: dist2 is a NaN).
+ *  (X) If the triangle queries' (B) and (X) both hold for (q, x) -- x would be in q's rtbvh_cross list -- dist2 = +0.
+ *      The witness points stay the winning candidate's: they are then the NEAREST FEATURE PAIR of two crossing
+ *      triangles, not a contact point, and their own distance is not 0.
+ * The result of q is the lexicographic minimum of (dist2, triangle id) over the triangles with dist2 <= max_dist2.
+ * There is no result, and no walk, when !(max_dist2 >= 0) (a NaN included; -0 counts as +0) or when a vertex of q has
+ * a non-finite component; nor is there one when no triangle is within the bound.
+ * Every candidate is a pair of points of the two triangles, up to rounding, so dist2 never undershoots the true
+ * distance by more than rounding; in exact arithmetic the minimum of the fifteen IS the distance of two triangles that
+ * do not cross (it is attained at a vertex of one or between two edges).  Limits: those of (X) -- coplanar crossing
+ * pairs are not seen by it and get their feature distance, which is then 0 up to rounding.
+ * Pruning.  Let bb(q, box) = (dx*dx + dy*dy) + dz*dz with dk = fmaxf(fmaxf(lo_k - qhi_k, qlo_k - hi_k), 0).  Then
+ * dist2(q, x) >= bb(q, any box that contains x's leaf box): the two clamps give cq_k >= qlo_k and cx_k <= hi_k, and
+ * rounding is monotone, so fl(cq_k - cx_k) >= fl(qlo_k - hi_k), and the other sign likewise; squares and the
+ * fixed-association sum of non-negative terms are monotone; under (B) every dk is 0, which covers (X).  So a walk
+ * that enters a box iff bb <= the best dist2 so far (non-strict: ties are visited for the id tie-break) reaches every
+ * triangle that can win, whatever order it visits in. */
+typedef struct {
+    float point_q[3]; /* on the query triangle, in its box */
+    float dist2;
+    float point_x[3]; /* on the scene triangle, in its leaf box */
+    uint32_t tri;     /* triangle id (Node.index / 3) */
+} rtbvh_clearance; /* 32 B.  No result: dist2 = -1, both points 0, tri = 0xFFFFFFFF */
+enum {
+    RTBVH_CLEARANCE_SORT = 1u << 1, /* walk the queries in the Morton order of their box centres (RTBVH_CROSS_SORT's
+                                       keys): the same results, each at its query's own index */
+    RTBVH_CLEARANCE_COUNT = 1u << 2 /* count queries, results and steps for rtbvh_clearance_counts (slower) */
+    /* every other bit: RTBVH_ERR_INVALID_ARG */
+};
+/* n triangles at dev_tris and n results at dev_out (device memory of the context's device, 16-B aligned), enqueued on
+ * `stream` (hipStream_t, NULL = the context stream).  Everything else follows rtbvh_cross_first_async and
+ * rtbvh_nearest_async one for one: it reads the node records, or the topology plus node boxes, never the quantized
+ * nodes; the call waits for the last build and only enqueues; the library orders it among all other queries, which
+ * share the query scratch, and the next build waits for it.  n == 0 returns RTBVH_OK and touches nothing;
+ * RTBVH_ERR_NOT_READY before a build and after a vertex update until the next build or refit;
+ * RTBVH_ERR_INVALID_ARG for NULL pointers with n > 0, unknown mode bits and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit ends with the best found so far -- a genuine (dist2, triangle) pair, not
+ * necessarily the nearest -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_clearance_async(rtbvh_ctx* ctx, const rtbvh_tri* dev_tris, uint64_t n, float max_dist2,
+                                   rtbvh_clearance* dev_out, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_clearance_host(rtbvh_ctx* ctx, const rtbvh_tri* tris, uint64_t n, float max_dist2,
+                                  rtbvh_clearance* out, uint32_t mode);
+/* The last RTBVH_CLEARANCE_COUNT query (waits for it): queries, results found, internal-node steps, leaf steps.  Its
+ * own words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting clearance query. */
+rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
  * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The

@@ -14,6 +14,7 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    KHITS_COUNT, KHITS_MAX_K, KHITS_SORT,
                    COLLIDE_COUNT, COLLIDE_FILL, COLLIDE_SIZES, COLLIDE_SYMMETRIC, COLLIDE_TRIANGLE,
                    CROSS_COUNT, CROSS_FILL, CROSS_SIZES, CROSS_SORT, TRI_DTYPE,
+                   CLEARANCE_COUNT, CLEARANCE_DTYPE, CLEARANCE_SORT,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, check_cross_tris, check_nearest_points, check_overlap_boxes, check_query_rays,
@@ -40,4 +41,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "KHITS_SORT", "KHITS_COUNT", "KHITS_MAX_K",
            "COLLIDE_COUNT", "COLLIDE_TRIANGLE", "COLLIDE_SIZES", "COLLIDE_FILL", "COLLIDE_SYMMETRIC",
            "TRI_DTYPE", "CROSS_SORT", "CROSS_COUNT", "CROSS_SIZES", "CROSS_FILL", "make_tris", "check_cross_tris",
+           "CLEARANCE_DTYPE", "CLEARANCE_SORT", "CLEARANCE_COUNT",
            "check_query_rays", "check_vertex_array"]

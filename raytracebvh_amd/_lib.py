@@ -55,6 +55,7 @@ EXPORTS = [
     "rtbvh_khits_async", "rtbvh_khits_host", "rtbvh_khits_counts",
     "rtbvh_collide_async", "rtbvh_collide_host", "rtbvh_collide_counts",
     "rtbvh_cross_async", "rtbvh_cross_host", "rtbvh_cross_first_async", "rtbvh_cross_first_host", "rtbvh_cross_counts",
+    "rtbvh_clearance_async", "rtbvh_clearance_host", "rtbvh_clearance_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -103,6 +104,10 @@ TRI_DTYPE = np.dtype([("v0", "<f4", (3,)), ("reserved0", "<u4"), ("v1", "<f4", (
                       ("v2", "<f4", (3,)), ("reserved2", "<u4")])
 assert TRI_DTYPE.itemsize == 48
 CROSS_SORT, CROSS_COUNT, CROSS_SIZES, CROSS_FILL = 2, 4, 16, 32   # RTBVH_CROSS_*; its lists hold triangle ids (uint32)
+# rtbvh_clearance: the nearest scene triangle to a query triangle and the two witness points
+CLEARANCE_DTYPE = np.dtype([("point_q", "<f4", (3,)), ("dist2", "<f4"), ("point_x", "<f4", (3,)), ("tri", "<u4")])
+assert CLEARANCE_DTYPE.itemsize == 32
+CLEARANCE_SORT, CLEARANCE_COUNT = 2, 4   # RTBVH_CLEARANCE_*
 
 
 class Config(ctypes.Structure):
@@ -289,6 +294,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_cross_first_async": (i32, [vp, vp, u64, vp, u32, vp]),
         "rtbvh_cross_first_host": (i32, [vp, vp, u64, vp, u32]),
         "rtbvh_cross_counts": (i32, [vp, vp]),
+        "rtbvh_clearance_async": (i32, [vp, vp, u64, ctypes.c_float, vp, u32, vp]),
+        "rtbvh_clearance_host": (i32, [vp, vp, u64, ctypes.c_float, vp, u32]),
+        "rtbvh_clearance_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

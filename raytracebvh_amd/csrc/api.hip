@@ -328,6 +328,7 @@ struct rtbvh_ctx {
     bool khits_counted = false;              // the first-k queries' count block holds a RTBVH_KHITS_COUNT query's counts
     bool collide_counted = false;            // the self-collision queries' count block holds a RTBVH_COLLIDE_COUNT query's counts
     bool cross_counted = false;              // the triangle queries' count block holds a RTBVH_CROSS_COUNT query's counts
+    bool clearance_counted = false;          // the clearance queries' count block holds a RTBVH_CLEARANCE_COUNT query's counts
 };
 
 namespace {
@@ -3183,6 +3184,82 @@ rtbvh_status rtbvh_cross_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CROSS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- clearance queries ---------------------------------------------------------------------------------
+// rtbvh_cross_first_async's rules, one for one, and its place in the ev_query chain: cross_args' waits, tree forms,
+// [keys + sort] and stack limit, then one launch.  The count block is its own (QUERY_CLEARANCE_AT); cross_args zeroes
+// the triangle queries' block for a counting call, so the counting is set up here.
+rtbvh_status rtbvh_clearance_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, float max_dist2,
+                                   rtbvh_clearance* dev_out, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (mode & ~(uint32_t)(RTBVH_CLEARANCE_SORT | RTBVH_CLEARANCE_COUNT))
+        return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: 2^31 triangles or more");
+    if (n == 0) return RTBVH_OK;
+    if (!dev_tris || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: NULL triangles or results");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "clearance before build");
+    if (c->stale) return fail_stale(c, "clearance");
+    static_assert(sizeof(rtbvh_clearance) == 32, "clearance record layout");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool sort = (mode & RTBVH_CLEARANCE_SORT) != 0, count = (mode & RTBVH_CLEARANCE_COUNT) != 0;
+    CrossArgs x{};
+    TRY(cross_args(c, dev_tris, (uint32_t)n, sort, false, false, s, x));
+    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_CLEARANCE_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    ClearanceArgs a{};
+    a.inner = x.inner;
+    a.topo = x.topo;
+    a.nbox = x.nbox;
+    a.nb = x.nb;
+    a.leaf = x.leaf;
+    a.T = x.T;
+    a.tris = x.tris;
+    a.max_dist2 = max_dist2;
+    a.out = reinterpret_cast<float4*>(dev_out);
+    a.n = x.n;
+    a.perm = x.perm;
+    a.next = x.next;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_CLEARANCE_AT);
+    a.overflow = x.overflow;
+    a.stack_limit = x.stack_limit;
+    launch_clearance(a, count, s);
+    rtbvh_status st = check_launch(c, "clearance kernel");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->clearance_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_clearance_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, float max_dist2, rtbvh_clearance* out,
+                                  uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    if (n == 0 || n >= (1ull << 31) || !tris || !out || !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_clearance_async(c, tris, n, max_dist2, out, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // triangles, then the results: both 16-B aligned
+    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_tri) + sizeof(rtbvh_clearance))));
+    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d.h);
+    rtbvh_clearance* dr = reinterpret_cast<rtbvh_clearance*>(d + (size_t)n * sizeof(rtbvh_tri));
+    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "clearance_host: upload failed");
+    TRY(rtbvh_clearance_async(c, dt, n, max_dist2, dr, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "clearance_host: sync");
+    if (hipMemcpy(out, dr, (size_t)n * sizeof(rtbvh_clearance), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "clearance_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->clearance_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_CLEARANCE_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CLEARANCE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

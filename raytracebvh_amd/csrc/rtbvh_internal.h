@@ -610,11 +610,36 @@ struct CrossArgs {
 };
 // the triangle queries' own count block, behind the self-collision queries'
 constexpr uint32_t QUERY_CROSS_AT = QUERY_COLLIDE_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_CROSS_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_CROSS_AT % 2 == 0, "the count block's 8-byte words");
 void launch_cross(const CrossArgs& a, CrossPass pass, bool count, hipStream_t s);
 // RTBVH_CROSS_SORT's keys (the 30-bit Morton codes, in the root box, of the query boxes' centres) and vals[i] = i
 void launch_cross_keys(const float4* tris, uint32_t n, const float* box, uint32_t* keys, uint32_t* vals,
                        hipStream_t s);
+
+// ---- clearance queries (trace.hip k_clearance; rtbvh_clearance_async) -------
+// CrossArgs' query triangles on the same tree forms, one bound for the call, and one rtbvh_clearance (two float4:
+// {point_q, dist2}, {point_x, tri}) stored per query at its own index.
+struct ClearanceArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* tris;       // [3n]
+    float max_dist2;
+    float4* out;              // [2n]
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_CLEARANCE_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_CLEARANCE_COUNT: [4] queries, found, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the clearance queries' own count block, behind the triangle queries'
+constexpr uint32_t QUERY_CLEARANCE_AT = QUERY_CROSS_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_CLEARANCE_AT + 2 * QUERY_COUNT_WORDS;
+static_assert(QUERY_CLEARANCE_AT % 2 == 0, "the count block's 8-byte words");
+void launch_clearance(const ClearanceArgs& a, bool count, hipStream_t s);
 
 }  // namespace rtbvh

@@ -4192,7 +4192,241 @@ __global__ __launch_bounds__(BLOCK) void k_cross_keys(const float4* __restrict__
     vals[i] = i;
 }
 
+// ---- clearance queries (rtbvh_clearance_async): the nearest scene triangle to a caller's triangle ----------------
+// For each query triangle the lexicographic minimum of (dist2, triangle id) over the scene triangles with dist2 <=
+// max_dist2.  include/rtbvh.h has the formulas: the first smallest of fifteen candidate point pairs -- each vertex
+// of one triangle against the other triangle through triangle_dist2, unchanged, and the nine segment pairs -- every
+// point clamped into its own triangle's box, and +0 where k_cross's (B) and (X) hold.  DESIGN.md 5n has why the walk
+// returns the brute-force answer bit for bit: with both points clamped, a pair's dist2 is never below the box-box
+// distance of the query's box and any box that contains the leaf box, so a walk that enters a box iff that distance
+// is <= the bound (non-strict: ties are visited for the id tie-break) reaches every triangle that can win.
+// k_nearest's frame -- the claims, the stack, one 64-B fetch a step before the leaf / node branch, the guard and the
+// run-time stack limit, the u64 best key, the winner's points recomputed at the end from its leaf record -- with
+// k_cross's query load.  Plain fp32 as specified: no fma, no fast intrinsics, every division the IEEE quotient.
+// The fifteen candidates run as one loop that is not unrolled, so one candidate's intermediates are live at a time;
+// CLEARANCE_WAVES is chosen from the instances' register counts.
+#ifndef RTBVH_CLEARANCE_WAVES   // (an A/B build sets another launch bound: EXTRA=-DRTBVH_CLEARANCE_WAVES=<n>)
+#define RTBVH_CLEARANCE_WAVES 5
+#endif
+constexpr uint32_t CLEARANCE_WAVES = RTBVH_CLEARANCE_WAVES;
+__device__ __forceinline__ f3 sel(bool s, f3 x, f3 y) { return mk(s ? x.x : y.x, s ? x.y : y.y, s ? x.z : y.z); }
+__device__ __forceinline__ f3 clamp_box(f3 lo, f3 hi, f3 p) {
+    return mk(fmaxf(lo.x, fminf(hi.x, p.x)), fmaxf(lo.y, fminf(hi.y, p.y)), fmaxf(lo.z, fminf(hi.z, p.z)));
+}
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }   // a NaN becomes 0
+__device__ __forceinline__ float box_box_dist2(f3 qlo, f3 qhi, f3 lo, f3 hi) {
+    const float dx = fmaxf(fmaxf(lo.x - qhi.x, qlo.x - hi.x), 0.f);
+    const float dy = fmaxf(fmaxf(lo.y - qhi.y, qlo.y - hi.y), 0.f);
+    const float dz = fmaxf(fmaxf(lo.z - qhi.z, qlo.z - hi.z), 0.f);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// the closest points of the segments (P1, D1) and (P2, D2), before the box clamps
+__device__ __forceinline__ void segment_pair(f3 P1, f3 D1, f3 P2, f3 D2, f3& c1, f3& c2) {
+    const f3 r = sub(P1, P2);
+    const float A = dot(D1, D1), E = dot(D2, D2), F = dot(D2, r), C = dot(D1, r), B = dot(D1, D2);
+    const float den = A * E - B * B;
+    float s = den > 0.f ? clamp01((B * F - C * E) / den) : 0.f;
+    float t = (B * s + F) / E;
+    if (t < 0.f) s = clamp01(-C / A);
+    else if (t > 1.f) s = clamp01((B - C) / A);
+    t = clamp01(t);
+    c1 = add(P1, mul(D1, s));
+    c2 = add(P2, mul(D2, t));
+}
+// candidate k of the header's fifteen for the query (qa, qe1, qe2, [qlo, qhi]) and the scene triangle
+// (a, e1, e2, [lo, hi]): its two points, clamped, and their squared distance.  k is the same in every lane.
+__device__ __forceinline__ float clearance_candidate(int k, f3 qa, f3 qe1, f3 qe2, f3 qlo, f3 qhi, f3 a, f3 e1, f3 e2,
+                                                     f3 lo, f3 hi, f3& cq, f3& cx) {
+    if (k < 6) {   // a vertex of one triangle (o) against the other (t): 0..2 the query's vertices, 3..5 the scene's
+        const bool s = k >= 3;
+        const int i = s ? k - 3 : k;
+        const f3 oa = sel(s, a, qa), oe = sel(s, i == 1 ? e1 : e2, i == 1 ? qe1 : qe2);
+        const f3 V = i == 0 ? oa : add(oa, oe);
+        float u, v;
+        f3 c;
+        triangle_dist2(V, sel(s, qa, a), sel(s, qe1, e1), sel(s, qe2, e2), sel(s, qlo, lo), sel(s, qhi, hi), u, v, c);
+        cq = sel(s, c, V);
+        cx = sel(s, V, c);
+    } else {       // segment i of the query against segment j of the scene triangle, i major
+        const int i = (k - 6) / 3, j = (k - 6) - 3 * i;
+        const f3 P1 = i == 2 ? add(qa, qe1) : qa, D1 = i == 0 ? qe1 : i == 1 ? qe2 : sub(qe2, qe1);
+        const f3 P2 = j == 2 ? add(a, e1) : a, D2 = j == 0 ? e1 : j == 1 ? e2 : sub(e2, e1);
+        segment_pair(P1, D1, P2, D2, cq, cx);
+    }
+    cq = clamp_box(qlo, qhi, cq);
+    cx = clamp_box(lo, hi, cx);
+    const f3 e = sub(cq, cx);
+    return dot(e, e);
+}
+// the pair's distance without the override: the first candidate with the smallest d (a NaN never wins), its points
+__device__ __forceinline__ float clearance_pair(f3 qa, f3 qe1, f3 qe2, f3 qlo, f3 qhi, f3 a, f3 e1, f3 e2, f3 lo, f3 hi,
+                                                f3& bq, f3& bx) {
+    float best = __uint_as_float(0x7FC00000u);
+#pragma unroll 1
+    for (int k = 0; k < 15; k++) {
+        f3 cq, cx;
+        const float d = clearance_candidate(k, qa, qe1, qe2, qlo, qhi, a, e1, e2, lo, hi, cq, cx);
+        if (d < best || best != best) {
+            best = d;
+            bq = cq;
+            bx = cx;
+        }
+    }
+    return best;
+}
+template <bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, CLEARANCE_WAVES) void k_clearance(ClearanceArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nqueries = 0, nfound = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (bl: the best triangle's sorted leaf index; hit, best unused)
+    uint64_t key = 0;
+    f3 qlo = mk(0.f, 0.f, 0.f), qhi = mk(0.f, 0.f, 0.f);
+    f3 qa = mk(0.f, 0.f, 0.f), qe1 = mk(0.f, 0.f, 0.f), qe2 = mk(0.f, 0.f, 0.f);
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    const float4 none0 = make_float4(0.f, 0.f, 0.f, -1.f), none1 = make_float4(0.f, 0.f, 0.f, __uint_as_float(INVALID));
+    const float bound0 = a.max_dist2 + 0.f;   // (-0 -> +0: the key's bits order as the floats)
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th triangle of the walk order
+            r = a.perm ? a.perm[k] : k;
+            const float4 t0 = a.tris[3 * (size_t)r], t1 = a.tris[3 * (size_t)r + 1], t2 = a.tris[3 * (size_t)r + 2];
+            const f3 v0 = mk(t0.x, t0.y, t0.z), v1 = mk(t1.x, t1.y, t1.z), v2 = mk(t2.x, t2.y, t2.z);
+            if (COUNT) nqueries++;
+            const bool finite = fabsf(v0.x) < INFINITY && fabsf(v0.y) < INFINITY && fabsf(v0.z) < INFINITY &&
+                                fabsf(v1.x) < INFINITY && fabsf(v1.y) < INFINITY && fabsf(v1.z) < INFINITY &&
+                                fabsf(v2.x) < INFINITY && fabsf(v2.y) < INFINITY && fabsf(v2.z) < INFINITY;
+            if (!(bound0 >= 0.f) || !finite) {   // no walk: no result
+                a.out[2 * (size_t)r] = none0;
+                a.out[2 * (size_t)r + 1] = none1;
+            } else {
+                has = true;
+                qa = v0;
+                qe1 = sub(v1, v0);
+                qe2 = sub(v2, v0);
+                qlo = mk(fminf(fminf(v0.x, v1.x), v2.x), fminf(fminf(v0.y, v1.y), v2.y), fminf(fminf(v0.z, v1.z), v2.z));
+                qhi = mk(fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z));
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                key = (uint64_t)__float_as_uint(bound0) << 32 | 0xFFFFFFFFull;
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const float bound = key_t(key);
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            // the leaf's own box first (words 10..15): a pair's dist2 is never below its box-box distance
+            const f3 lo = mk(q2.z, q2.w, q3.x), hi = mk(q3.y, q3.z, q3.w);
+            if (box_box_dist2(qlo, qhi, lo, hi) <= bound) {
+                const f3 p0 = mk(q0.x, q0.y, q0.z), f1 = mk(q0.w, q1.x, q1.y), f2 = mk(q1.z, q1.w, q2.x);
+                float d = 0.f;   // (B) and (X): the triangles cross
+                if (!(boxes_meet(qlo, qhi, lo, hi) &&
+                      (edges_cross(qa, qe1, qe2, p0, f1, f2) || edges_cross(p0, f1, f2, qa, qe1, qe2)))) {
+                    f3 bq, bx;
+                    d = clearance_pair(qa, qe1, qe2, qlo, qhi, p0, f1, f2, lo, hi, bq, bx);
+                }
+                const uint64_t cand = (uint64_t)__float_as_uint(d) << 32 | (__float_as_uint(q2.y) & ~LEAF_BIT);
+                if (cand < key) {
+                    key = cand;
+                    w.bl = w.node & ~LEAF_BIT;
+                }
+            }
+            walk_pop(w, st);
+            done = w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            const float bdl = box_box_dist2(qlo, qhi, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y));
+            const float bdr = box_box_dist2(qlo, qhi, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w));
+            const bool lh = bdl <= bound, rh = bdr <= bound;
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                const bool swap = lh && rh && bdr < bdl;   // the nearer child first
+                if (lh && rh) {
+                    st.store(w.sp, w.top);   // push the other
+                    w.sp++;
+                    w.top = swap ? cl : cr;
+                }
+                w.node = swap ? cr : (lh ? cl : cr);
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            float4 o0 = none0, o1 = none1;
+            if ((uint32_t)key != 0xFFFFFFFFu) {   // the winner's points, recomputed from its leaf record
+                const float4* lr = leaf + 4 * (size_t)w.bl;
+                const float4 la = lr[0], lb = lr[1], lc = lr[2], ld = lr[3];
+                f3 bq = mk(0.f, 0.f, 0.f), bx = mk(0.f, 0.f, 0.f);
+                clearance_pair(qa, qe1, qe2, qlo, qhi, mk(la.x, la.y, la.z), mk(la.w, lb.x, lb.y), mk(lb.z, lb.w, lc.x),
+                               mk(lc.z, lc.w, ld.x), mk(ld.y, ld.z, ld.w), bq, bx);
+                o0 = make_float4(bq.x, bq.y, bq.z, key_t(key));   // (dist2: +0 where the pair crosses)
+                o1 = make_float4(bx.x, bx.y, bx.z, __uint_as_float((uint32_t)key));
+            }
+            a.out[2 * (size_t)r] = o0;
+            a.out[2 * (size_t)r + 1] = o1;
+            has = false;
+            if (COUNT) nfound += (uint32_t)key != 0xFFFFFFFFu;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nqueries, nfound, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_clearance(const ClearanceArgs& a, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    // the persistent grid of the kernel's occupancy, or a workgroup per 256 triangles when that is fewer
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * CLEARANCE_WAVES ? need : 256 * CLEARANCE_WAVES;
+    with_bools([&](auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_clearance<COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, count, a.nb);
+}
 
 void launch_cross(const CrossArgs& a, CrossPass pass, bool count, hipStream_t s) {
     if (a.n == 0) return;

@@ -1106,6 +1106,57 @@ class Context:
         self._check(_L.lib().rtbvh_cross_counts(self._h, _L.ptr(out)))
         return dict(zip(("queries", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
 
+    # -- clearance queries --
+    def clearance(self, tris, max_dist2=float("inf"), mode: int = 0, stream=None):
+        """rtbvh_clearance_async / rtbvh_clearance_host: for each query triangle the nearest scene triangle within
+        max_dist2 (one bound for the call), the squared distance -- 0 where the two cross, as cross() decides it --
+        and the two witness points, in the space the BVH was built in.
+
+        A numpy input -- (N, 3, 3) or (N, 9) vertices, packed by make_tris, or what cross() takes -- goes through the
+        synchronous host entry and returns a CLEARANCE_DTYPE array (no result: dist2 = -1, tri = 0xFFFFFFFF).  A
+        torch CUDA (N, 12) tensor (make_tris) goes to the device entry, enqueued on `stream` as nearest's with no host
+        copy and no synchronisation, and returns an (N, 8) float32 device tensor {point_q, dist2, point_x, tri}: read
+        the triangle ids with out[:, 7].view(torch.int32) (no result: -1).  mode: CLEARANCE_SORT, CLEARANCE_COUNT.
+        ValueError for a wrong shape, dtype, device or layout."""
+        if isinstance(tris, np.ndarray) and tris.dtype != _L.TRI_DTYPE and (
+                (tris.ndim == 3 and tris.shape[1:] == (3, 3)) or (tris.ndim == 2 and tris.shape[1] == 9)):
+            tris = make_tris(tris)
+        kind, tr = check_cross_tris(tris, getattr(self, "device", None))
+        if mode & ~(_L.CLEARANCE_SORT | _L.CLEARANCE_COUNT):
+            raise ValueError(f"clearance: mode takes CLEARANCE_SORT and CLEARANCE_COUNT only, got {mode:#x}")
+        try:
+            bound = ctypes.c_float(max_dist2)
+        except TypeError:
+            raise ValueError(f"clearance: max_dist2 must be one number, got {max_dist2!r}") from None
+        n = len(tr)
+        if kind == "numpy":
+            if stream is not None:
+                raise ValueError("clearance: a stream goes with a torch tensor of triangles")
+            out = np.zeros(n, _L.CLEARANCE_DTYPE)
+            self._check(_L.lib().rtbvh_clearance_host(self._h, ctypes.c_void_p(tr.ctypes.data), n, bound,
+                                                      ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        out = torch.empty((n, 8), dtype=torch.float32, device=tr.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(tr.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(tr.device).synchronize()
+        self._check(_L.lib().rtbvh_clearance_async(self._h, ctypes.c_void_p(tr.data_ptr()), n, bound,
+                                                   ctypes.c_void_p(out.data_ptr()), mode,
+                                                   ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+        return out
+
+    def clearance_counts(self) -> dict:
+        """rtbvh_clearance_counts: queries, results found, internal-node and leaf steps of the last CLEARANCE_COUNT
+        query (the other queries' counts are kept apart)."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_clearance_counts(self._h, _L.ptr(out)))
+        return dict(zip(("queries", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
     # -- signed-distance queries --
     def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
         """rtbvh_signed_async / rtbvh_signed_host: for each point Context.nearest's fields and `flags`, the crossing
