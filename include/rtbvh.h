@@ -227,6 +227,12 @@ typedef struct {
      * not cover (a direction component under 2^-20, |d| off unit, |o| > 2^90), deferred at their first step and
      * walked in the reference order by the walk's drained waves or the re-trace kernel */
     uint64_t redo_deferred;
+    /* The walk-only tree (rtbvh_read_walk_qnodes; added at the end, the ABI number stays): how many the context has
+     * made since rtbvh_create, and whether the last trace's certified bounce passes walked one (1) or the built
+     * tree's QNodes (0) */
+    uint64_t walk_tree_builds;
+    uint32_t walk_tree_used;
+    uint32_t reserved_walk_tree;
 } rtbvh_stats;
 typedef struct rtbvh_ctx rtbvh_ctx;
 
@@ -1184,6 +1190,13 @@ rtbvh_status rtbvh_read_wide(rtbvh_ctx* ctx, uint32_t* records, uint64_t capacit
  * 12-15 (a build of more than 2048 triangles leaves the others untouched); capacity in records
  * (>= 2n-1). */
 rtbvh_status rtbvh_read_qnodes(rtbvh_ctx* ctx, uint32_t* nodes, uint64_t capacity);
+/* The walk-only tree's quantized nodes, in rtbvh_read_qnodes' format (every internal node's is written): a second
+ * tree over the same sorted leaves -- the built tree's top, every maximal subtree of <= 512 leaves rebuilt by binned
+ * SAH -- that the certified 4-wide bounce walk reads from the third trace of a build on (environment
+ * RTBVH_WALK_TREE at rtbvh_create: 0 never, 1 from the first).  Nothing else reads it: queries, the other walks
+ * and every other read-back keep the built tree.  RTBVH_ERR_NOT_READY when the context holds none for the
+ * current build (rtbvh_stats.walk_tree_builds counts them). */
+rtbvh_status rtbvh_read_walk_qnodes(rtbvh_ctx* ctx, uint32_t* nodes, uint64_t capacity);
 /* Per-triangle Morton codes in triangle order (MortonCodes.hlsl:104-112). */
 rtbvh_status rtbvh_read_morton(rtbvh_ctx* ctx, uint32_t* codes);
 /* Stable radix order: sorted codes and the triangle id of each sorted position. */

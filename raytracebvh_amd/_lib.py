@@ -35,7 +35,7 @@ EXPORTS = [
     "rtbvh_trace_async", "rtbvh_compute_bvh", "rtbvh_trace_band_async", "rtbvh_band_rows", "rtbvh_verify_walk",
     "rtbvh_deal_bands", "rtbvh_deal_rows", "rtbvh_set_band_deal",
     "rtbvh_synchronize", "rtbvh_read_framebuffer", "rtbvh_read_intensity", "rtbvh_framebuffer_device",
-    "rtbvh_read_bvh", "rtbvh_read_wide", "rtbvh_read_qnodes", "rtbvh_read_morton", "rtbvh_read_sorted", "rtbvh_read_rays", "rtbvh_get_stats",
+    "rtbvh_read_bvh", "rtbvh_read_wide", "rtbvh_read_qnodes", "rtbvh_read_walk_qnodes", "rtbvh_read_morton", "rtbvh_read_sorted", "rtbvh_read_rays", "rtbvh_get_stats",
     "rtbvh_reset_stats", "rtbvh_set_flags", "rtbvh_bin_builds", "rtbvh_bin_sets",
     "rtbvh_sort_pairs_async", "rtbvh_sort_pairs_host", "rtbvh_build_from_codes", "rtbvh_scene_load_obj",
     "rtbvh_scene_synthetic", "rtbvh_scene_free", "rtbvh_scene_num_vertices", "rtbvh_scene_num_indices",
@@ -158,7 +158,9 @@ class Stats(ctypes.Structure):
                 ("walk_state", ctypes.c_uint32), ("packet_steps", ctypes.c_uint64 * 2),
                 ("cert_traces", ctypes.c_uint64), ("redo_total", ctypes.c_uint64),
                 ("bin_entries", ctypes.c_uint64 * 2), ("redo_rays", ctypes.c_uint64 * 2),
-                ("trav_longest", ctypes.c_uint64), ("redo_deferred", ctypes.c_uint64)]
+                ("trav_longest", ctypes.c_uint64), ("redo_deferred", ctypes.c_uint64),
+                ("walk_tree_builds", ctypes.c_uint64), ("walk_tree_used", ctypes.c_uint32),
+                ("reserved_walk_tree", ctypes.c_uint32)]
 
     def as_dict(self) -> dict:
         d = {}
@@ -227,6 +229,7 @@ def lib() -> ctypes.CDLL:
         "rtbvh_read_morton": (i32, [vp, vp]),
         "rtbvh_read_wide": (i32, [vp, vp, ctypes.c_uint64]),
         "rtbvh_read_qnodes": (i32, [vp, vp, ctypes.c_uint64]),
+        "rtbvh_read_walk_qnodes": (i32, [vp, vp, ctypes.c_uint64]),
         "rtbvh_read_sorted": (i32, [vp, vp, vp]),
         "rtbvh_read_rays": (i32, [vp, vp, vp]),
         "rtbvh_get_stats": (i32, [vp, ctypes.POINTER(Stats)]),

@@ -131,6 +131,31 @@ struct PbBufs {
     uint32_t readers = 0;       // trace buffer sets whose traces have read the set since its fill (bit k: set k)
 };
 
+// The walk-only tree (rtbvh_internal.h WalkTree) is a product of the built tree alone, like a bin
+// set: it records the tree it was made from (`epoch`: bins_epoch, which everything that rewrites leaf records, node
+// boxes or topology bumps -- a build, a replayed build, a refit, set_scene, build_from_codes; a vertex update makes
+// the tree stale until one of them).  Made on the context stream before the third certified bounce trace of a
+// build (`passes`): two traces on the built tree's QNodes cost nothing extra, and a tree traced a third time is
+// taken as static.  `ready` is recorded behind its QNode pass: a reader on another stream waits for it.  Its
+// buffers are overwritten only for a later tree, whose build has waited for every trace that read them.
+// Never made or used inside a graph capture.  RTBVH_WALK_TREE=0: never; =1: before the first trace.
+struct WalkTreeBufs {
+    Grown<uint4> topo;
+    Grown<uint32_t> pint, roots;
+    Grown<float> nbox, edge;
+    Grown<QNode> qnode;
+    bool valid = false;
+    uint64_t epoch = 0;        // when valid: the tree it is of
+    uint32_t T = 0;
+    Event ready;
+    uint64_t seen_epoch = 0;   // the tree whose certified bounce traces `passes` counts
+    uint32_t passes = 0;
+    void reset() {
+        topo.reset(); pint.reset(); roots.reset(); nbox.reset(); edge.reset(); qnode.reset();
+        valid = false;
+    }
+};
+
 // A trace buffer set: everything one primary -> bounce chain writes.  Set 0 is the context stream's; set b >= 1
 // is chain b of a context-stream trace dealt over chains (the rank's bands over `nsplit` chains on their own
 // streams, so one chain's kernel tail overlaps the others' work), or the set of a caller stream with frames in
@@ -174,6 +199,7 @@ struct LastTrace {
     bool cert = false;               // certified (its re-trace counts)
     bool frame_here = false;         // d_color holds its whole frame
     bool intensity_here = false;     // d_intensity holds its intensities
+    bool walk_tree = false;          // its certified bounce passes walked the walk-only tree
 };
 
 struct rtbvh_ctx {
@@ -255,6 +281,9 @@ struct rtbvh_ctx {
     uint64_t bins_epoch = 1;        // bumped whenever the leaf footprints are (or are about to be) rewritten
     uint64_t bin_builds = 0;        // count passes launched (rtbvh_bin_builds)
     bool knob_bins_reuse = true;    // RTBVH_BINS_REUSE
+    WalkTreeBufs wt;                // the walk-only tree, freed with the build buffers
+    int knob_walk_tree = -1;        // RTBVH_WALK_TREE: 0 never, 1 before the first trace, else before the third
+    uint64_t walk_tree_builds = 0;
     LastTrace last;
 
     // hipEvent rings: per build 6 events (before bounds, after bounds/morton/sort/karras/refit),
@@ -442,6 +471,7 @@ rtbvh_status ensure_build_capacity(rtbvh_ctx* c, uint32_t T) {
     if (T <= c->cap_T && c->d_codes) return RTBVH_OK;
     drop_graph(c);
     reset_tree(c);   // (its buffers go)
+    c->wt.reset();
     const size_t n = T, ni = T > 1 ? T - 1 : 1;
     HIPC(c, c->d_codes.alloc(n));
     HIPC(c, c->d_ids.alloc(n));
@@ -921,7 +951,46 @@ struct WalkPlan {
     bool inflight, fuse_tail, overlap, small_tiles, early_shade;
     uint32_t bset;          // prepare_walks: the buffer set whose bin set the binned pass reads ...
     bool fill_bins;         //   ... and fills first (its own)
+    bool walk_tree;         // prepare_walks: the certified bounce passes walk the walk-only tree
 };
+
+// The walk-only tree for this trace's certified 4-wide bounce passes: 0 none (the built tree's QNodes), 1 the one the
+// context holds for the current build, 2 made first.  Counts the trace (WalkTreeBufs::passes).
+int plan_walk_tree(rtbvh_ctx* c, const WalkPlan& p) {
+    if (c->capturing || c->knob_walk_tree == 0 || c->T < 2) return 0;
+    if (!(p.cert && p.bounces > 0 && p.wk.refill && p.wk.bounce == BounceWalk::WIDE_QUANTIZED)) return 0;
+    WalkTreeBufs& w = c->wt;
+    if (w.seen_epoch != c->bins_epoch) {
+        w.seen_epoch = c->bins_epoch;
+        w.passes = 0;
+    }
+    w.passes++;
+    if (w.valid && w.epoch == c->bins_epoch && w.T == c->T) return 1;
+    return c->knob_walk_tree == 1 || w.passes >= 3 ? 2 : 0;
+}
+// ... made: on the context stream, behind the complete built tree (its crossing nodes and node boxes included)
+rtbvh_status make_walk_tree(rtbvh_ctx* c) {
+    WalkTreeBufs& w = c->wt;
+    const size_t T = c->T, ni = T - 1;
+    w.valid = false;
+    HIPC(c, w.topo.reserve(ni));
+    HIPC(c, w.pint.reserve(ni));
+    HIPC(c, w.nbox.reserve(6 * ni));
+    HIPC(c, w.edge.reserve(ni));
+    HIPC(c, w.qnode.reserve(2 * T - 1));
+    HIPC(c, w.roots.reserve(2 + T / 2));
+    if (!w.ready) HIPC(c, hipEventCreateWithFlags(w.ready.out(), hipEventDisableTiming));
+    BuildArgs a = build_args(c);
+    a.nbox = c->d_nbox;
+    launch_walk_tree(a, WalkTree{w.topo, w.pint, w.nbox, w.edge, w.qnode, w.roots}, c->stream);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(w.ready, c->stream));
+    w.valid = true;
+    w.epoch = c->bins_epoch;
+    w.T = c->T;
+    c->walk_tree_builds++;
+    return RTBVH_OK;
+}
 
 WalkPlan plan_walks(const rtbvh_ctx* c, const TraceArgs& a, uint32_t bounces, hipStream_t s, uint32_t slot,
                     uint32_t flags, bool cert, bool timed, bool tail_pending, bool leaf_pending) {
@@ -1001,6 +1070,8 @@ rtbvh_status prepare_walks(rtbvh_ctx* c, WalkPlan& p, TraceArgs& a, const rtbvh_
         a.refl_rec = c->d_refl_rec;
         a.refr_rec = c->d_refr_rec;
     }
+    const int wt = plan_walk_tree(c, p);
+    if (wt == 2) p.fuse_tail = false;   // (it reads the crossing nodes: they run first, not in this trace's bin launches)
     if (!p.fuse_tail && tail.pending) {   // before any walk reads the tree
         tail.run();
         TRY(order_after_context(c, s));   // (a caller stream: ordered after it like after the build)
@@ -1010,6 +1081,14 @@ rtbvh_status prepare_walks(rtbvh_ctx* c, WalkPlan& p, TraceArgs& a, const rtbvh_
     TRY(ensure_split_capacity(c, p.slot ? p.slot + 1 : p.nsplit, p.Pg));
     // a 4-wide bounce walk over a one-workgroup build that quantized no nodes (the context's walks took none)
     if (p.bounces > 0 && p.wk.refill && p.wk.bounce == BounceWalk::WIDE_QUANTIZED) TRY(ensure_form(c, QNODES, s));
+    // the walk-only tree of the certified bounce passes: made here (the node boxes are there: p.nodes), or the
+    // context's; a trace on another stream waits for its QNode pass
+    if (wt) {
+        if (wt == 2) TRY(make_walk_tree(c));
+        if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->wt.ready, 0));
+        a.qnode_walk = c->wt.qnode;
+        p.walk_tree = true;
+    }
     // a packet walk over a tree built without the leaf pseudo-records (the context's walks took none;
     // set_flags since, or a frame past the binned pass's 32768 pixels a side)
     if (p.pkind == PrimaryKind::PACKET_REFERENCE || p.pkind == PrimaryKind::PACKET_NEAREST ||
@@ -1213,7 +1292,7 @@ rtbvh_status enqueue_walks(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bounce
     TRY(launch_walks(c, p, a, tail));
     const bool frame_here = color == c->d_color && nranks == 1;
     c->last = LastTrace{true, W, H, bounces, rank, nranks, p.nsplit, slot, p.records ? p.P : 0, flags & WALK_FLAGS,
-                        walk_state, cert, frame_here, frame_here && inten != nullptr};
+                        walk_state, cert, frame_here, frame_here && inten != nullptr, p.walk_tree};
     return check_launch(c, "trace kernels");
 }
 
@@ -1376,6 +1455,7 @@ rtbvh_status rtbvh_create(const rtbvh_config* cfg, rtbvh_ctx** out) {
     if (const char* e = getenv("RTBVH_EARLY_SHADE")) c->knob_no_early_shade = atoi(e) == 0;   // (A/B: 0 = off)
     if (const char* e = getenv("RTBVH_PB_SMALL_TILES")) c->knob_no_small_tiles = atoi(e) == 0;   // (A/B: 0 = off)
     if (const char* e = getenv("RTBVH_BINS_REUSE")) c->knob_bins_reuse = atoi(e) != 0;   // (A/B: 0 = a fill per trace)
+    if (const char* e = getenv("RTBVH_WALK_TREE")) c->knob_walk_tree = atoi(e) != 0 ? 1 : 0;   // (tests, A/B)
     *out = c;
     return RTBVH_OK;
 }
@@ -2062,6 +2142,19 @@ rtbvh_status rtbvh_read_qnodes(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
     return RTBVH_OK;
 }
 
+rtbvh_status rtbvh_read_walk_qnodes(rtbvh_ctx* c, uint32_t* out, uint64_t capacity) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    const WalkTreeBufs& w = c->wt;
+    if (!c->tree.built || !(w.valid && w.epoch == c->bins_epoch && w.T == c->T))
+        return fail(c, RTBVH_ERR_NOT_READY, "read_walk_qnodes: no walk-only tree of the current build");
+    const uint64_t total = 2 * (uint64_t)c->T - 1;
+    if (capacity < total) return fail(c, RTBVH_ERR_INVALID_ARG, "read_walk_qnodes: capacity < 2n-1");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpy(out, w.qnode, total * sizeof(QNode), hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
 rtbvh_status rtbvh_read_morton(rtbvh_ctx* c, uint32_t* codes) {
     if (!c || !codes) return RTBVH_ERR_INVALID_ARG;
     if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "no build yet");
@@ -2174,6 +2267,8 @@ rtbvh_status rtbvh_get_stats(rtbvh_ctx* c, rtbvh_stats* out) {
         }
     }
     out->redo_total = out->redo_rays[0] + out->redo_rays[1];
+    out->walk_tree_builds = c->walk_tree_builds;
+    out->walk_tree_used = t.traced && t.walk_tree ? 1u : 0u;
     return RTBVH_OK;
 }
 

@@ -865,16 +865,21 @@ __global__ __launch_bounds__(BLOCK) void k_qnodes(Inner* __restrict__ rec, const
 }
 
 // the QNode of crossing node k at its slot, from the node boxes or the records (k_qnodes_late, k_pb_count_late)
+// the QNode of node k at its slot from the topology and the node boxes (a.topo, a.nbox, a.pint: the built tree's, or
+// the walk-only tree's, k_wt_qnodes), E the largest edge bound below it
+__device__ __forceinline__ void qnode_nbox(const BuildArgs& a, uint32_t k, float E) {
+    QEnt e0, e1;
+    nbox_kids(a, k, e0, e1);
+    float4 w[4];
+    uint32_t ent[4];
+    greedy_qnode_words(e0, e1, [&](const QEnt& e, QEnt& c0, QEnt& c1) { nbox_kids(a, e.id, c0, c1); }, E, w, ent);
+    store4(a.qnode + slot_of(a.pint[k], a.T), w);
+}
 __device__ __forceinline__ void qnode_cross(const BuildArgs& a, uint32_t k) {
     const uint32_t slot = slot_of(a.pint[k], a.T);
     const float E = *node_edge(a, k);
     if (!a.rec_on) {   // no records: the topology and the node boxes (no pseudo-records either)
-        QEnt e0, e1;
-        nbox_kids(a, k, e0, e1);
-        float4 w[4];
-        uint32_t ent[4];
-        greedy_qnode_words(e0, e1, [&](const QEnt& e, QEnt& c0, QEnt& c1) { nbox_kids(a, e.id, c0, c1); }, E, w, ent);
-        store4(a.qnode + slot, w);
+        qnode_nbox(a, k, E);
     } else if (a.pseudo) {
         qnode_from_records<false>(a.rec, slot, E, a.qnode + slot);
     } else {
@@ -1675,9 +1680,303 @@ __global__ __launch_bounds__(BLOCK) void k_export(BuildArgs a, RefNode* __restri
     out[r] = o;
 }
 
+// ---- the walk-only tree (rtbvh_internal.h WalkTree) --------------------------------------
+// A second tree over the same sorted leaves for the certified 4-wide bounce walk, which is exact on any tree
+// whose boxes contain its leaves: the built tree's top as it is, and every maximal subtree of <= WT_K leaves
+// rebuilt top-down by binned SAH (tools/collapse_study.cpp REBUILD=bottom is the same rule on the CPU: WT_NB
+// centroid bins an axis, cost area(L) nL + area(R) nR, the lowest axis and then plane on a tie, halves where no
+// plane separates the centroids).  Such a subtree is a run of sorted leaves [lo, hi] whose internal nodes are the
+// ids [lo, hi] but one: its root (lo or hi) keeps its id, the others come from (lo, hi) by Karras' own rule on
+// the subtree's new leaf order -- a left child is named by its last position, a right child by its first.
+// The leaves keep their sorted index (LEAF_BIT | j), so hit keys and leaf records are the built tree's.
+constexpr uint32_t WT_K = 512;     // leaves of a rebuilt subtree (one workgroup, the subtree in LDS)
+constexpr uint32_t WT_BLOCK = 256, WT_WAVES = WT_BLOCK / 64;
+constexpr int WT_NB = 16;          // centroid bins per axis
+constexpr int WT_DEPTH = 32;       // SAH splits above this depth below the subtree's root; halves from there on
+constexpr int WT_LEVELS = 64;      // internal levels of a root path (STACK4B: three stack entries a level)
+static_assert(RBLOCK <= WT_K, "a node of more than WT_K leaves crosses a refit workgroup: its edge bound is in inner[]");
+static_assert(WT_K <= 65536 && WT_K % 2 == 0, "positions are 16-bit");
+
+// floats as unsigned integers of the same order (no NaN among them): the bins' boxes by integer atomics
+__device__ __forceinline__ uint32_t wt_ord(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float wt_unord(uint32_t u) {
+    return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+__device__ __forceinline__ int wt_clog2(uint32_t m) { return m <= 1 ? 0 : 32 - __clz(m - 1); }
+// what one wave wrote to LDS, read by its other lanes
+__device__ __forceinline__ void wt_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ float wt_first(float x) {   // lane 0's value, in every lane
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
+}
+__device__ __forceinline__ int wt_bin(float lo, float hi, float cl, float sc) {
+    return (int)fminf(fmaxf((0.5f * (lo + hi) - cl) * sc, 0.f), (float)(WT_NB - 1));   // (NaN: the last bin)
+}
+
+// One thread per internal node: a node of more than WT_K leaves is of the top (copied), a node of <= WT_K under
+// such a parent (or the root) is a subtree root (listed; the count stays on the device), the others are rewritten
+// by k_wt_rebuild
+__global__ __launch_bounds__(BLOCK) void k_wt_select(BuildArgs a, WalkTree w) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k + 1 >= a.T) return;
+    const uint4 t = a.topo[k];
+    const uint32_t e = a.pint[k];
+    // (a range that is none -- a tree with the CPUTests delta, which no certified walk takes -- is never rebuilt)
+    if (t.w - t.z + 1 > WT_K || t.z > t.w || t.w >= a.T) {
+        w.topo[k] = t;
+        w.pint[k] = e;
+        float b[6];
+        ld_nbox(a.nbox, k, b);
+        st_nbox(w.nbox, k, mk(b[0], b[1], b[2]), mk(b[3], b[4], b[5]));
+        w.edge[k] = *node_edge(a, k);
+        return;
+    }
+    bool root = e == INVALID;
+    if (!root) {
+        const uint4 p = a.topo[e >> 1];
+        root = p.w - p.z + 1 > WT_K;
+    }
+    if (root) {
+        w.pint[k] = e;
+        w.roots[1 + atomicAdd(&w.roots[0], 1u)] = k;
+    }
+}
+
+// One workgroup per listed root (a fixed grid over the list), level by level: a wave per range of the level.
+// Every loop is bounded by the data: a range of m >= 2 leaves always splits into two non-empty ones, and the
+// levels by WT_LEVELS (a range at depth d keeps d + ceil(log2 m) within the subtree's level budget: a split that
+// would break that, a range past WT_DEPTH, a non-finite box or no separating plane splits in halves).
+__global__ __launch_bounds__(WT_BLOCK) void k_wt_rebuild(BuildArgs a, WalkTree w) {
+    __shared__ float s_box[6][WT_K];          // the leaves' boxes, by sorted index - lo
+    __shared__ float s_edge[WT_K];            // ... and edge bounds (margin.h)
+    __shared__ uint16_t s_perm[2][WT_K];      // position -> leaf; [1]: the partition's other side
+    __shared__ uint32_t s_seg[2][WT_K / 2][2];   // the ranges of this level and the next: first | last << 16, node id
+    __shared__ uint32_t s_nseg[2];
+    __shared__ int s_budget;
+    __shared__ uint32_t s_bin[WT_WAVES][3][WT_NB][7];   // a wave's bins: box (wt_ord), count
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nroots = min(w.roots[0], a.T / 2);
+    for (uint32_t r = blockIdx.x; r < nroots; r += gridDim.x) {
+        __syncthreads();   // (the last subtree's LDS is read no more)
+        const uint32_t k0 = w.roots[1 + r];
+        const uint4 t0 = a.topo[k0];
+        const uint32_t lo = t0.z, n = min(t0.w - t0.z + 1, WT_K);
+        for (uint32_t i = tid; i < n; i += WT_BLOCK) {
+            const float4* rec = a.leaf + 4 * (size_t)(lo + i);
+            const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+            s_box[0][i] = r2.z; s_box[1][i] = r2.w; s_box[2][i] = r3.x;
+            s_box[3][i] = r3.y; s_box[4][i] = r3.z; s_box[5][i] = r3.w;
+            s_edge[i] = mt_edge_bound(r0.w, r1.x, r1.y, r1.z, r1.w, r2.x);
+            s_perm[0][i] = (uint16_t)i;
+        }
+        if (tid == 0) {
+            int depth = 0;   // of k0 in the built tree
+            for (uint32_t e = a.pint[k0]; e != INVALID && depth < WT_LEVELS; e = a.pint[e >> 1]) ++depth;
+            s_budget = max(min(WT_DEPTH + wt_clog2(WT_K), WT_LEVELS - depth), wt_clog2(n));
+            s_seg[0][0][0] = (n - 1) << 16;
+            s_seg[0][0][1] = k0;
+            s_nseg[0] = 1;
+            s_nseg[1] = 0;
+        }
+        __syncthreads();
+        for (int level = 0; level < WT_LEVELS; level++) {
+            const uint32_t cur = level & 1, nxt = cur ^ 1u;
+            const uint32_t ns = min(s_nseg[cur], WT_K / 2);
+            if (ns == 0) break;
+            for (uint32_t sg = wave; sg < ns; sg += WT_WAVES) {
+                const uint32_t ab = s_seg[cur][sg][0], id = s_seg[cur][sg][1];
+                const uint32_t pa = ab & 0xFFFFu, pb = ab >> 16, m = pb - pa + 1;
+                // the range's box, centroid box, edge bound; `fin`: every corner finite
+                f3 bl = mk(INFINITY, INFINITY, INFINITY), bh = mk(-INFINITY, -INFINITY, -INFINITY), cl = bl, ch = bh;
+                float em = 0.f;
+                bool fin = true;
+                for (uint32_t p = pa + lane; p <= pb; p += 64) {
+                    const uint32_t j = s_perm[0][p];
+                    const f3 l = mk(s_box[0][j], s_box[1][j], s_box[2][j]), h = mk(s_box[3][j], s_box[4][j], s_box[5][j]);
+                    bl = vmin(bl, l);
+                    bh = vmax(bh, h);
+                    const f3 c = mk(0.5f * (l.x + h.x), 0.5f * (l.y + h.y), 0.5f * (l.z + h.z));
+                    cl = vmin(cl, c);
+                    ch = vmax(ch, c);
+                    em = fmaxf(em, s_edge[j]);
+                    fin = fin && fabsf(l.x) < INFINITY && fabsf(l.y) < INFINITY && fabsf(l.z) < INFINITY &&
+                          fabsf(h.x) < INFINITY && fabsf(h.y) < INFINITY && fabsf(h.z) < INFINITY;
+                }
+                // (a butterfly over the lanes that hold leaves: lane 0 has the whole range's; the centroid box, which
+                // every lane bins by, from there)
+                for (int off = m >= 64 ? 32 : (1 << wt_clog2(m)) >> 1; off > 0; off >>= 1) {
+                    bl = vmin(bl, mk(__shfl_xor(bl.x, off, 64), __shfl_xor(bl.y, off, 64), __shfl_xor(bl.z, off, 64)));
+                    bh = vmax(bh, mk(__shfl_xor(bh.x, off, 64), __shfl_xor(bh.y, off, 64), __shfl_xor(bh.z, off, 64)));
+                    cl = vmin(cl, mk(__shfl_xor(cl.x, off, 64), __shfl_xor(cl.y, off, 64), __shfl_xor(cl.z, off, 64)));
+                    ch = vmax(ch, mk(__shfl_xor(ch.x, off, 64), __shfl_xor(ch.y, off, 64), __shfl_xor(ch.z, off, 64)));
+                    em = fmaxf(em, __shfl_xor(em, off, 64));
+                }
+                cl = mk(wt_first(cl.x), wt_first(cl.y), wt_first(cl.z));
+                ch = mk(wt_first(ch.x), wt_first(ch.y), wt_first(ch.z));
+                fin = __all(fin);
+                if (lane == 0) {
+                    st_nbox(w.nbox, id, bl, bh);
+                    w.edge[id] = em;
+                }
+                // the split: the cheapest of the 3 x (WT_NB - 1) planes, a lane each
+                const float cmin[3] = {cl.x, cl.y, cl.z}, cmax[3] = {ch.x, ch.y, ch.z};
+                float sc[3];
+                bool axis_ok[3];
+#pragma unroll
+                for (int x = 0; x < 3; x++) {
+                    axis_ok[x] = cmax[x] > cmin[x];
+                    sc[x] = axis_ok[x] ? (float)WT_NB / (cmax[x] - cmin[x]) : 0.f;
+                }
+                uint32_t nl = m / 2;   // halves
+                int best = -1;         // axis * WT_NB + plane, or none
+                if (m > 2 && fin && level < WT_DEPTH && (axis_ok[0] || axis_ok[1] || axis_ok[2])) {
+                    uint32_t* bins = &s_bin[wave][0][0][0];
+                    for (uint32_t q = lane; q < 3 * WT_NB; q += 64) {
+                        uint32_t* b = bins + 7 * q;
+                        b[0] = b[1] = b[2] = 0xFFFFFFFFu;
+                        b[3] = b[4] = b[5] = b[6] = 0u;
+                    }
+                    wt_wave_sync();
+                    for (uint32_t p = pa + lane; p <= pb; p += 64) {
+                        const uint32_t j = s_perm[0][p];
+                        uint32_t o[6];
+#pragma unroll
+                        for (int q = 0; q < 6; q++) o[q] = wt_ord(s_box[q][j]);
+#pragma unroll
+                        for (int x = 0; x < 3; x++) {
+                            if (!axis_ok[x]) continue;
+                            uint32_t* b = &s_bin[wave][x][wt_bin(s_box[x][j], s_box[3 + x][j], cmin[x], sc[x])][0];
+                            atomicMin(&b[0], o[0]); atomicMin(&b[1], o[1]); atomicMin(&b[2], o[2]);
+                            atomicMax(&b[3], o[3]); atomicMax(&b[4], o[4]); atomicMax(&b[5], o[5]);
+                            atomicAdd(&b[6], 1u);
+                        }
+                    }
+                    wt_wave_sync();
+                    float cost = INFINITY;
+                    uint32_t cnt_l = 0;
+                    const int x = (int)lane / (WT_NB - 1), plane = (int)lane % (WT_NB - 1);
+                    if (x == 0 ? axis_ok[0] : x == 1 ? axis_ok[1] : x == 2 ? axis_ok[2] : false) {
+                        uint32_t L[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u}, R[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u}, nL = 0, nR = 0;
+#pragma unroll
+                        for (int k = 0; k < WT_NB; k++) {   // (an empty bin holds the neutral values)
+                            const uint32_t* b = &s_bin[wave][x][k][0];
+                            const bool isl = k <= plane;
+                            nL += isl ? b[6] : 0u;
+                            nR += isl ? 0u : b[6];
+#pragma unroll
+                            for (int q = 0; q < 3; q++) {
+                                L[q] = isl ? min(L[q], b[q]) : L[q];
+                                L[3 + q] = isl ? max(L[3 + q], b[3 + q]) : L[3 + q];
+                                R[q] = isl ? R[q] : min(R[q], b[q]);
+                                R[3 + q] = isl ? R[3 + q] : max(R[3 + q], b[3 + q]);
+                            }
+                        }
+                        if (nL && nR) {
+                            float lb[6], rb[6];
+#pragma unroll
+                            for (int q = 0; q < 6; q++) { lb[q] = wt_unord(L[q]); rb[q] = wt_unord(R[q]); }
+                            const float c = half_area(lb) * (float)nL + half_area(rb) * (float)nR;
+                            if (c < INFINITY) { cost = c; cnt_l = nL; }   // (NaN, inf: not a candidate)
+                        }
+                    }
+                    uint32_t pick = cost < INFINITY ? lane : 0xFFFFu;
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const float oc = __shfl_xor(cost, off, 64);
+                        const uint32_t op = __shfl_xor(pick, off, 64);
+                        if (oc < cost || (oc == cost && op < pick)) { cost = oc; pick = op; }
+                    }
+                    if (pick != 0xFFFFu) {
+                        const uint32_t cn = __shfl(cnt_l, (int)pick, 64);
+                        // (the level budget: both sides must still fit below as halves)
+                        if (level + 1 + wt_clog2(max(cn, m - cn)) <= s_budget) {
+                            best = (int)(pick / (WT_NB - 1)) * WT_NB + (int)(pick % (WT_NB - 1));
+                            nl = cn;
+                        }
+                    }
+                }
+                if (best >= 0) {   // a stable partition of the positions [pa, pb] by the plane
+                    const int x = best / WT_NB, plane = best % WT_NB;
+                    uint32_t base_l = pa, base_r = pa + nl;
+                    for (uint32_t p0 = pa; p0 <= pb; p0 += 64) {
+                        const uint32_t p = p0 + lane;
+                        const bool valid = p <= pb;
+                        const uint32_t j = valid ? s_perm[0][p] : 0u;
+                        // (the axis by a chain of selects: no dynamically indexed registers)
+                        const float blo = x == 0 ? s_box[0][j] : x == 1 ? s_box[1][j] : s_box[2][j];
+                        const float bhi = x == 0 ? s_box[3][j] : x == 1 ? s_box[4][j] : s_box[5][j];
+                        const float c0 = x == 0 ? cmin[0] : x == 1 ? cmin[1] : cmin[2];
+                        const float s0 = x == 0 ? sc[0] : x == 1 ? sc[1] : sc[2];
+                        const bool left = valid && wt_bin(blo, bhi, c0, s0) <= plane;
+                        const unsigned long long ml = __ballot(left), mr = __ballot(valid && !left);
+                        const unsigned long long below = (1ull << lane) - 1ull;
+                        if (valid) {
+                            const uint32_t dst = left ? base_l + (uint32_t)__popcll(ml & below)
+                                                      : base_r + (uint32_t)__popcll(mr & below);
+                            if (dst <= pb) s_perm[1][dst] = (uint16_t)j;
+                        }
+                        base_l += (uint32_t)__popcll(ml);
+                        base_r += (uint32_t)__popcll(mr);
+                    }
+                    wt_wave_sync();
+                    for (uint32_t p = pa + lane; p <= pb; p += 64) s_perm[0][p] = s_perm[1][p];
+                    wt_wave_sync();
+                }
+                if (lane == 0) {   // the node, and its internal children as the next level's ranges
+                    const uint32_t la = pa, lb = pa + nl - 1, ra = pa + nl, rb = pb;
+                    const uint32_t idl = la == lb ? (LEAF_BIT | (lo + s_perm[0][la])) : lo + lb;
+                    const uint32_t idr = ra == rb ? (LEAF_BIT | (lo + s_perm[0][ra])) : lo + ra;
+                    w.topo[id] = make_uint4(idl, idr, lo + pa, lo + pb);   // (z, w: its positions, not a leaf range)
+                    if (la != lb) {
+                        w.pint[idl] = id << 1;
+                        const uint32_t q = atomicAdd(&s_nseg[nxt], 1u);
+                        if (q < WT_K / 2) { s_seg[nxt][q][0] = la | lb << 16; s_seg[nxt][q][1] = idl; }
+                    }
+                    if (ra != rb) {
+                        w.pint[idr] = (id << 1) | 1u;
+                        const uint32_t q = atomicAdd(&s_nseg[nxt], 1u);
+                        if (q < WT_K / 2) { s_seg[nxt][q][0] = ra | rb << 16; s_seg[nxt][q][1] = idr; }
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid == 0) s_nseg[cur] = 0;
+            __syncthreads();
+        }
+    }
+}
+
+// The walk-only tree's QNodes, one thread per internal node: qnode_cross's no-records path over the walk tree's
+// arrays (a: the build's arguments with topo, pint, nbox and qnode the walk tree's)
+__global__ __launch_bounds__(BLOCK) void k_wt_qnodes(BuildArgs a, const float* __restrict__ edge) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k + 1 >= a.T) return;
+    qnode_nbox(a, k, edge[k]);
+}
+
 inline uint32_t blocks_for(size_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); }
 
 }  // namespace
+
+void launch_walk_tree(const BuildArgs& a, const WalkTree& w, hipStream_t s) {
+    if (a.T < 2) return;   // (one leaf: the walk starts at it)
+    (void)hipMemsetAsync(w.roots, 0, sizeof(uint32_t), s);
+    hipLaunchKernelGGL(k_wt_select, dim3(blocks_for(a.T - 1)), dim3(BLOCK), 0, s, a, w);
+    hipLaunchKernelGGL(k_wt_rebuild, dim3(min(4096u, blocks_for(a.T))), dim3(WT_BLOCK), 0, s, a, w);
+    BuildArgs q = a;
+    q.topo = w.topo;
+    q.pint = w.pint;
+    q.nbox = w.nbox;
+    q.qnode = w.qnode;
+    q.rec_on = 0;
+    hipLaunchKernelGGL(k_wt_qnodes, dim3(blocks_for(a.T - 1)), dim3(BLOCK), 0, s, q, w.edge);
+}
 
 void launch_bounds(const BuildArgs& a, hipStream_t s) {
     uint32_t blocks = blocks_for(a.V);

@@ -122,6 +122,19 @@ void launch_morton_sort_small(const BuildArgs& a, hipStream_t s);
 // records (one that wrote only records)
 void launch_records(const BuildArgs& a, hipStream_t s);
 void launch_nbox(const BuildArgs& a, hipStream_t s);
+// The walk-only tree (build.hip k_wt_*): the built tree's top with every maximal subtree of <= 512
+// leaves rebuilt by binned SAH over the same sorted leaves, and its QNodes in slots -- what the certified 4-wide
+// bounce walk reads in place of BuildArgs::qnode on a tree that is traced again and again.  Made from the complete
+// built tree (topo, pint, the node boxes a.nbox, the crossing nodes' edge bounds in a.inner, the leaf records)
+struct WalkTree {
+    uint4* topo;        // [T-1] child ids as BuildArgs::topo; z, w: the node's positions in its subtree's leaf order
+    uint32_t* pint;     // [T-1]
+    float* nbox;        // [6 (T-1)]
+    float* edge;        // [T-1] the largest leaf edge bound below the node (margin.h)
+    QNode* qnode;       // [2T-1]
+    uint32_t* roots;    // [1 + T / 2] the rebuilt subtrees' roots: their count (kept on the device), then the list
+};
+void launch_walk_tree(const BuildArgs& a, const WalkTree& w, hipStream_t s);
 // reference-layout export (44-B Node), 2T-1 entries
 void launch_export(const BuildArgs& a, void* out_nodes, hipStream_t s);
 // Karras + refit from given sorted codes and leaf boxes (n x 6 floats, device)
@@ -169,6 +182,8 @@ struct TraceArgs {
     float* refl_rec;          // optional 14-float RayPresent records (reference reflectRay)
     float* refr_rec;          // optional refractRay records
     const QNode* qnode;       // [2T-1] quantized 4-wide nodes in slots (bounce walk mode 4)
+    const QNode* qnode_walk;  // the walk-only tree's (WalkTree::qnode), or null: what a certified 4-wide bounce pass
+                              //   walks in place of qnode (same slots' meaning, same leaves; nothing else reads it)
     // N > 1, the binned pass's bins: the leaves whose footprint meets the rank's rows, in PB_LISTS lists (the
     // count pass appends them, the fill pass reads only them; null at N = 1, where every leaf is read):
     // counters PB_LIST_STRIDE words apart, then the lists, pb_list_cap(T) entries each (pb_bin.h)

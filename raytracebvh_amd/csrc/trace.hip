@@ -4702,8 +4702,10 @@ void launch_bounce_traverse(const TraceArgs& a, const RayQ* qin, const uint32_t*
     const bool early = RTBVH_EARLY_SHADE && certified && es;
     const uint32_t nshade = early ? (es->P + ESHADE_RAYS - 1) / ESHADE_RAYS : 0u;
     if (early) hipLaunchKernelGGL(k_hit_init, dim3(1024), dim3(BLOCK), 0, s, hitrec, qin_count);
+    // (the certified walk is exact on any tree over the same leaves: the walk-only tree's QNodes where there are any)
+    const QNode* qn = certified && a.qnode_walk ? a.qnode_walk : a.qnode;
     const auto launch = [&](auto* kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks + nshade), dim3(BLOCK), 0, s, a.inner, a.qnode, a.leaf, a.T, qin, qin_count,
+        hipLaunchKernelGGL(kernel, dim3(blocks + nshade), dim3(BLOCK), 0, s, a.inner, qn, a.leaf, a.T, qin, qin_count,
                            perm, hitrec, next, a.counters, a.overflow, wide ? a.stack_limit4b : a.stack_limit, defer,
                            a.topo, a.nb ? a.nbox : nullptr, blocks, a, early ? es->qout : nullptr,
                            early ? es->qout_count : nullptr, early ? (int)es->emit : 0, early ? es->redo : nullptr,

@@ -1309,6 +1309,13 @@ class Context:
         self._check(_L.lib().rtbvh_read_qnodes(self._h, _L.ptr(out), len(out)))
         return out
 
+    def read_walk_qnodes(self) -> np.ndarray:
+        """The walk-only tree's quantized nodes, in read_qnodes' format: (2n-1, 16) uint32, see
+        rtbvh_read_walk_qnodes (RtbvhError NOT_READY when the context holds none for the current build)."""
+        out = np.zeros((max(2 * self.num_tris - 1, 0), 16), np.uint32)
+        self._check(_L.lib().rtbvh_read_walk_qnodes(self._h, _L.ptr(out), len(out)))
+        return out
+
     def read_morton(self) -> np.ndarray:
         out = np.zeros(self.num_tris, np.uint32)
         self._check(_L.lib().rtbvh_read_morton(self._h, _L.ptr(out)))

@@ -113,11 +113,17 @@ static float tri_hit(const float o[3], const float d[3], const float* v) {
 // REBUILD=sah: a binned-SAH top-down binary tree over the same leaves (their boxes; 16 centroid bins on each
 // axis, the cheapest plane), in place of the reference's Karras tree -- what a higher-quality tree would save
 // the walk (max leaves 1 only: the leaf ranges of the Karras tree no longer hold)
+// REBUILD=bottom (BOT_K, default 512): the input tree's top kept, and every maximal subtree of <= BOT_K leaves -- a node
+// of <= BOT_K leaves whose parent has more, or the root -- rebuilt over the same leaves by the same builder, its
+// internal ids reused (`pool`) and its root keeping its id: the rule of the library's walk-only tree (build.hip
+// k_wt_rebuild: a stable partition, halves below `max_depth` levels under the subtree's root)
 struct SahBuilder {
     std::vector<Node>& N;
     uint32_t T;
     std::vector<uint32_t> idx;
-    uint32_t next;   // internal ids from T + 1 (the root is T)
+    uint32_t next;   // internal ids from T + 1 (the root is T); with a pool: the next of its ids
+    std::vector<uint32_t> pool = {};
+    int max_depth = 1 << 30;
     static void grow(float (&b)[6], const Node& n) {
         for (int a = 0; a < 3; a++) { b[a] = std::min(b[a], n.bmin[a]); b[3 + a] = std::max(b[3 + a], n.bmax[a]); }
     }
@@ -129,9 +135,9 @@ struct SahBuilder {
         uint32_t v;
 #pragma omp atomic capture
         v = next++;
-        return v;
+        return pool.empty() ? v : pool[v];
     }
-    uint32_t build(size_t lo, size_t hi, uint32_t id) {
+    uint32_t build(size_t lo, size_t hi, uint32_t id, int depth = 0) {
         if (hi - lo == 1) return idx[lo];
         constexpr int NB = 16;
         float cl[3] = {INFINITY, INFINITY, INFINITY}, ch[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -146,7 +152,7 @@ struct SahBuilder {
         }
         int ba = -1, bb = 0;
         double bc = INFINITY;
-        for (int a = 0; a < 3; a++) {
+        for (int a = 0; a < 3 && depth < max_depth; a++) {
             if (!(ch[a] > cl[a])) continue;
             const float sc = NB / (ch[a] - cl[a]);
             float bx[NB][6];
@@ -182,7 +188,7 @@ struct SahBuilder {
             mid = (lo + hi) / 2;   // every centroid equal: halves
         } else {
             const float sc = NB / (ch[ba] - cl[ba]);
-            auto it = std::partition(idx.begin() + lo, idx.begin() + hi, [&](uint32_t j) {
+            auto it = std::stable_partition(idx.begin() + lo, idx.begin() + hi, [&](uint32_t j) {
                 const Node& n = N[j];
                 return std::min(NB - 1, (int)((0.5f * (n.bmin[ba] + n.bmax[ba]) - cl[ba]) * sc)) <= bb;
             });
@@ -193,13 +199,13 @@ struct SahBuilder {
         uint32_t l, r;
         if (hi - lo > 200000) {
 #pragma omp task shared(l)
-            l = build(lo, mid, il);
+            l = build(lo, mid, il, depth + 1);
 #pragma omp task shared(r)
-            r = build(mid, hi, ir);
+            r = build(mid, hi, ir, depth + 1);
 #pragma omp taskwait
         } else {
-            l = build(lo, mid, il);
-            r = build(mid, hi, ir);
+            l = build(lo, mid, il, depth + 1);
+            r = build(mid, hi, ir, depth + 1);
         }
         Node& n = N[id];
         n.child_l = l;
@@ -241,6 +247,37 @@ int main(int argc, char** argv) {
         rebuilt[T].parent = ~0u;
         N = rebuilt.data();
         fprintf(stderr, "rebuilt: %u internal nodes\n", B.next - T);
+    } else if (rebuild && !strcmp(rebuild, "bottom") && T >= 2) {
+        const uint32_t K = getenv("BOT_K") ? (uint32_t)atoi(getenv("BOT_K")) : 512u;
+        rebuilt.assign(N, N + NN);
+        // the leaves below every node (children before parents: a pre-order, reversed)
+        std::vector<uint32_t> pre{T}, cnt(NN, 1);
+        for (size_t i = 0; i < pre.size(); i++)
+            for (uint32_t c : {N[pre[i]].child_l, N[pre[i]].child_r})
+                if (c >= T) pre.push_back(c);
+        for (size_t i = pre.size(); i-- > 0;) cnt[pre[i]] = cnt[N[pre[i]].child_l] + cnt[N[pre[i]].child_r];
+        size_t roots = 0, nodes = 0;
+        for (uint32_t x : pre) {
+            if (cnt[x] > K || (x != T && cnt[N[x].parent] <= K)) continue;
+            SahBuilder B{rebuilt, T, {}, 0};
+            B.max_depth = 32;
+            std::vector<uint32_t> st{x};   // the subtree's leaves in sorted order, its internal ids but the root's
+            while (!st.empty()) {
+                const uint32_t y = st.back();
+                st.pop_back();
+                if (y < T) { B.idx.push_back(y); continue; }
+                if (y != x) B.pool.push_back(y);
+                st.push_back(N[y].child_r);
+                st.push_back(N[y].child_l);
+            }
+            const uint32_t parent = N[x].parent;
+            B.build(0, B.idx.size(), x);
+            rebuilt[x].parent = parent;
+            ++roots;
+            nodes += B.idx.size() - 1;
+        }
+        N = rebuilt.data();
+        fprintf(stderr, "bottom: %zu subtrees of <= %u leaves rebuilt, %zu internal nodes\n", roots, K, nodes);
     }
     const float* tri = reinterpret_cast<const float*>(tb.data());
     const float* rays = reinterpret_cast<const float*>(rb.data());
