@@ -73,6 +73,8 @@ def lib():
                                 ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]
         L.orc_trace_ex.restype = ctypes.c_int
         L.orc_trace_ex.argtypes = L.orc_trace.argtypes + [u32p, u32p]
+        L.orc_walk_tree.restype = ctypes.c_int
+        L.orc_walk_tree.argtypes = [ctypes.c_uint32, ctypes.c_uint32] + [u32p] * 11
         L.orc_camera_reference.argtypes = [ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]
         L.orc_sample_texture.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, u32p]
         L.orc_fnv1a64.restype = ctypes.c_uint64
@@ -181,6 +183,31 @@ def build(scene: Scene, wvp, morton_mode=MORTON_CPUTESTS, delta_mode=DELTA_CLZ64
     if rc != 0:
         raise RuntimeError(f"orc_build failed ({rc})")
     return out
+
+
+WT_KEPT, WT_SAH, WT_HALVES, WT_HALVES_BUDGET = 0, 1, 2, 3
+WT_INFO_DTYPE = np.dtype([("how", "<u4"), ("axis", "<u4"), ("plane", "<u4"), ("level", "<u4")])
+
+
+def walk_tree(nodes: np.ndarray, K: int = 512):
+    """orc_walk_tree on a built tree (NODE_DTYPE: parent, child_l, child_r and the boxes are read): the walk-only
+    tree of DESIGN.md 6c in the same layout (code and index as the built tree's), and for every internal node k
+    how it came about (WT_KEPT / WT_SAH / WT_HALVES / WT_HALVES_BUDGET: halves for the level budget's sake), the axis and plane of an SAH split and its level below its
+    subtree's root."""
+    n = (len(nodes) + 1) // 2
+    cols = [np.ascontiguousarray(nodes[f], np.uint32) for f in ("parent", "child_l", "child_r")]
+    boxes = [np.ascontiguousarray(nodes[f], np.float32) for f in ("bb_min", "bb_max")]
+    par, cl, cr = (np.full(2 * n - 1, 0xFFFFFFFF, np.uint32) for _ in range(3))
+    bmin, bmax = np.zeros((2 * n - 1, 3), np.float32), np.zeros((2 * n - 1, 3), np.float32)
+    info = np.zeros(max(n - 1, 1), np.uint32)
+    rc = lib().orc_walk_tree(n, K, *map(_p, cols + boxes + [par, cl, cr, bmin, bmax, info]))
+    if rc != 0:
+        raise RuntimeError(f"orc_walk_tree failed ({rc})")
+    out = np.array(nodes, dtype=NODE_DTYPE)
+    out["parent"], out["child_l"], out["child_r"], out["bb_min"], out["bb_max"] = par, cl, cr, bmin, bmax
+    how = np.zeros(n - 1, WT_INFO_DTYPE)
+    how["how"], how["axis"], how["plane"], how["level"] = info & 15, (info >> 4) & 15, (info >> 8) & 255, info >> 16
+    return out, how
 
 
 def trace(scene: Scene, nodes: np.ndarray, wvp, wv, W, H, bounces, row_begin=0, row_end=None,

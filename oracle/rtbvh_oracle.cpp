@@ -410,6 +410,184 @@ int orc_build(const orc_scene* s, const float wvp[16], int morton_mode, int delt
 
 }  // extern "C"
 
+// ---- the walk-only tree's rebuild, sequential and recursive in plain fp32 ----------------
+namespace {
+
+struct WtModel {
+    uint32_t T, K;
+    const float *lmin, *lmax;                 // the leaves' boxes, by sorted index
+    uint32_t *parent, *cl, *cr, *info;        // the outputs, reference layout (leaf j, internal T + k)
+    float *bmin, *bmax;
+    uint32_t lo = 0;                          // the first sorted leaf of the subtree in hand
+    int budget = 0;
+    std::vector<uint32_t> perm, tmp;          // position -> leaf - lo
+};
+
+inline int wt_clog2(uint32_t m) {
+    int l = 0;
+    while ((1ull << l) < m) ++l;
+    return l;
+}
+inline float wt_half_area(const float* l, const float* h) {
+    const float dx = h[0] - l[0], dy = h[1] - l[1], dz = h[2] - l[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+inline int wt_bin_of(float l, float h, float cmin, float sc) {
+    return (int)fminf(fmaxf((0.5f * (l + h) - cmin) * sc, 0.f), 15.f);   // fminf / fmaxf drop a NaN: bin 0
+}
+
+// the range of positions [pa, pb] at `level` below its subtree's root becomes internal node `id`
+// (0 .. T-2); false: past the 64 levels of a root path
+bool wt_range(WtModel& w, uint32_t pa, uint32_t pb, int level, uint32_t id) {
+    if (level >= 64) return false;
+    const uint32_t m = pb - pa + 1, T = w.T;
+    float bl[3] = {INFINITY, INFINITY, INFINITY}, bh[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool fin = true;
+    for (uint32_t p = pa; p <= pb; p++) {
+        const float *l = w.lmin + 3 * (size_t)(w.lo + w.perm[p]), *h = w.lmax + 3 * (size_t)(w.lo + w.perm[p]);
+        for (int x = 0; x < 3; x++) {
+            bl[x] = fminf(bl[x], l[x]);
+            bh[x] = fmaxf(bh[x], h[x]);
+            const float c = 0.5f * (l[x] + h[x]);
+            cmin[x] = fminf(cmin[x], c);
+            cmax[x] = fmaxf(cmax[x], c);
+            fin = fin && std::fabs(l[x]) < INFINITY && std::fabs(h[x]) < INFINITY;
+        }
+    }
+    for (int x = 0; x < 3; x++) { w.bmin[3 * (size_t)(T + id) + x] = bl[x]; w.bmax[3 * (size_t)(T + id) + x] = bh[x]; }
+    bool ok[3];
+    float sc[3];
+    for (int x = 0; x < 3; x++) {
+        ok[x] = cmax[x] > cmin[x];
+        sc[x] = ok[x] ? 16.f / (cmax[x] - cmin[x]) : 0.f;
+    }
+    uint32_t nl = m / 2, how = ORC_WT_HALVES;
+    int axis = 0, plane = 0;
+    if (m > 2 && fin && level < 32 && (ok[0] || ok[1] || ok[2])) {
+        float best = INFINITY;
+        uint32_t best_nl = 0;
+        bool found = false;
+        for (int x = 0; x < 3; x++) {
+            if (!ok[x]) continue;
+            float binl[16][3], binh[16][3];
+            uint32_t cnt[16];
+            for (int b = 0; b < 16; b++) {
+                cnt[b] = 0;
+                for (int q = 0; q < 3; q++) { binl[b][q] = INFINITY; binh[b][q] = -INFINITY; }
+            }
+            for (uint32_t p = pa; p <= pb; p++) {
+                const size_t j = w.lo + w.perm[p];
+                const int b = wt_bin_of(w.lmin[3 * j + x], w.lmax[3 * j + x], cmin[x], sc[x]);
+                cnt[b]++;
+                for (int q = 0; q < 3; q++) {
+                    binl[b][q] = fminf(binl[b][q], w.lmin[3 * j + q]);
+                    binh[b][q] = fmaxf(binh[b][q], w.lmax[3 * j + q]);
+                }
+            }
+            for (int pl = 0; pl < 15; pl++) {
+                float Ll[3] = {INFINITY, INFINITY, INFINITY}, Lh[3] = {-INFINITY, -INFINITY, -INFINITY};
+                float Rl[3] = {INFINITY, INFINITY, INFINITY}, Rh[3] = {-INFINITY, -INFINITY, -INFINITY};
+                uint32_t nL = 0, nR = 0;
+                for (int b = 0; b < 16; b++) {
+                    if (!cnt[b]) continue;
+                    float *dl = b <= pl ? Ll : Rl, *dh = b <= pl ? Lh : Rh;
+                    (b <= pl ? nL : nR) += cnt[b];
+                    for (int q = 0; q < 3; q++) { dl[q] = fminf(dl[q], binl[b][q]); dh[q] = fmaxf(dh[q], binh[b][q]); }
+                }
+                if (!nL || !nR) continue;
+                const float c = wt_half_area(Ll, Lh) * (float)nL + wt_half_area(Rl, Rh) * (float)nR;
+                if (c < INFINITY && c < best) {   // (strictly: a tie stays with the lower axis, then plane)
+                    best = c; best_nl = nL; axis = x; plane = pl; found = true;
+                }
+            }
+        }
+        if (found && level + 1 + wt_clog2(std::max(best_nl, m - best_nl)) > w.budget) {
+            how = ORC_WT_HALVES_BUDGET;   // (a side would no longer fit below as halves)
+        } else if (found) {
+            how = ORC_WT_SAH;
+            nl = best_nl;
+            uint32_t a = pa, b = pa + nl;   // the stable partition
+            for (uint32_t p = pa; p <= pb; p++) {
+                const size_t j = w.lo + w.perm[p];
+                const bool left = wt_bin_of(w.lmin[3 * j + axis], w.lmax[3 * j + axis], cmin[axis], sc[axis]) <= plane;
+                w.tmp[left ? a++ : b++] = w.perm[p];
+            }
+            for (uint32_t p = pa; p <= pb; p++) w.perm[p] = w.tmp[p];
+        }
+    }
+    w.info[id] = how | (uint32_t)axis << 4 | (uint32_t)plane << 8 | (uint32_t)level << 16;
+    const uint32_t la = pa, lb = pa + nl - 1, ra = pa + nl, rb = pb;
+    const uint32_t l = la == lb ? w.lo + w.perm[la] : T + w.lo + lb;   // an internal left child: its last position
+    const uint32_t r = ra == rb ? w.lo + w.perm[ra] : T + w.lo + ra;   // ... a right child: its first
+    w.cl[T + id] = l;
+    w.cr[T + id] = r;
+    w.parent[l] = w.parent[r] = T + id;
+    if (la != lb && !wt_range(w, la, lb, level + 1, w.lo + lb)) return false;
+    if (ra != rb && !wt_range(w, ra, rb, level + 1, w.lo + ra)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int orc_walk_tree(uint32_t T, uint32_t K, const uint32_t* parent, const uint32_t* cl, const uint32_t* cr,
+                             const float* bb_min, const float* bb_max, uint32_t* out_parent, uint32_t* out_cl,
+                             uint32_t* out_cr, float* out_bb_min, float* out_bb_max, uint32_t* info) {
+    if (T < 2 || K < 2) return 1;
+    const uint32_t total = 2 * T - 1, NONE = 0xFFFFFFFFu;
+    // the leaf range of every built node, children before parents (the leaves are in sorted order)
+    std::vector<uint32_t> first(total), last(total), order, st{T};
+    for (uint32_t j = 0; j < T; j++) first[j] = last[j] = j;
+    while (!st.empty()) {
+        const uint32_t x = st.back();
+        st.pop_back();
+        if (x < T || x >= total || order.size() >= T - 1) return 2;
+        order.push_back(x);
+        if (cl[x] >= T) st.push_back(cl[x]);
+        if (cr[x] >= T) st.push_back(cr[x]);
+    }
+    if (order.size() != T - 1) return 2;
+    for (size_t q = order.size(); q-- > 0;) {
+        const uint32_t x = order[q];
+        first[x] = first[cl[x]];
+        last[x] = last[cr[x]];
+        if (last[cl[x]] + 1 != first[cr[x]]) return 2;
+    }
+    WtModel w{T, K, bb_min, bb_max, out_parent, out_cl, out_cr, info, out_bb_min, out_bb_max};
+    w.perm.resize(K);
+    w.tmp.resize(K);
+    for (uint32_t j = 0; j < T; j++) {
+        for (int x = 0; x < 3; x++) {
+            out_bb_min[3 * (size_t)j + x] = bb_min[3 * (size_t)j + x];
+            out_bb_max[3 * (size_t)j + x] = bb_max[3 * (size_t)j + x];
+        }
+        out_cl[j] = out_cr[j] = NONE;
+    }
+    out_parent[T] = NONE;
+    for (uint32_t x : order) {
+        const uint32_t n = last[x] - first[x] + 1;
+        if (n > K) {   // of the top: kept (its children's parent links here, a subtree root's too)
+            out_cl[x] = cl[x];
+            out_cr[x] = cr[x];
+            out_parent[cl[x]] = out_parent[cr[x]] = x;
+            for (int q = 0; q < 3; q++) {
+                out_bb_min[3 * (size_t)x + q] = bb_min[3 * (size_t)x + q];
+                out_bb_max[3 * (size_t)x + q] = bb_max[3 * (size_t)x + q];
+            }
+            info[x - T] = ORC_WT_KEPT;
+            continue;
+        }
+        if (parent[x] != NONE && last[parent[x]] - first[parent[x]] + 1 <= K) continue;   // inside a subtree
+        int depth = 0;   // of the subtree's root in the built tree
+        for (uint32_t e = parent[x]; e != NONE && depth < 64; e = parent[e]) ++depth;
+        w.lo = first[x];
+        w.budget = std::max(std::min(32 + wt_clog2(K), 64 - depth), wt_clog2(n));
+        for (uint32_t i = 0; i < n; i++) w.perm[i] = i;
+        if (!wt_range(w, 0, n - 1, 0, x - T)) return 3;
+    }
+    return 0;
+}
+
 namespace {
 
 struct Tri { f3 p[3]; f3 nrm[3]; float uv[3][2]; };

@@ -119,6 +119,19 @@ int orc_trace_ex(const orc_scene* s, const orc_node* nodes, uint32_t n,
  * RayTraceRender.hlsl:22-26 (include/rtbvh.h rtbvh_texture). */
 void orc_sample_texture(const orc_texture* t, float u, float v, float out[4]);
 
+/* ---- the walk-only tree -------------------------------------- */
+/* The model of build.hip's k_wt_select / k_wt_rebuild, written from DESIGN.md 6c: sequential, recursive, plain
+ * fp32 (no waves, no ordered-integer keys, no atomics).  In: the built tree in orc_node's layout (leaves [0, T) in
+ * sorted order, internal node k at T + k, the root at T; bb_min / bb_max (2T-1) x 3 floats) and K, the largest
+ * subtree that is rebuilt (the library's: 512).  Out, in the same layout: the walk tree's links and boxes, and for
+ * internal node k info[k] = how | axis << 4 | plane << 8 | level << 16 (axis, plane: of an ORC_WT_SAH split;
+ * level: below its subtree's root; ORC_WT_HALVES_BUDGET: halves because the cheapest plane broke the level budget).  Returns 0; 1: T < 2; 2: not a tree over sorted leaves; 3: a root path of
+ * more than 64 levels below a subtree's root. */
+enum { ORC_WT_KEPT = 0, ORC_WT_SAH = 1, ORC_WT_HALVES = 2, ORC_WT_HALVES_BUDGET = 3 };
+int orc_walk_tree(uint32_t T, uint32_t K, const uint32_t* parent, const uint32_t* child_l, const uint32_t* child_r,
+                  const float* bb_min, const float* bb_max, uint32_t* out_parent, uint32_t* out_child_l,
+                  uint32_t* out_child_r, float* out_bb_min, float* out_bb_max, uint32_t* info);
+
 /* ---- misc ------------------------------------------------------------------ */
 /* XMMatrixLookAtLH * XMMatrixPerspectiveFovLH as Graphics.cpp:44-53 (row-vector
  * convention, float32, libm sinf/cosf).  wvp and wv row-major 4x4. */

@@ -1683,9 +1683,10 @@ __global__ __launch_bounds__(BLOCK) void k_export(BuildArgs a, RefNode* __restri
 // ---- the walk-only tree (rtbvh_internal.h WalkTree) --------------------------------------
 // A second tree over the same sorted leaves for the certified 4-wide bounce walk, which is exact on any tree
 // whose boxes contain its leaves: the built tree's top as it is, and every maximal subtree of <= WT_K leaves
-// rebuilt top-down by binned SAH (tools/collapse_study.cpp REBUILD=bottom is the same rule on the CPU: WT_NB
-// centroid bins an axis, cost area(L) nL + area(R) nR, the lowest axis and then plane on a tie, halves where no
-// plane separates the centroids).  Such a subtree is a run of sorted leaves [lo, hi] whose internal nodes are the
+// rebuilt top-down by binned SAH (WT_NB centroid bins an axis, cost area(L) nL + area(R) nR, the lowest axis and
+// then plane on a tie, halves where no plane separates the centroids; oracle/rtbvh_oracle.cpp orc_walk_tree is the
+// same rule step for step on the CPU and the tests compare the two word for word; tools/collapse_study.cpp
+// REBUILD=bottom is the study's looser form of it).  Such a subtree is a run of sorted leaves [lo, hi] whose internal nodes are the
 // ids [lo, hi] but one: its root (lo or hi) keeps its id, the others come from (lo, hi) by Karras' own rule on
 // the subtree's new leaf order -- a left child is named by its last position, a right child by its first.
 // The leaves keep their sorted index (LEAF_BIT | j), so hit keys and leaf records are the built tree's.
@@ -1716,7 +1717,7 @@ __device__ __forceinline__ float wt_first(float x) {   // lane 0's value, in eve
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
 }
 __device__ __forceinline__ int wt_bin(float lo, float hi, float cl, float sc) {
-    return (int)fminf(fmaxf((0.5f * (lo + hi) - cl) * sc, 0.f), (float)(WT_NB - 1));   // (NaN: the last bin)
+    return (int)fminf(fmaxf((0.5f * (lo + hi) - cl) * sc, 0.f), (float)(WT_NB - 1));   // (NaN: bin 0, fmaxf drops it)
 }
 
 // One thread per internal node: a node of more than WT_K leaves is of the top (copied), a node of <= WT_K under

@@ -116,7 +116,9 @@ RTBVH_HD inline MtNodeRho mt_node_prep(const MtNodeK& k, float E) {
 RTBVH_HD inline float mt_node_eval(const MtNodeRho& n, float t) { return fmaf(n.s, t, n.c); }
 RTBVH_HD inline float mt_node_rho(const MtNodeK& k, float E, float t) { return mt_node_eval(mt_node_prep(k, E), t); }
 
-// the global edge bound of a triangle: max(|e1|, |e2|) rounded up (inf for a non-finite triangle).  Below
+// the global edge bound of a triangle: max(|e1|, |e2|) rounded up.  inf for an infinite component, and for a NaN in
+// both edges; a NaN in one edge alone is dropped by fmaxf and the bound is the other edge's (no ray test accepts
+// a triangle with a NaN vertex, so no margin is ever taken from it: DESIGN.md 5m).  Below
 // 2^-50 a component's square can underflow (to a denormal that rounds by more than the 2^-20, or to 0): then
 // the bound is sqrt(3) max |component|, rounded up, plus the smallest denormal (E >= |e| must hold
 // for the tiniest triangles too)

@@ -4,7 +4,11 @@ findCollision (tests/ray_walk_ref.py).  Every comparison is bit-exact; frames ar
 
 Scenes: Rect (12 triangles), Test (1,952: the one-workgroup build), Image_Test (3,072: the one-workgroup sort,
 the multi-kernel rest), rt.synthetic(20000) (radix sort, several refit workgroups, crossing nodes), the crossing
-scene of tests/deep_scenes.py (the grouped refit's fallback), and scenes of 1 and 2 triangles."""
+scene of tests/deep_scenes.py (the grouped refit's fallback), and scenes of 1 and 2 triangles.
+
+Section 8 runs the QNode model of tests/test_gpu_parity.py (entries, grids, containment, the E code exactly, the tcap
+code) on live contexts after every transition that rewrites the QNodes, and the walk-only tree of the same state
+against its model (tests/test_walk_tree_gpu.py)."""
 import functools
 
 import numpy as np
@@ -15,7 +19,9 @@ from oracle import lib as orc
 from tests import deep_scenes as ds
 from tests import ray_walk_ref as rw
 from tests.conftest import load_scene_fixture
+from tests.test_gpu_parity import check_qnodes_live
 from tests.test_query_gpu import assert_genuine, assert_hits_equal, random_rays, tiny_scene
+from tests.test_walk_tree_gpu import scaled_thirds, walk_tree_equals_the_model, with_positions
 
 pytestmark = pytest.mark.gpu
 W = H = 64
@@ -417,6 +423,138 @@ def test_query_after_async_refit_sees_the_new_tree():
         assert_hits_equal(before.cpu().numpy().view(rt.HIT_DTYPE).reshape(-1), want0, "before the refit")
         assert_hits_equal(after.cpu().numpy().view(rt.HIT_DTYPE).reshape(-1), want1, "after the refit")
         assert not np.array_equal(before.cpu().numpy(), after.cpu().numpy())
+
+
+# ---------------------------------------------------------------- 8. the QNodes after every transition
+MK, CERT = rt.FLAG_MULTI_KERNEL_BUILD, rt.FLAG_CERTIFIED
+QN_KINDS = {"one workgroup": (1000, 0), "records": (2049, MK), "node boxes": (2049, CERT | MK)}
+
+
+def qn_states(n):
+    """(scene, positions) of the three geometries: as made; a third of the triangles scaled up tenfold and a third
+    down (E rises and falls); and from there the other way and further."""
+    s0 = rt.synthetic(n, seed=0x5EED0004)
+    P1 = scaled_thirds(s0, 10.0, 0.1)
+    s1 = with_positions(s0, P1)
+    P2 = scaled_thirds(s1, 0.03, 40.0)
+    return s0, (s1, P1), (with_positions(s0, P2), P2)
+
+
+def qn_cameras():
+    """The reference camera, and one whose WVP has another scale (every clip-space edge three times as long)."""
+    wvp, wv = rt.camera_reference(W, H)
+    return (wvp, wv), ((np.asarray(wvp, np.float32) * np.float32(3)).astype(np.float32), wv)
+
+
+def assert_rose_and_fell(before, after):
+    (r0, e0), (r1, e1) = before, after
+    both = np.intersect1d(r0, r1)
+    assert (e1[both] > e0[both]).any() and (e1[both] < e0[both]).any()
+
+
+def walk_tree_now(c, s, cam, bounces=1):
+    """The walk tree the next trace makes (RTBVH_WALK_TREE=1, a certified context) against its model."""
+    builds = c.stats()["walk_tree_builds"]
+    c.trace(W, H, bounces)
+    st = c.stats()
+    assert st["walk_tree_used"] == 1 and st["walk_tree_builds"] == builds + 1
+    walk_tree_equals_the_model(c, s, cam[0])
+
+
+@pytest.mark.parametrize("kind", list(QN_KINDS))
+def test_qnodes_after_refits_and_a_rebuild(kind, monkeypatch):
+    """The built tree's QNodes against their model after update + refit (E rises and falls), a second refit from
+    there, a camera-only refit under a WVP of another scale, and the rebuild that follows: on a one-workgroup
+    tree, a multi-kernel records tree and a certified context's node-box tree (there also the walk tree)."""
+    monkeypatch.setenv("RTBVH_WALK_TREE", "1")
+    n, flags = QN_KINDS[kind]
+    s0, (s1, P1), (s2, P2) = qn_states(n)
+    cam, cam2 = qn_cameras()
+    with rt.Context(device=0, flags=flags) as c:
+        c.set_scene(s0)
+        c.set_camera(*cam)
+        c.build()
+        built = check_qnodes_live(c, s0, cam)
+        if flags & CERT:
+            walk_tree_now(c, s0, cam)   # (one of the old geometry: the refit has to drop it)
+        c.update_vertices(P1)
+        c.refit()
+        first = check_qnodes_live(c, s1, cam)
+        assert_rose_and_fell(built, first)
+        if flags & CERT:
+            walk_tree_now(c, s1, cam)
+        c.update_vertices(P2)
+        c.refit()
+        second = check_qnodes_live(c, s2, cam)
+        assert_rose_and_fell(first, second)
+        c.set_camera(*cam2)
+        c.refit()
+        scaled = check_qnodes_live(c, s2, cam2)
+        assert scaled[1][0] > second[1][0]   # (the root's E: the longest edge, three times as long)
+        c.build()
+        check_qnodes_live(c, s2, cam2)
+
+
+def test_qnodes_after_graph_replays(monkeypatch):
+    """CERTIFIED | GRAPH: the captured frame replayed under a moved camera, then after a vertex update; the QNodes
+    and, from a trace outside the graph, the walk tree of each state; then a rebuild."""
+    monkeypatch.setenv("RTBVH_WALK_TREE", "1")
+    s0, (s1, P1), _ = qn_states(2049)
+    cam, cam2 = qn_cameras()
+    with rt.Context(device=0, flags=CERT | MK | rt.FLAG_GRAPH) as c:
+        c.set_scene(s0)
+        c.set_camera(*cam)
+        c.compute_bvh(W, H, 1)
+        c.compute_bvh(W, H, 1)
+        assert c.stats()["graph_captures"] == 1
+        built = check_qnodes_live(c, s0, cam)
+        c.set_camera(*cam2)
+        c.compute_bvh(W, H, 1)
+        assert c.stats()["graph_captures"] == 1   # a replay
+        moved = check_qnodes_live(c, s0, cam2)
+        assert moved[1][0] > built[1][0]   # (the root's E: the longest edge, three times as long)
+        walk_tree_now(c, s0, cam2)
+        c.update_vertices(P1)
+        c.compute_bvh(W, H, 1)
+        assert c.stats()["graph_captures"] == 1
+        check_qnodes_live(c, s1, cam2)
+        walk_tree_now(c, s1, cam2)
+        c.build()
+        check_qnodes_live(c, s1, cam2)
+
+
+@pytest.mark.parametrize("kind", ["one workgroup", "records"])
+def test_qnodes_derived_on_a_plain_context(kind, monkeypatch):
+    """A plain context (the reference-order walks: its build quantizes no node): the QNodes the first certified
+    query derives, those after a refit, the walk tree a certified trace then makes of that tree, and a rebuild."""
+    monkeypatch.setenv("RTBVH_WALK_TREE", "1")
+    n, flags = QN_KINDS[kind]
+    s0, (s1, P1), _ = qn_states(n)
+    cam, _ = qn_cameras()
+    with rt.Context(device=0, flags=flags) as c:
+        c.set_scene(s0)
+        c.set_camera(*cam)
+        c.build()
+        tree = c.read_bvh()
+        o, d = random_rays(tree, 256)
+        rays = rt.make_rays(o, d)
+        tris = rw.clip_triangles(s0.vertices, s0.indices, cam[0])
+        assert_hits_equal(c.query(rays, rt.QUERY_CERTIFIED), rw.walk(tree, tris, o, d), "certified")
+        derived = check_qnodes_live(c, s0, cam)
+        c.set_flags(flags | CERT)
+        walk_tree_now(c, s0, cam)
+        c.set_flags(flags)
+        c.update_vertices(P1)
+        c.refit()
+        refitted = check_qnodes_live(c, s1, cam)
+        assert_rose_and_fell(derived, refitted)
+        tris = rw.clip_triangles(s1.vertices, s1.indices, cam[0])
+        assert_hits_equal(c.query(rays, rt.QUERY_CERTIFIED), rw.walk(c.read_bvh(), tris, o, d), "after the refit")
+        c.set_flags(flags | CERT)
+        walk_tree_now(c, s1, cam)
+        c.set_flags(flags)
+        c.build()
+        check_qnodes_live(c, s1, cam)
 
 
 # ---------------------------------------------------------------- 7. the C++ host's --animate mode

@@ -550,11 +550,12 @@ def _denormal_scene(seed=5):
 
 
 def _edge_bound_np(e1, e2):
-    """margin.h mt_edge_bound in numpy float32 (the device's operation order)."""
+    """margin.h mt_edge_bound in numpy float32 (the device's operation order; fmaxf drops a NaN, so np.fmax: a
+    NaN in one edge alone leaves the other edge's bound)."""
     sq = lambda e: (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
-    with np.errstate(invalid="ignore", under="ignore"):
-        m = np.sqrt(np.maximum(sq(e1), sq(e2))) * np.float32(1 + 2.0 ** -20)
-        mx = np.max(np.abs(np.concatenate([e1, e2], 1)), axis=1)
+    with np.errstate(invalid="ignore", under="ignore", over="ignore"):
+        m = np.sqrt(np.fmax(sq(e1), sq(e2))) * np.float32(1 + 2.0 ** -20)
+        mx = np.fmax.reduce(np.abs(np.concatenate([e1, e2], 1)), axis=1)
         tiny = (mx * np.float32(1.7320510)) * np.float32(1 + 2.0 ** -20) + np.float32(2.0 ** -149)
     out = np.where(mx < np.float32(2.0 ** -50), tiny, m)
     return np.where(np.isnan(m), np.float32(np.inf), out).astype(np.float32)
@@ -586,16 +587,31 @@ def test_qnodes_contain_the_exact_boxes(scene):
     check_qnodes(s, cam, tiny=scene == "tiny triangles")
 
 
-def check_qnodes(s, cam, tiny=False, flags=0):
-    """test_qnodes_contain_the_exact_boxes' checks on scene s under camera cam = (wvp, wv), built by a context with
-    `flags` (tests/test_deep_trees_gpu.py runs them on its own scene)."""
-    with rt.Context(device=0, flags=flags) as c:
-        c.set_scene(s)
-        c.set_camera(*cam)
-        c.build()
-        nodes = c.read_bvh()
-        q = c.read_qnodes()
-    T = s.num_tris
+def leaf_edge_bounds(s, wvp, nodes):
+    """margin.h mt_edge_bound of every sorted leaf's clip-space triangle (rtbvh_device.h xform_point's operation
+    order, no FMA: numpy float32), and the same for every triangle in the scene's order."""
+    wvp = np.asarray(wvp, np.float32).reshape(4, 4)
+    P = s.vertices[:, :3].astype(np.float32)
+    with np.errstate(under="ignore", over="ignore", invalid="ignore"):
+        clip = ((P[:, 0:1] * wvp[0] + P[:, 1:2] * wvp[1]) + P[:, 2:3] * wvp[2]) + wvp[3]
+        tri = clip[s.indices.reshape(-1, 3), :3]
+        e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+        eb = _edge_bound_np(e1, e2)
+    T = (len(nodes) + 1) // 2
+    return eb[nodes["index"][:T] // 3], (eb, e1, e2)
+
+
+def check_qnode_array(q, nodes, leaf_e, finite=True):
+    """test_qnodes_contain_the_exact_boxes' checks on one QNode array in slots (rtbvh_read_qnodes' or
+    rtbvh_read_walk_qnodes') against the binary tree it was made from: `nodes` in the oracle's layout (leaves
+    [0, T), internal k at T + k, the root at T; parent, child_l, child_r, bb_min, bb_max are read) -- the built
+    tree, or the model's walk tree (oracle.lib.walk_tree) -- and `leaf_e`, the sorted leaves' edge bounds.  At
+    every QNode the 4-wide walk reads from the root's slot on: the four entry words and the E code exactly,
+    power-of-two minimal grids, containment, the tcap code against condition (C).  finite=False (scenes with
+    non-finite or huge corners): a node may be without a grid if an entry's corners are past 2^100 or not finite
+    -- its entry words are still compared -- and a NaN corner is contained by anything.  Returns (the internal
+    nodes 0 .. T-2 whose QNodes were read, every internal node's E code as the leaves' bounds give it)."""
+    T = (len(nodes) + 1) // 2
     assert q.shape == (2 * T - 1, 16)
     cl, cr, par = nodes["child_l"], nodes["child_r"], nodes["parent"]
 
@@ -613,14 +629,16 @@ def check_qnodes(s, cam, tiny=False, flags=0):
     shifts = np.arange(4, dtype=np.uint32) * 8
     lo = ((q[:, 6:9, None] >> shifts) & 255).astype(np.float32)   # [k, axis, c]
     hi = ((q[:, 9:12, None] >> shifts) & 255).astype(np.float32)
-    dlo = org[:, :, None] + lo * scl[:, :, None]   # q * step exact; one rounding in the add
-    dhi = org[:, :, None] + hi * scl[:, :, None]
+    with np.errstate(all="ignore"):   # (the words of a node that is never read, or without a grid, mean nothing)
+        dlo = org[:, :, None] + lo * scl[:, :, None]   # q * step exact; one rounding in the add
+        dhi = org[:, :, None] + hi * scl[:, :, None]
     top = np.full((T - 1, 3), -np.inf, dtype=np.float32)   # the exact max corner of the four boxes
     bmin, bmax = nodes["bb_min"], nodes["bb_max"]
 
     def area(g):   # fp32, the kernel's operation order
-        d = (bmax[g] - bmin[g]).astype(np.float32)
-        return (d[0] * d[1] + d[1] * d[2]) + d[2] * d[0]
+        with np.errstate(all="ignore"):
+            d = (bmax[g] - bmin[g]).astype(np.float32)
+            return (d[0] * d[1] + d[1] * d[2]) + d[2] * d[0]
 
     def greedy(x):
         ents = [cl[x], cr[x]]
@@ -644,40 +662,41 @@ def check_qnodes(s, cam, tiny=False, flags=0):
     while todo:
         k = todo.pop()
         read.append(k)
+        assert len(read) < T, "the entries do not form a tree"
         todo.extend(g - T for g in greedy(T + k) if g is not None and g >= T)
     read = np.array(sorted(read))
-    assert len(read) < 0.5 * (T - 1) or T < 3000   # (the greedy collapse expands about two in three)
-    assert (scl[read, 0] != 0).all()   # every node of these scenes has a finite grid
-    m, e = np.frexp(scl[read])
+    grid = scl[read, 0] != 0
+    if finite:
+        assert grid.all()   # every node of these scenes has a finite grid
+    m, e = np.frexp(scl[read][grid])
     assert (m == 0.5).all(), "grid steps are powers of two"
-    for k in read:
+    for k, has_grid in zip(read, grid):
         gc = greedy(T + k)
         ids = [0xFFFFFFFF if g is None else ((0x80000000 | g) if g < T else slot(g)) for g in gc]
         assert list(q[k, 12:16]) == ids, k
+        ents = [g for g in gc if g is not None]
+        if not has_grid:   # allowed only where quantize_axis must refuse: a corner or an extent past 2^100, or NaN
+            with np.errstate(all="ignore"):
+                l, h = bmin[ents].min(0), bmax[ents].max(0)   # (numpy's min / max keep a NaN)
+                assert not (np.abs(np.concatenate([l, h, h - l])) <= np.float32(2.0 ** 100)).all(), k
+            continue
         for cidx, g in enumerate(gc):
             if g is None:
                 continue
-            assert (dlo[k, :, cidx] <= nodes["bb_min"][g]).all(), (k, cidx)
-            assert (dhi[k, :, cidx] >= nodes["bb_max"][g]).all(), (k, cidx)
-            top[k] = np.maximum(top[k], nodes["bb_max"][g])
+            if finite:
+                assert (dlo[k, :, cidx] <= bmin[g]).all(), (k, cidx)
+                assert (dhi[k, :, cidx] >= bmax[g]).all(), (k, cidx)
+            else:
+                assert ((dlo[k, :, cidx] <= bmin[g]) | np.isnan(bmin[g])).all(), (k, cidx)
+                assert ((dhi[k, :, cidx] >= bmax[g]) | np.isnan(bmax[g])).all(), (k, cidx)
+            top[k] = np.fmax(top[k], bmax[g])
+    read_all, read = read, read[grid]
     # the step is the smallest power of two (>= 2^-120) whose grid reaches the boxes' max
-    half = scl / np.float32(2)
-    reach = org + np.float32(255) * half   # product exact, one rounding in the add
+    with np.errstate(all="ignore"):
+        half = scl / np.float32(2)
+        reach = org + np.float32(255) * half   # product exact, one rounding in the add
     assert ((reach < top) | (half < np.float32(2.0 ** -120)))[read].all(), "grid step not minimal"
-    # the margin codes: E_k = max over node k's leaves of margin.h mt_edge_bound on the clip-space
-    # triangle (rtbvh_device.h xform_point's operation order, no FMA: numpy float32), rounded up
-    wvp = np.asarray(cam[0], np.float32).reshape(4, 4)
-    P = s.vertices[:, :3].astype(np.float32)
-    with np.errstate(under="ignore"):
-        clip = ((P[:, 0:1] * wvp[0] + P[:, 1:2] * wvp[1]) + P[:, 2:3] * wvp[2]) + wvp[3]
-    tri = clip[s.indices.reshape(-1, 3), :3]
-    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
-    eb = _edge_bound_np(e1, e2)
-    if tiny:   # the bound is >= the exact 2-norm at every scale
-        n64 = lambda e: np.sqrt((e.astype(np.float64) ** 2).sum(1))
-        assert (eb.astype(np.float64) >= np.maximum(n64(e1), n64(e2))).all()
-        assert (eb < 2.0 ** -100).sum() > 500
-    leaf_e = eb[nodes["index"][:T] // 3]
+    # the margin codes: E_k = max over node k's leaves of the edge bound, rounded up
     node_e = np.zeros(T - 1, np.float32)
     order = []   # internal nodes, children before parents
     st = [T]
@@ -703,6 +722,34 @@ def check_qnodes(s, cam, tiny=False, flags=0):
     assert np.where(tcap >= 0, tcn <= tcap, tcn < 0).all()
     big = (tcap >= 1) & (tcap < 2.0 ** 127)   # (the 16-bit code truncates: within 2^-8; 0.999 of mt_margin)
     assert (tcn[big] >= 0.99 * 0.999 * tcap[big]).all()
+    return read_all, want_e
+
+
+def check_qnodes_live(c, s, cam, tiny=False):
+    """test_qnodes_contain_the_exact_boxes' checks on the tree and the QNodes a live context holds now, for the
+    scene as it is now: s with the current vertices, cam = (wvp, wv) the current camera.  Builds nothing.
+    Returns (the internal nodes whose QNodes were read, every internal node's E code)."""
+    nodes = c.read_bvh()
+    q = c.read_qnodes()
+    T = s.num_tris
+    leaf_e, (eb, e1, e2) = leaf_edge_bounds(s, cam[0], nodes)
+    if tiny:   # the bound is >= the exact 2-norm at every scale
+        n64 = lambda e: np.sqrt((e.astype(np.float64) ** 2).sum(1))
+        assert (eb.astype(np.float64) >= np.maximum(n64(e1), n64(e2))).all()
+        assert (eb < 2.0 ** -100).sum() > 500
+    read, codes_e = check_qnode_array(q, nodes, leaf_e)
+    assert len(read) < 0.5 * (T - 1) or T < 3000   # (the greedy collapse expands about two in three)
+    return read, codes_e
+
+
+def check_qnodes(s, cam, tiny=False, flags=0):
+    """check_qnodes_live on scene s under camera cam = (wvp, wv), built by a context with `flags`
+    (tests/test_deep_trees_gpu.py runs them on its own scene)."""
+    with rt.Context(device=0, flags=flags) as c:
+        c.set_scene(s)
+        c.set_camera(*cam)
+        c.build()
+        check_qnodes_live(c, s, cam, tiny)
 
 
 def _general_box(lo, hi):

@@ -1,12 +1,19 @@
 """tools/collapse_study.cpp REBUILD=bottom (the CPU study behind the walk-only tree): the tool builds,
 and a tree whose subtrees of <= BOT_K leaves were rebuilt is still a tree over the same leaves -- the counted walk
-finds the same hit for every ray and tests about as many triangles -- whatever BOT_K."""
+finds the same hit for every ray and tests about as many triangles -- whatever BOT_K.  Below it, the rebuild's model
+in the CPU oracle (oracle.lib.walk_tree), which the GPU tests compare the library's walk tree with."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+import raytracebvh_amd as rt
+from oracle import lib as orc
+from tests import hostile_scenes as hs
+from tests import walk_tree_scenes as ws
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -37,3 +44,189 @@ def test_bottom_rebuild_keeps_the_leaves_and_the_hits(study):
         assert got["greedy"]["hits"] == base["greedy"]["hits"] and got["sah_opt"]["hits"] == base["sah_opt"]["hits"]
         assert abs(got["greedy"]["leaf_tests"] - base["greedy"]["leaf_tests"]) < 0.25 * base["greedy"]["leaf_tests"]
     assert study(REBUILD="bottom")[1].count("<= 512 leaves") == 1   # BOT_K's default
+
+
+# ---------------------------------------------------------------- the rebuild's model (oracle.lib.walk_tree)
+# DESIGN.md 6c's rebuild restated sequentially in the CPU oracle; tests/test_walk_tree_gpu.py compares the library's
+# walk tree with it word for word.  Here: the model against what 6c says, on trees the oracle builds.
+
+
+def model_of(s, wvp=ws.IDENTITY[0], K=512):
+    built = ws.oracle_tree(s, wvp)
+    wt, how = orc.walk_tree(built, K)
+    return built, wt, how
+
+
+def split_of(wt, x):
+    """(leaves under the left child, leaves under the right child) of internal node x, as sorted-leaf sets."""
+    def leaves(c):
+        T = (len(wt) + 1) // 2
+        out, st = [], [c]
+        while st:
+            y = st.pop()
+            if y < T:
+                out.append(int(y))
+            else:
+                st.extend((wt["child_l"][y], wt["child_r"][y]))
+        return sorted(out)
+    return leaves(wt["child_l"][x]), leaves(wt["child_r"][x])
+
+
+@pytest.mark.parametrize("case", ["syn 3", "syn 513", "syn 2049", "syn 6000 K=64", "lattice", "planar", "identical",
+                                  "hostile", "syn 700 K=2"])
+def test_model_is_a_tree_over_the_same_leaves(case):
+    K = 512
+    wvp = rt.camera_reference(64, 64)[0]
+    if case.startswith("syn"):
+        s = rt.synthetic(int(case.split()[1]), seed=ws.SEED)
+        if "K=" in case:
+            K = int(case.split("=")[1])
+    elif case == "lattice":
+        s, wvp = ws.lattice_scene(8, 8, 16, seed=3), ws.IDENTITY[0]
+    elif case == "planar":
+        s, wvp = ws.lattice_scene(32, 32, 1, seed=3), ws.IDENTITY[0]
+    elif case == "identical":
+        s = ws.identical_scene()
+    else:
+        s = hs.hostile("all").scene
+    built, wt, how = model_of(s, wvp, K)
+    T = s.num_tris
+    depth = ws.check_tree_over_the_same_leaves(wt, built, K)
+    first, last, _ = ws.leaf_ranges(built)
+    size = last[T:] - first[T:] + 1
+    np.testing.assert_array_equal(how["how"] == orc.WT_KEPT, size > K)
+    assert depth.max() < 64
+    if case == "identical":
+        assert (how["how"][size <= K] == orc.WT_HALVES).all()
+    if case == "syn 700 K=2":   # subtrees of two leaves: nothing to choose
+        assert not (how["how"] == orc.WT_SAH).any()
+
+
+def test_model_square_block_ties_go_to_x():
+    """2 x 2 x 1 identical triangles in boxes of 0.5^3, step 2: centroids at two x and two y, none apart in z.
+    Every x plane splits 2 | 2 into boxes of 0.5 x 2.5 x 0.5 at (1.25 + 1.25 + 0.25) * 2 * 2 = 11, every y plane
+    into boxes of 2.5 x 0.5 x 0.5 at the same 11: the lowest axis, then the lowest plane."""
+    s = ws.lattice_scene(2, 2, 1, step=2.0)
+    built, wt, how = model_of(s)
+    assert tuple(how[0]) == (orc.WT_SAH, 0, 0, 0)
+    T = 4
+    x_of = built["bb_min"][:T, 0]
+    l, r = split_of(wt, T)
+    assert sorted(x_of[l]) == [1.0, 1.0] and sorted(x_of[r]) == [3.0, 3.0]
+    assert l == sorted(l) and (how["how"][1:] == orc.WT_HALVES).all() and (how["level"][1:] == 1).all()
+    # the stable partition and Karras' rule: the left child is named by its last position (1), the right by its first
+    assert wt["child_l"][T] == T + 1 and wt["child_r"][T] == T + 2
+    assert (wt["child_l"][T + 1], wt["child_r"][T + 1]) == (l[0], l[1])
+    assert (wt["child_l"][T + 2], wt["child_r"][T + 2]) == (r[0], r[1])
+
+
+def test_model_row_takes_the_lowest_of_the_equal_planes():
+    """1 x 4 in x, step 1, boxes of 0.5^3: bins 0, 5, 10, 15 (16/3 a unit).  Planes 0-4 split 1 | 3 at 0.75 +
+    2.75 * 3 = 9, planes 5-9 split 2 | 2 at 1.75 * 2 * 2 = 7, planes 10-14 cost 9 again: plane 5."""
+    s = ws.lattice_scene(4, 1, 1)
+    built, wt, how = model_of(s)
+    assert tuple(how[0]) == (orc.WT_SAH, 0, 5, 0)
+    l, r = split_of(wt, 4)
+    x_of = built["bb_min"][:4, 0]
+    assert sorted(x_of[l]) == [1.0, 2.0] and sorted(x_of[r]) == [3.0, 4.0]
+
+
+def test_model_planar_scene_uses_two_axes():
+    built, wt, how = model_of(ws.lattice_scene(32, 32, 1, seed=3))
+    sah = how["how"] == orc.WT_SAH
+    assert sah.sum() > 500 and set(how["axis"][sah]) == {0, 1}
+
+
+def test_model_nonfinite_ranges_split_in_halves():
+    s = hs.hostile("all").scene
+    built, wt, how = model_of(s)
+    T = s.num_tris
+    first, last, _ = ws.leaf_ranges(wt)
+    bad = ~(np.isfinite(built["bb_min"][:T]).all(1) & np.isfinite(built["bb_max"][:T]).all(1))
+    assert bad.any()
+    n_bad = np.concatenate([[0], np.cumsum(bad)])
+    for k in range(T - 1):   # (a rebuilt node's range of positions holds the leaves [first, last] in some order)
+        if how["how"][k] != orc.WT_KEPT and n_bad[last[T + k] + 1] - n_bad[first[T + k]] > 0:
+            assert how["how"][k] == orc.WT_HALVES, k
+    assert (how["how"] == orc.WT_SAH).any()
+
+
+def chain_tree(depth, boxes):
+    """A synthetic built tree: a chain of `depth` internal nodes, each with one leaf on the left, above a balanced
+    subtree over the last len(boxes) - depth leaves."""
+    T = len(boxes)
+    nodes = np.zeros(2 * T - 1, orc.NODE_DTYPE)
+    nodes["parent"] = 0xFFFFFFFF
+    nodes["bb_min"][:T], nodes["bb_max"][:T] = boxes[:, 0], boxes[:, 1]
+    nxt = [T]
+
+    def link(x, l, r):
+        nodes["child_l"][x], nodes["child_r"][x] = l, r
+        nodes["parent"][l] = nodes["parent"][r] = x
+
+    def balanced(a, b):   # leaves [a, b] -> node id
+        if a == b:
+            return a
+        x = nxt[0]
+        nxt[0] += 1
+        m = (a + b) // 2
+        link(x, balanced(a, m), balanced(m + 1, b))
+        return x
+
+    x = T
+    for j in range(depth):
+        nxt[0] = x + 1
+        if j + 1 < depth:
+            link(x, j, x + 1)
+            x += 1
+        else:
+            link(x, j, balanced(depth, T - 1))
+    _, _, order = ws.leaf_ranges(nodes)
+    for y in reversed(order):
+        l, r = nodes["child_l"][y], nodes["child_r"][y]
+        nodes["bb_min"][y] = np.minimum(nodes["bb_min"][l], nodes["bb_min"][r])
+        nodes["bb_max"][y] = np.maximum(nodes["bb_max"][l], nodes["bb_max"][r])
+    return nodes
+
+
+def test_model_level_budget_under_a_deep_root():
+    """A subtree of 16 leaves (K = 16) whose SAH splits peel one leaf at a time (boxes at 2^i), at depth 0 and at
+    depth 60: there the budget is max(min(32 + 4, 64 - 60), 4) = 4 levels, which only halves-like splits keep."""
+    def boxes(n):
+        x = np.float32(2.0) ** np.arange(n, dtype=np.float32)
+        lo = np.stack([x, np.ones(n, np.float32), np.ones(n, np.float32)], 1)
+        return np.stack([lo, lo + np.float32(0.5)], 1)
+
+    nodes = chain_tree(60, boxes(76))
+    wt, how = orc.walk_tree(nodes, 16)
+    depth = ws.check_tree_over_the_same_leaves(wt, nodes, 16)
+    T = 76
+    sub = how["how"] != orc.WT_KEPT
+    assert (how["how"] == orc.WT_KEPT).sum() == 60 and sub.sum() == 15
+    assert depth[T:].max() == 63 and how["level"][sub].max() == 3
+    assert (how["how"] == orc.WT_HALVES_BUDGET).any()
+    # the same 16 boxes under the root itself: 41 levels to spend, and the splits peel
+    b = boxes(76)[60:]
+    shallow = chain_tree(1, np.concatenate([b[:1], b]))   # (one chain node above: depth 1)
+    wt2, how2 = orc.walk_tree(shallow, 16)
+    ws.check_tree_over_the_same_leaves(wt2, shallow, 16)
+    assert how2["level"][how2["how"] != orc.WT_KEPT].max() > 3 and not (how2["how"] == orc.WT_HALVES_BUDGET).any()
+
+
+def test_model_costs_less_than_halves():
+    for n, K in ((2049, 512), (6000, 512), (6000, 64)):
+        built, wt, how = model_of(rt.synthetic(n, seed=ws.SEED), rt.camera_reference(64, 64)[0], K)
+        got, halves = ws.summed_area(wt), ws.halves_area(built, K)
+        print(f"T = {n}, K = {K}: summed half area {got:.6g} (model) against {halves:.6g} (halves)")
+        assert got < 0.9 * halves
+
+
+def test_model_budget_scene_reaches_the_budget():
+    """The scene the GPU comparison uses for the level budget: its peeled subtree's root is 31 levels deep, planes
+    are refused for the budget's sake, and every root path stays within 64 levels."""
+    s = ws.budget_scene()
+    built, wt, how = model_of(s)
+    depth = ws.check_tree_over_the_same_leaves(wt, built)
+    T = s.num_tris
+    assert (how["how"] == orc.WT_HALVES_BUDGET).any() and how["level"].max() == 32
+    assert depth[T:].max() + 1 <= 64

@@ -1,16 +1,21 @@
 """The walk-only tree: the built tree's top with every maximal subtree of <= 512 leaves rebuilt by
 binned SAH, which the certified 4-wide bounce walk reads from the third trace of a build on (RTBVH_WALK_TREE=1: from
 the first).  Its structure (rtbvh_read_walk_qnodes walked on the host), its frames (bit for bit the reference
-order's), its visit counts and the policy that makes, keeps and drops it."""
+order's), its visit counts and the policy that makes, keeps and drops it; and every QNode the walk can reach
+compared, entry word for entry word and edge code for edge code, with the rebuild's sequential model in the CPU
+oracle (oracle.lib.walk_tree, written from DESIGN.md 6c) under the built tree's own QNode checks."""
 import numpy as np
 import pytest
 
 import raytracebvh_amd as rt
+from oracle import lib as orc
 from tests import deep_scenes as ds
 from tests import hostile_scenes as hs
+from tests import walk_tree_scenes as ws
 from tests.cert_scenes import camera
 from tests.conftest import load_scene_fixture
-from tests.test_gpu_parity import _edge_bound_np, _huge_scene
+from tests.test_gpu_parity import _edge_bound_np, _huge_scene, check_qnode_array, leaf_edge_bounds
+from tests.walk_tree_scenes import identical_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,16 +31,6 @@ def cert_ctx(monkeypatch, knob="1", flags=CERT):
     else:
         monkeypatch.setenv("RTBVH_WALK_TREE", knob)
     return rt.Context(device=0, flags=flags)
-
-
-def identical_scene(n=600):
-    """n copies of one triangle: every centroid equal, so every range splits in halves."""
-    base = rt.synthetic(n, seed=SEED)
-    v = base.vertices.copy()
-    idx = base.indices.reshape(-1, 3)
-    for k in range(3):
-        v[idx[:, k]] = v[idx[0, k]]
-    return rt.Scene(v, base.indices, base.mat_indices, base.materials)
 
 
 def fixture_scene(name):
@@ -150,6 +145,110 @@ def test_structure(T, monkeypatch):
         np.testing.assert_array_equal(q[sl], q2[sl])
         np.testing.assert_array_equal(q[sl], q3[sl])
         reach.extend(e for e in map(int, q[sl, 12:16]) if e != NONE and not (e & LEAF))
+
+
+def walk_tree_equals_the_model(c, s, wvp, finite=True):
+    """The walk-tree QNodes a context holds (its last trace made or used them) against the model of the rebuild run on
+    the context's own built tree and the scene as it is now: check_qnode_array from the root's slot -- at every
+    slot the walk can reach the four entry words and the E code exactly, and the grid, containment and tcap
+    properties of the built tree's QNodes.  Returns (built tree, model tree, how each node came about, nodes read)."""
+    nodes, q = c.read_bvh(), c.read_walk_qnodes()
+    wt, how = orc.walk_tree(nodes)
+    ws.check_tree_over_the_same_leaves(wt, nodes)
+    read, _ = check_qnode_array(q, wt, leaf_edge_bounds(s, wvp, nodes)[0], finite)
+    return nodes, wt, how, read
+
+
+def scaled_thirds(s, big=10.0, small=0.1):
+    """Positions with every third triangle scaled by `big` about its first vertex and every third by `small` (each
+    vertex belongs to one triangle in the synthetic scenes): edge bounds that rise and fall, boxes that move."""
+    P = s.vertices[:, :3].astype(np.float32).copy()
+    idx = s.indices.reshape(-1, 3)
+    f = np.ones(len(idx), np.float32)
+    f[0::3], f[1::3] = big, small
+    for k in (1, 2):
+        P[idx[:, k]] = P[idx[:, 0]] + f[:, None] * (P[idx[:, k]] - P[idx[:, 0]])
+    return np.ascontiguousarray(P)
+
+
+def with_positions(s, P):
+    v = s.vertices.copy()
+    v[:, :3] = P
+    return rt.Scene(v, s.indices, s.mat_indices, s.materials)
+
+
+MK = rt.FLAG_MULTI_KERNEL_BUILD
+MODEL_CASES = ["syn513", "syn2049", "syn6000", "lattice", "planar", "identical", "nonfinite", "fan", "crossing",
+               "budget", "syn2049 refitted"]
+
+
+@pytest.mark.parametrize("case", MODEL_CASES)
+def test_rebuild_equals_the_model(case, monkeypatch):
+    """The smallest scenes that reach each branch of k_wt_select / k_wt_rebuild: one top node over two subtrees of a
+    one-workgroup build (513); several top levels, subtrees near 512 leaves and ranges above and below a wave's 64
+    (2,049 and 6,000, multi-kernel builds); exact costs that tie on all three axes (a lattice of 8 x 8 x 16
+    identical triangles at unit spacing under the identity camera) and on two (a planar one); no plane at all
+    (identical triangles); halves under non-finite corners; the deep-tree scenes (the fan: one subtree of 15
+    levels; the crossing scene: 65 subtrees of up to 29 levels, none of them deep enough in the built tree to run out
+    of levels); a subtree root 31 levels deep whose planes peel, so that the level budget refuses some and the 32-level
+    limit others (walk_tree_scenes.budget_scene); a refitted tree."""
+    cam, flags, finite, moved = rt.camera_reference(64, 64), CERT | MK, True, None
+    if case.startswith("syn"):
+        n = int(case.split()[0][3:])
+        s = rt.synthetic(n, seed=SEED)
+        if n == 513:
+            flags = CERT   # the one-workgroup build: the top node's edge bound is k_build_small's
+        if "refitted" in case:
+            moved = scaled_thirds(s)
+    elif case == "lattice":
+        s, cam = ws.lattice_scene(8, 8, 16, seed=3), ws.IDENTITY
+    elif case == "planar":
+        s, cam = ws.lattice_scene(32, 32, 1, seed=3), ws.IDENTITY
+    elif case == "identical":
+        s = identical_scene()
+    elif case == "nonfinite":
+        s, cam, finite = hs.hostile("nonfinite").scene, hs.camera("reference"), False
+    elif case == "fan":
+        s, cam = ds.fan_scene(), camera("A")
+    elif case == "crossing":
+        s, cam, flags = ds.crossing_scene(), ds.crossing_camera(), CERT
+    else:
+        s, cam = ws.budget_scene(), ws.IDENTITY
+    with cert_ctx(monkeypatch, "1", flags) as c:
+        c.set_scene(s)
+        c.set_camera(*cam)
+        c.build()
+        if moved is not None:
+            c.trace(64, 64, 1)   # (a walk tree of the old geometry first)
+            c.update_vertices(moved)
+            c.refit()
+            s = with_positions(s, moved)
+        c.trace(64, 64, 1)
+        st = c.stats()
+        assert st["walk_tree_used"] == 1 and st["walk_tree_builds"] == (2 if moved is not None else 1)
+        nodes, wt, how, read = walk_tree_equals_the_model(c, s, cam[0], finite)
+    T = s.num_tris
+    first, last, _ = ws.leaf_ranges(wt)
+    size = (last - first + 1)[T:]
+    kept, sah, budget = (how["how"] == k for k in (orc.WT_KEPT, orc.WT_SAH, orc.WT_HALVES_BUDGET))
+    halves = ~kept & ~sah
+    print(f"{case}: T = {T}, {kept.sum()} kept, {sah.sum()} SAH, {halves.sum()} halves ({budget.sum()} for the "
+          f"level budget), {len(read)} QNodes read, deepest level {how['level'].max()}")
+    if case == "syn513":
+        assert kept.sum() == 1 and (how["level"][~kept] == 0).sum() == 2
+    if case in ("syn2049", "syn6000", "syn2049 refitted"):
+        assert kept.sum() > 2 and size[~kept].max() > 256
+        assert (sah & (size > 64)).any() and (sah & (size < 64) & (size > 2)).any()
+    if case == "lattice":
+        assert set(how["axis"][sah]) == {0, 1, 2}
+    if case == "planar":
+        assert set(how["axis"][sah]) == {0, 1}
+    if case == "identical":
+        assert not sah.any()
+    if case == "nonfinite":
+        assert sah.any() and (halves & (size > 2)).any()
+    if case == "budget":
+        assert budget.any() and how["level"].max() == 32
 
 
 def frames(s, cam, W, H, bounces, monkeypatch, flags=CERT, multi_kernel=False):
