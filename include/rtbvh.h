@@ -1089,6 +1089,74 @@ rtbvh_status rtbvh_overlap_host(rtbvh_ctx* ctx, const rtbvh_box* boxes, uint64_t
  * RTBVH_ERR_NOT_READY before any counting box query. */
 rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
+/* ---- region queries: every triangle within up to six planes the caller chose -----------------------
+ * (No reference equivalent.)  A region is the intersection of up to six half-spaces: a frustum, an oriented box, a
+ * single half-space (a clip or section plane), a slab between two parallel planes -- a slab of zero thickness
+ * lists the triangles one layer of a slicer cuts.  The planes live in the space the BVH was built in, as the other
+ * queries' inputs.  Plane i is {nx, ny, nz, d}; point x is on its inner side when n.x + d <= 0.  An unused plane is
+ * all zeros: its value is +0 everywhere, so it holds everywhere and there is no count field.
+ * The value of plane P = {n, d} at x, fp32 without contraction:
+ *     t_k = (n_k == 0) ? +0 : fl(n_k * x_k)   for k = x, y, z  (a zero component is skipped: 0 * inf makes no NaN)
+ *     s(P, x) = fl(fl(fl(t_x + t_y) + t_z) + d)
+ * For a box [lo, hi] the near corner takes lo_k where n_k >= 0 and hi_k elsewhere, and m(P, box) is s there; the far
+ * corner is the opposite choice, and M(P, box) is s there.
+ * Membership is defined on the floats of the triangle's leaf record -- a = p0, e1 = fl(p1 - p0), e2 = fl(p2 - p0)
+ * and the leaf box [lo, hi] -- independently of the tree and of the walk.  Triangle x is a member of the region iff
+ *  (B) for every plane i: m(P_i, leaf box) <= 0.  A NaN fails it.
+ *  (V) with RTBVH_REGION_TRIANGLE only: with v0 = a, v1 = clamp(fl(a + e1)), v2 = clamp(fl(a + e2)), where
+ *      clamp(q)_k = fmaxf(lo_k, fminf(hi_k, q_k)) (the clearance queries' clamping into the triangle's own box), for
+ *      every plane i: s(P_i, v0) <= 0 || s(P_i, v1) <= 0 || s(P_i, v2) <= 0.
+ *      (V) is the usual conservative frustum test on the vertices: no single plane has all three vertices outside.
+ *      It is NOT an exact triangle-polytope intersection -- a triangle outside the region near an edge or a corner
+ *      of it can pass -- but for the slab {n, d}, {-n, -d} it is exact: some vertex on each side.
+ * The list is empty, and there is no walk, for a region with a non-finite float among its 24.
+ * The set is exact, whatever the tree: rounded products and sums are monotone, so for nested boxes and a vertex
+ * inside them m(node) <= m(leaf) <= s(v) <= M(leaf) <= M(node); a walk that enters a child iff m <= 0 on every plane
+ * reaches every member, and a subtree whose box has M <= 0 on every plane holds members only and is taken whole --
+ * its leaves are one run of the sort order -- while no leaf box of the tree holds a NaN.  The cost
+ * follows the region's boundary, not its contents.
+ * Order, output (CSR: dev_offsets, dev_ids) and `capacity` are rtbvh_overlap_async's, word for word: each list
+ * ascends by the member's position in the last build's sort order, dev_offsets[n] is the true total, and nothing is
+ * ever written past dev_ids + capacity. */
+typedef struct rtbvh_region {
+    float plane[6][4]; /* plane i: {nx, ny, nz, d} */
+} rtbvh_region;        /* 96 B: six 16-B words */
+enum {
+    RTBVH_REGION_COUNT = 1u << 2,    /* count regions, ids, steps and accepts for rtbvh_region_counts (slower) */
+    RTBVH_REGION_TRIANGLE = 1u << 3, /* members must also pass the vertex test (V) above */
+    RTBVH_REGION_SIZES = 1u << 4,    /* write dev_offsets only; dev_ids may be NULL */
+    RTBVH_REGION_FILL = 1u << 5,     /* dev_offsets is INPUT (from a SIZES call for the same regions, tree and
+                                        TRIANGLE bit): write the ids only */
+    RTBVH_REGION_NO_ACCEPT = 1u << 6 /* never take a subtree whole: descend to every leaf.  The same bytes; for
+                                        A/B runs and tests */
+    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG.  There is no SORT mode: a region has no
+       centre. */
+};
+/* n regions at dev_regions (16-B aligned), n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` ids at
+ * dev_ids (device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the context stream).
+ * Mode 0 runs the sizes pass, a scan of the offsets on the device and the fill pass in one call, with no host round
+ * trip; RTBVH_REGION_SIZES then RTBVH_REGION_FILL is the two-call form.  A FILL over any non-decreasing offsets
+ * writes region k's ids only inside [dev_offsets[k], min(dev_offsets[k + 1], capacity)), whether an id comes from a
+ * leaf or from a subtree taken whole: foreign offsets truncate lists, they never make a write go astray.
+ * The first region query after a build or a refit runs one pass over the leaf records on its stream (is there a
+ * NaN in a leaf box?); the region queries of that tree on other streams are ordered behind it on the device.
+ * Everything else follows rtbvh_overlap_async one for one: the tree forms read (and the topology's leaf ranges in
+ * both), the waits, the place among the other queries, growing the scan's block sums, n == 0, the errors
+ * (RTBVH_ERR_NOT_READY before a build and after a vertex update; RTBVH_ERR_INVALID_ARG for NULL regions or offsets
+ * with n > 0, NULL ids with capacity > 0 outside RTBVH_REGION_SIZES, bad mode bits, n >= 2^31) and the stack limit:
+ * a walk that hits rtbvh_config.stack_limit loses that subtree's ids, both passes alike, and the next synchronising
+ * call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_region_async(rtbvh_ctx* ctx, const rtbvh_region* dev_regions, uint64_t n, uint64_t* dev_offsets,
+                                uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream): offsets (n + 1) and ids are
+ * host arrays; ids receives min(total, capacity) entries.  With RTBVH_REGION_FILL, offsets is read. */
+rtbvh_status rtbvh_region_host(rtbvh_ctx* ctx, const rtbvh_region* regions, uint64_t n, uint64_t* offsets,
+                               uint32_t* ids, uint64_t capacity, uint32_t mode);
+/* The last RTBVH_REGION_COUNT query (waits for it): regions, ids (the true total, counted once), internal-node steps,
+ * leaf steps, subtrees taken whole (these three summed over the passes the call ran) and the ids that came from
+ * them (counted once).  Its own words.  RTBVH_ERR_NOT_READY before any counting region query. */
+rtbvh_status rtbvh_region_counts(rtbvh_ctx* ctx, uint64_t out[6]);
+
 /* ---- signed-distance queries: the nearest triangle, and on which side of the surface the point is ----
  * (No reference equivalent.)  Same points (rtbvh_point: {point.xyz, max_dist2}) and the same space as the
  * closest-point queries above.  For each point: rtbvh_nearest's fields, and the number of triangles crossed by one

@@ -56,6 +56,7 @@ EXPORTS = [
     "rtbvh_collide_async", "rtbvh_collide_host", "rtbvh_collide_counts",
     "rtbvh_cross_async", "rtbvh_cross_host", "rtbvh_cross_first_async", "rtbvh_cross_first_host", "rtbvh_cross_counts",
     "rtbvh_clearance_async", "rtbvh_clearance_host", "rtbvh_clearance_counts",
+    "rtbvh_region_async", "rtbvh_region_host", "rtbvh_region_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -108,6 +109,11 @@ CROSS_SORT, CROSS_COUNT, CROSS_SIZES, CROSS_FILL = 2, 4, 16, 32   # RTBVH_CROSS_
 CLEARANCE_DTYPE = np.dtype([("point_q", "<f4", (3,)), ("dist2", "<f4"), ("point_x", "<f4", (3,)), ("tri", "<u4")])
 assert CLEARANCE_DTYPE.itemsize == 32
 CLEARANCE_SORT, CLEARANCE_COUNT = 2, 4   # RTBVH_CLEARANCE_*
+# rtbvh_region (96 B): a region query's up to six planes {nx, ny, nz, d}, inner side n.x + d <= 0, an unused plane
+# all zeros; its lists hold triangle ids (uint32)
+REGION_DTYPE = np.dtype([("plane", "<f4", (6, 4))])
+assert REGION_DTYPE.itemsize == 96
+REGION_COUNT, REGION_TRIANGLE, REGION_SIZES, REGION_FILL, REGION_NO_ACCEPT = 4, 8, 16, 32, 64   # RTBVH_REGION_*
 
 
 class Config(ctypes.Structure):
@@ -300,6 +306,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_clearance_async": (i32, [vp, vp, u64, ctypes.c_float, vp, u32, vp]),
         "rtbvh_clearance_host": (i32, [vp, vp, u64, ctypes.c_float, vp, u32]),
         "rtbvh_clearance_counts": (i32, [vp, vp]),
+        "rtbvh_region_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
+        "rtbvh_region_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
+        "rtbvh_region_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

@@ -358,6 +358,12 @@ struct rtbvh_ctx {
     bool collide_counted = false;            // the self-collision queries' count block holds a RTBVH_COLLIDE_COUNT query's counts
     bool cross_counted = false;              // the triangle queries' count block holds a RTBVH_CROSS_COUNT query's counts
     bool clearance_counted = false;          // the clearance queries' count block holds a RTBVH_CLEARANCE_COUNT query's counts
+    bool region_counted = false;             // the region queries' count block holds a RTBVH_REGION_COUNT query's counts
+    // The region queries' leaf-NaN word (d_qscratch + QUERY_LEAF_NAN_AT) is a product of the built tree, like a bin
+    // set: written on the stream of the first region query of a tree (nan_epoch: its bins_epoch), with ev_nan
+    // recorded behind it for the region queries of that tree on other streams
+    uint64_t nan_epoch = 0;
+    Event ev_nan;
 };
 
 namespace {
@@ -3355,6 +3361,140 @@ rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* c, uint64_t out[4]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CLEARANCE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+// ---- region queries --------------------------------------------------------------------------------------
+// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain (no sort: a region has no centre):
+// [the leaf-NaN word, once a tree], then [sizes + scan], then [fill], all on the caller's stream.  Its count block
+// is QUERY_REGION_AT.
+rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, uint64_t n, uint64_t* dev_offsets,
+                                uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    constexpr uint32_t ALL = RTBVH_REGION_COUNT | RTBVH_REGION_TRIANGLE | RTBVH_REGION_SIZES | RTBVH_REGION_FILL |
+                             RTBVH_REGION_NO_ACCEPT;
+    constexpr uint32_t BOTH = RTBVH_REGION_SIZES | RTBVH_REGION_FILL;
+    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "region: bad mode bits");
+    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "region: 2^31 regions or more");
+    const bool sizes = !(mode & RTBVH_REGION_FILL), fill = !(mode & RTBVH_REGION_SIZES);
+    static_assert(sizeof(rtbvh_region) == 96, "region query layout");
+    if (n == 0) {
+        if (!dev_offsets || !sizes) return RTBVH_OK;
+        HIPC(c, hipSetDevice(c->cfg.device));
+        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+        return RTBVH_OK;
+    }
+    if (!dev_regions || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "region: NULL regions or offsets");
+    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "region: NULL ids");
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "region before build");
+    if (c->stale) return fail_stale(c, "region");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool count = (mode & RTBVH_REGION_COUNT) != 0, tri = (mode & RTBVH_REGION_TRIANGLE) != 0;
+    const uint32_t N = (uint32_t)n;
+    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
+    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
+    if (!c->ev_nan) HIPC(c, hipEventCreateWithFlags(c->ev_nan.out(), hipEventDisableTiming));
+    if (sizes && !c->d_qscan.has(scan_sums_words(N))) {
+        // (as rtbvh_overlap_async: earlier queries scan in the old buffer)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
+    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    uint32_t* nan_word = c->d_qscratch + QUERY_LEAF_NAN_AT;
+    if (c->nan_epoch != c->bins_epoch) {   // the first region query of this tree writes the word, behind the tree
+        HIPC(c, hipMemsetAsync(nan_word, 0, sizeof(uint32_t), s));
+        launch_leaf_nan(c->d_leaf, c->T, nan_word, s);
+        HIPC(c, hipEventRecord(c->ev_nan, s));
+        c->nan_epoch = c->bins_epoch;
+    } else {
+        HIPC(c, hipStreamWaitEvent(s, c->ev_nan, 0));   // (written on another stream, perhaps)
+    }
+    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REGION_AT, 0, sizeof(uint64_t) * REGION_COUNT_WORDS, s));
+    RegionArgs a{};
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.rootbox = c->d_rootbox;
+    a.regions = reinterpret_cast<const float4*>(dev_regions);
+    a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
+    a.ids = dev_ids;
+    a.capacity = capacity;
+    a.n = N;
+    a.accept = !(mode & RTBVH_REGION_NO_ACCEPT);
+    a.leaf_nan = nan_word;
+    a.next = c->d_qscratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_REGION_AT);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+    if (sizes) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+        a.count_ids = true;
+        launch_region(a, false, count, tri, s);
+        scan_offsets(a.offsets, N, c->d_qscan, s);
+    }
+    if (fill) {
+        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        a.count_ids = !sizes;
+        launch_region(a, true, count, tri, s);
+    }
+    rtbvh_status st = check_launch(c, "region kernels");
+    HIPC(c, hipEventRecord(c->ev_query, s));
+    c->query_busy = true;
+    c->query_ovf = true;
+    if (count && !st) c->region_counted = true;
+    return st;
+}
+
+rtbvh_status rtbvh_region_host(rtbvh_ctx* c, const rtbvh_region* regions, uint64_t n, uint64_t* offsets, uint32_t* ids,
+                               uint64_t capacity, uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    const bool fill_only = (mode & RTBVH_REGION_FILL) != 0, sizes_only = (mode & RTBVH_REGION_SIZES) != 0;
+    if (n == 0) {   // (nothing to stage)
+        const rtbvh_status st = rtbvh_region_async(c, regions, 0, nullptr, ids, capacity, mode, nullptr);
+        if (!st && offsets && !fill_only) offsets[0] = 0;
+        return st;
+    }
+    if (n >= (1ull << 31) || !regions || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
+        !c->tree.built || c->stale)   // (the query's checks)
+        return rtbvh_region_async(c, regions, n, offsets, ids, capacity, mode, nullptr);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;   // offsets, then regions: 8- and 16-B aligned
+    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
+    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_region)));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
+    rtbvh_region* dr = reinterpret_cast<rtbvh_region*>(d + off_bytes);
+    if (hipMemcpy(dr, regions, (size_t)n * sizeof(rtbvh_region), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "region_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "region_host: upload failed");
+    DevBuf<uint32_t> dids;   // (SIZES: none)
+    if (sizes_only) capacity = 0;
+    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
+    if (capacity && fill_only)   // (offsets of another tree or other regions leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
+    TRY(rtbvh_region_async(c, dr, n, doff, dids, capacity, mode, nullptr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "region_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "region_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, "region_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+rtbvh_status rtbvh_region_counts(rtbvh_ctx* c, uint64_t out[6]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->region_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_REGION_COUNT query yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_REGION_AT, sizeof(uint64_t) * REGION_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

@@ -69,7 +69,10 @@ struct BuildArgs {
     uint32_t* xlist;          // [T] k_refit workgroup b's crossing nodes at [b * RBLOCK, ...)
     uint32_t* xcnt;           // [T / RBLOCK + 1] their counts
     float* rootbox;           // [ROOTBOX_WORDS] the root box (min xyz, max xyz), the leaves' depth range and
-                              //   [8] the largest leaf edge bound (k_zrange; margin.h)
+                              //   [8] the largest leaf edge bound (k_zrange; margin.h).  The region queries
+                              //   (trace.hip k_region) rely on words 0..5 being the root node's own box, the
+                              //   NaN-dropping union of every leaf box, exactly: they prune and take the whole
+                              //   tree on it.  No padding, no finite-only box there (as word 8 is)
     QNode* qnode;             // [2T-1] quantized 4-wide nodes in slots (rtbvh_device.h), from rec
     uint4* lfp;               // [T] leaf footprints on the primary pixel grid (rtbvh_device.h leaf_footprint)
     float* zpart;             // [ZPART * refit_blocks(T)] k_refit workgroup b's leaf depth range, edge bound
@@ -653,8 +656,43 @@ struct ClearanceArgs {
 };
 // the clearance queries' own count block, behind the triangle queries'
 constexpr uint32_t QUERY_CLEARANCE_AT = QUERY_CROSS_AT + 2 * QUERY_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_CLEARANCE_AT + 2 * QUERY_COUNT_WORDS;
 static_assert(QUERY_CLEARANCE_AT % 2 == 0, "the count block's 8-byte words");
 void launch_clearance(const ClearanceArgs& a, bool count, hipStream_t s);
+
+// ---- region queries (trace.hip k_region; rtbvh_region_async) -----------------
+// Regions (six float4 each: plane i {n.xyz, d}) on the same tree forms, OverlapArgs' CSR output: a sizes pass
+// stores region r's count at offsets[r + 1], scan_offsets makes offsets of them, a fill pass stores its ids at
+// [offsets[r], min(offsets[r + 1], capacity)).  topo is read in both tree forms: an accepted subtree's leaf range.
+struct RegionArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float* rootbox;     // BuildArgs::rootbox: [0..5] the root's own box
+    const float4* regions;    // [6n]
+    unsigned long long* offsets;    // [n + 1]: the sizes pass writes [1, n], the fill pass reads
+    uint32_t* ids;            // the fill pass: [capacity] triangle ids
+    unsigned long long capacity;
+    uint32_t n;
+    bool accept;              // take subtrees whole (not RTBVH_REGION_NO_ACCEPT) ...
+    const uint32_t* leaf_nan; // ... while this word, launch_leaf_nan's for the current tree, is 0
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_REGION_COUNT: [6] regions, ids, internal-node steps, leaf steps,
+                                    //   accepted subtrees, ids from accepts
+    bool count_ids;           // ... this pass adds the regions, ids and ids from accepts (one pass of a call does)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the region queries' own count block (six words), behind the clearance queries', and the leaf-NaN word behind it
+constexpr uint32_t REGION_COUNT_WORDS = 6;
+constexpr uint32_t QUERY_REGION_AT = QUERY_CLEARANCE_AT + 2 * QUERY_COUNT_WORDS;
+constexpr uint32_t QUERY_LEAF_NAN_AT = QUERY_REGION_AT + 2 * REGION_COUNT_WORDS;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_LEAF_NAN_AT + 2;
+static_assert(QUERY_REGION_AT % 2 == 0, "the count block's 8-byte words");
+void launch_region(const RegionArgs& a, bool fill, bool count, bool tri, hipStream_t s);
+// *word (zeroed by the caller) = 1 if any of the T leaf records holds a NaN in its box words 10..15
+void launch_leaf_nan(const float4* leaf, uint32_t T, uint32_t* word, hipStream_t s);
 
 }  // namespace rtbvh

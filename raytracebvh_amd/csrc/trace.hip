@@ -3691,6 +3691,287 @@ __global__ __launch_bounds__(BLOCK) void k_overlap_keys(const float4* __restrict
     vals[i] = i;
 }
 
+// ---- region queries (rtbvh_region_async): up to six planes in, every triangle within them out -------------------
+// k_overlap's frame and CSR protocol with a plane set for the query.  The value of plane {n, d} at x is
+// s = ((t_x + t_y) + t_z) + d with t_k = n_k == 0 ? +0 : n_k * x_k, fp32 without contraction; m and M of a box are s
+// at its near and far corners (include/rtbvh.h).  Rounded products and sums are monotone, so m(node) <= m(leaf) <=
+// s(v) <= M(leaf) <= M(node) for nested boxes and a vertex inside them:
+//  * prune: a child is entered iff m <= 0 on every plane, which every box above a (B) member passes;
+//  * accept: an internal child with M <= 0 on every plane holds members only, so its leaf range topo[child].zw is
+//    taken whole -- counted in one step, copied by the wave in the fill pass -- while no leaf box holds a NaN
+//    (*leaf_nan, k_leaf_nan: node boxes drop NaNs, so an all-NaN triangle can sit inside an accepted box).
+// Both passes walk alike (the stack limit loses the same subtrees in both).  The walk is left-first and a list is in
+// sort order, so an accepted right child behind an entered left one waits on the stack as an ordinary node: its
+// children pass the accept when it is popped.  The root's own box is the root-box words: a region that holds it takes
+// [0, T - 1] with no step at all, one that misses it has an empty list.
+// The 24 plane floats stay in registers.  The launch bounds are chosen from the instances' register counts
+// (DESIGN.md 5o): the instances without COUNT take 59-70 VGPRs and keep 7 waves per SIMD with no VGPR spilled (at 8,
+// the fill instances spill 2-15 and the C5 fill pass took 1.4 times as long); the counting ones take up to 84 and
+// keep 5.  Every instance also keeps 39-54 uniform values (pointer arguments, exec masks) in VGPR lanes, reloaded
+// inside the loop by v_readlane: no memory traffic, counted in DESIGN.md 5o.
+#ifndef RTBVH_REGION_WAVES   // (an A/B build sets another launch bound: EXTRA=-DRTBVH_REGION_WAVES=<n>)
+#define RTBVH_REGION_WAVES 7
+#endif
+#ifndef RTBVH_REGION_COUNT_WAVES
+#define RTBVH_REGION_COUNT_WAVES 5
+#endif
+constexpr uint32_t REGION_WAVES = RTBVH_REGION_WAVES, REGION_COUNT_WAVES = RTBVH_REGION_COUNT_WAVES;
+// an accepted range of up to this many ids is copied by its own lane, a longer one by the whole wave (C5 boxes at
+// ten displacements, whose ranges hold 3 ids on average: the fill pass 380 ms at 4, 388 at 0, 420 at 16;
+// profiles/region_ab.json)
+#ifndef RTBVH_REGION_LANE_COPY
+#define RTBVH_REGION_LANE_COPY 4
+#endif
+constexpr uint32_t REGION_LANE_COPY = RTBVH_REGION_LANE_COPY;
+
+__device__ __forceinline__ float plane_term(float n, float x) { return n == 0.f ? 0.f : n * x; }
+__device__ __forceinline__ float plane_at(float nx, float ny, float nz, float d, f3 x) {
+    return ((plane_term(nx, x.x) + plane_term(ny, x.y)) + plane_term(nz, x.z)) + d;
+}
+// enter: m <= 0 on every plane; inside: and M <= 0 on every plane.  A NaN fails either.
+__device__ __forceinline__ void planes_box(const float (&pl)[24], f3 lo, f3 hi, bool& enter, bool& inside) {
+    bool e = true, in = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const float nx = pl[4 * i], ny = pl[4 * i + 1], nz = pl[4 * i + 2], d = pl[4 * i + 3];
+        const bool px = nx >= 0.f, py = ny >= 0.f, pz = nz >= 0.f;
+        const float m = plane_at(nx, ny, nz, d, mk(px ? lo.x : hi.x, py ? lo.y : hi.y, pz ? lo.z : hi.z));
+        const float M = plane_at(nx, ny, nz, d, mk(px ? hi.x : lo.x, py ? hi.y : lo.y, pz ? hi.z : lo.z));
+        e &= m <= 0.f;
+        in &= M <= 0.f;
+    }
+    enter = e;
+    inside = e && in;
+}
+// (V): on every plane one of the vertices a, clamp(a + e1), clamp(a + e2) lies on the inner side
+__device__ __forceinline__ bool planes_vertices(const float (&pl)[24], f3 a, f3 e1, f3 e2, f3 lo, f3 hi) {
+    const f3 v1 = mk(fmaxf(lo.x, fminf(hi.x, a.x + e1.x)), fmaxf(lo.y, fminf(hi.y, a.y + e1.y)),
+                     fmaxf(lo.z, fminf(hi.z, a.z + e1.z)));   // (k_clearance's clamp_box)
+    const f3 v2 = mk(fmaxf(lo.x, fminf(hi.x, a.x + e2.x)), fmaxf(lo.y, fminf(hi.y, a.y + e2.y)),
+                     fmaxf(lo.z, fminf(hi.z, a.z + e2.z)));
+    bool in = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const float nx = pl[4 * i], ny = pl[4 * i + 1], nz = pl[4 * i + 2], d = pl[4 * i + 3];
+        in &= plane_at(nx, ny, nz, d, a) <= 0.f || plane_at(nx, ny, nz, d, v1) <= 0.f ||
+              plane_at(nx, ny, nz, d, v2) <= 0.f;
+    }
+    return in;
+}
+
+// FILL = false counts a region's members and stores the count at offsets[r + 1]; FILL = true stores the ids at
+// offsets[r] + i while that is below min(offsets[r + 1], capacity), as k_overlap: whatever the offsets hold, no
+// store -- a lane's own or the wave's range copy -- leaves the region's segment or the first `capacity` ids.
+template <bool FILL, bool COUNT, bool NB, bool TRI>
+__global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) void k_region(RegionArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    const bool acc_on = a.accept && *a.leaf_nan == 0u;   // (one word for the whole grid)
+    const f3 rootlo = mk(a.rootbox[0], a.rootbox[1], a.rootbox[2]), roothi = mk(a.rootbox[3], a.rootbox[4], a.rootbox[5]);
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nregions = 0, nacc = 0;
+    unsigned long long nids = 0, naccids = 0;
+    bool has = false;
+    uint32_t r = 0, cnt = 0;
+    unsigned long long pos = 0, end = 0;   // FILL: the next id's index and the end of the region's segment
+    uint32_t plo = 0, plen = 0;            // FILL: an accepted range still to copy, leaves [plo, plo + plen)
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
+    float pl[24];
+#pragma unroll
+    for (int k = 0; k < 24; k++) pl[k] = 0.f;
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th region
+            r = k;
+            const float4* src = a.regions + 6 * (size_t)r;
+            bool finite = true;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const float4 p = src[i];
+                pl[4 * i] = p.x; pl[4 * i + 1] = p.y; pl[4 * i + 2] = p.z; pl[4 * i + 3] = p.w;
+                finite &= fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY &&
+                          fabsf(p.w) < INFINITY;
+            }
+            if (COUNT && a.count_ids) nregions++;
+            bool enter = false, inside = false;
+            if (finite) {
+                if (T == 1) enter = true;   // (the leaf test alone)
+                else planes_box(pl, rootlo, roothi, enter, inside);
+            }
+            if (!enter) {   // no walk: an empty list
+                if (!FILL) a.offsets[(size_t)r + 1] = 0;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                cnt = 0;
+                if (FILL) {
+                    pos = a.offsets[r];
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+                if (T > 1 && inside && acc_on) {   // the root accepted: every leaf, no step
+                    w.sp = -1;
+                    cnt = T;
+                    if (FILL) {
+                        plo = 0;
+                        plen = T;
+                    }
+                    if (COUNT) {
+                        nacc++;
+                        if (a.count_ids) naccids += T;
+                    }
+                }
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        bool done = false;
+        if (has && w.sp < 0) {
+            done = true;   // (accepted at the claim)
+        } else if (has) {
+            const bool isleaf = (w.node & LEAF_BIT) != 0;
+            // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+            v4f q0, q1, q2, q3;
+            uint32_t cl = 0, cr = 0, lid = 0, rid = 0;   // the children as the walk keeps them, and as topo indexes them
+            if (!NB || isleaf) {
+                const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                       : reinterpret_cast<const v4f*>(a.inner + w.node);
+                q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+                pin(q0); pin(q1); pin(q2); pin(q3);
+                if (!NB && !isleaf) {
+                    const uint32_t own = __float_as_uint(q3.z);
+                    lid = __float_as_uint(q3.x);
+                    rid = __float_as_uint(q3.y);
+                    cl = child_slot(lid, own, 0);
+                    cr = child_slot(rid, own, 1);
+                }
+            } else {
+                const ChildPair ch = nbt.children(w.node);
+                cl = lid = ch.cl;
+                cr = rid = ch.cr;
+                q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+                q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+                q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+                q3 = v4f{0.f, 0.f, 0.f, 0.f};
+            }
+            if (--w.guard == 0) {
+                c.overflow++;
+                done = true;
+            } else if (isleaf) {
+                if (COUNT) c.leaf++;
+                const f3 lo = mk(q2.z, q2.w, q3.x), hi = mk(q3.y, q3.z, q3.w);
+                bool in, whole;
+                planes_box(pl, lo, hi, in, whole);   // (B) on the leaf's own box
+                if (TRI && in)
+                    in = planes_vertices(pl, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), lo, hi);
+                if (in) {
+                    if (!FILL || COUNT) cnt++;
+                    if (FILL && pos < end) {
+                        a.ids[pos] = __float_as_uint(q2.y) & ~LEAF_BIT;
+                        pos++;
+                    }
+                }
+                walk_pop(w, st);
+                done = w.sp == -1;
+            } else {
+                if (COUNT) c.internal++;
+                bool lh, li, rh, ri;
+                planes_box(pl, mk(q0.x, q0.y, q2.x), mk(q0.z, q0.w, q2.y), lh, li);
+                planes_box(pl, mk(q1.x, q1.y, q2.z), mk(q1.z, q1.w, q2.w), rh, ri);
+                const bool la = li && acc_on && !(cl & LEAF_BIT);
+                const bool ra = ri && acc_on && !(cr & LEAF_BIT) && (la || !lh);   // (behind an entered left child: later)
+                if (la || ra) {
+                    uint32_t lo = 0, len = 0;
+                    if (la) {
+                        const uint4 t = a.topo[lid];
+                        lo = t.z;
+                        len = t.w - t.z + 1;
+                    }
+                    if (ra) {   // (behind an accepted left child its range follows the left one's)
+                        const uint4 t = a.topo[rid];
+                        if (!la) lo = t.z;
+                        len += t.w - t.z + 1;
+                    }
+                    if (!FILL || COUNT) cnt += len;
+                    if (COUNT) {
+                        nacc += (la ? 1u : 0u) + (ra ? 1u : 0u);
+                        if (a.count_ids) naccids += len;
+                    }
+                    if (FILL) {
+                        plo = lo;
+                        plen = len;
+                    }
+                }
+                const bool le = lh && !la, re = rh && !ra;   // the children still to walk
+                if (!le && !re) {
+                    walk_pop(w, st);
+                } else if (le && re && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                    c.overflow++;
+                    walk_pop(w, st);
+                } else {
+                    if (le && re) {   // left first: push the right child
+                        st.store(w.sp, w.top);
+                        w.sp++;
+                        w.top = cr;
+                    }
+                    w.node = le ? cl : cr;
+                }
+                done = w.sp == -1;
+            }
+        }
+        if (FILL) {   // every lane of the wave is here: the accepted ranges of this step, the ids from word 9
+            if (plen > 0 && plen <= REGION_LANE_COPY) {
+                for (uint32_t i = 0; i < plen && pos < end; i++, pos++)
+                    a.ids[pos] = __float_as_uint(leaf[4 * (size_t)(plo + i) + 2].y) & ~LEAF_BIT;
+                plen = 0;
+            }
+            uint64_t pm = __ballot(plen > 0);
+            while (pm) {
+                const uint32_t src = (uint32_t)__ffsll((unsigned long long)pm) - 1u;
+                pm &= pm - 1;
+                const uint32_t blo = __shfl(plo, (int)src, 64), blen = __shfl(plen, (int)src, 64);
+                const unsigned long long bpos = __shfl(pos, (int)src, 64), bend = __shfl(end, (int)src, 64);
+                const unsigned long long room = bpos < bend ? bend - bpos : 0ull;
+                const uint32_t m = room < blen ? (uint32_t)room : blen;
+                for (uint32_t i = lane; i < m; i += 64)
+                    a.ids[bpos + i] = __float_as_uint(leaf[4 * (size_t)(blo + i) + 2].y) & ~LEAF_BIT;
+                if (lane == src) {
+                    pos += m;
+                    plen = 0;
+                }
+            }
+        }
+        if (done) {
+            if (!FILL) a.offsets[(size_t)r + 1] = cnt;
+            if (COUNT && a.count_ids) nids += cnt;
+            has = false;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[7] = {nregions, nids, c.internal, c.leaf, nacc, naccids, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 6; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[6]) atomicAdd(a.overflow, v[6]);
+        }
+    }
+}
+
+// *word = 1 if a leaf box (words 10..15 of a leaf record) holds a NaN; the caller zeroes it first
+__global__ __launch_bounds__(BLOCK) void k_leaf_nan(const float4* __restrict__ leaf, uint32_t T, uint32_t* __restrict__ word) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= T) return;
+    const float4 w2 = leaf[4 * (size_t)i + 2], w3 = leaf[4 * (size_t)i + 3];
+    if (w2.z != w2.z || w2.w != w2.w || w3.x != w3.x || w3.y != w3.y || w3.z != w3.z || w3.w != w3.w) *word = 1u;
+}
+
 // ---- signed-distance queries (rtbvh_signed_async): caller points in, rtbvh_nearest's fields and crossing counts out --
 // Two passes over the same walk order.  The closest-point pass is k_nearest itself, storing into the record: an
 // rtbvh_signed is an rtbvh_nearest whose last word (0 there) holds the flags.  k_signed is the ray pass on the same
@@ -4475,6 +4756,21 @@ void launch_overlap_keys(const float4* boxes, uint32_t n, const float* box, uint
                          hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_overlap_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, boxes, n, box, keys, vals);
+}
+
+void launch_region(const RegionArgs& a, bool fill, bool count, bool tri, hipStream_t s) {
+    if (a.n == 0) return;
+    // the persistent grid of the kernel's occupancy, or a workgroup per 256 regions when that is fewer
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, full = 256 * (count ? REGION_COUNT_WAVES : REGION_WAVES);
+    const uint32_t blocks = need < full ? need : full;
+    with_bools([&](auto FILL, auto COUNT, auto NB, auto TRI) {
+        hipLaunchKernelGGL((k_region<FILL, COUNT, NB, TRI>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.nb, tri);
+}
+
+void launch_leaf_nan(const float4* leaf, uint32_t T, uint32_t* word, hipStream_t s) {
+    if (T == 0) return;
+    hipLaunchKernelGGL(k_leaf_nan, dim3((T + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, leaf, T, word);
 }
 
 void launch_allhits(const AllhitsArgs& a, bool fill, bool count, hipStream_t s) {

@@ -196,6 +196,106 @@ def check_overlap_boxes(boxes, hi=None, device=None):
     return "numpy", boxes.view(_L.BOX_DTYPE).reshape(-1)
 
 
+def make_regions(planes):
+    """Packs (N, P, 4) planes {nx, ny, nz, d}, P <= 6 (one region: (P, 4)), as region queries, the planes past P
+    all zero (they hold everywhere): a torch tensor gives an (N, 24) float32 tensor on its device, anything else a
+    REGION_DTYPE array (include/rtbvh.h rtbvh_region).  A point x is inside a plane when n.x + d <= 0; the planes
+    live in the space the BVH was built in."""
+    if _is_tensor(planes):
+        import torch
+        p = planes.to(torch.float32)
+        if p.dim() == 2:
+            p = p.reshape(1, *p.shape)
+        if p.dim() != 3 or p.shape[1] > 6 or p.shape[2] != 4:
+            raise ValueError(f"make_regions: planes must be (N, P <= 6, 4), got {tuple(planes.shape)}")
+        out = torch.zeros((p.shape[0], 6, 4), dtype=torch.float32, device=p.device)
+        out[:, :p.shape[1]] = p
+        return out.reshape(-1, 24)
+    p = np.asarray(planes, np.float32)
+    if p.ndim == 2:
+        p = p.reshape(1, *p.shape)
+    if p.ndim != 3 or p.shape[1] > 6 or p.shape[2] != 4:
+        raise ValueError(f"make_regions: planes must be (N, P <= 6, 4), got {np.shape(planes)}")
+    out = np.zeros(len(p), _L.REGION_DTYPE)
+    out["plane"][:, :p.shape[1]] = p
+    return out
+
+
+def box_region(lo, hi):
+    """The axis-aligned boxes [lo, hi] ((N, 3) each, or one) as regions of six axis planes {-1, 0, 0, lo_x},
+    {1, 0, 0, -hi_x}, ...: a plane {+-1, 0, 0, -+q} evaluates x <= q and q <= x exactly, so these regions list what
+    Context.overlap lists for the boxes.  Numpy in, a REGION_DTYPE array out."""
+    a = np.asarray(lo, np.float32).reshape(-1, 3)
+    b = np.asarray(hi, np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"box_region: {a.shape} lower and {b.shape} upper corners")
+    planes = np.zeros((len(a), 6, 4), np.float32)
+    for k in range(3):
+        planes[:, 2 * k, k] = -1.0      # lo_k - x_k <= 0
+        planes[:, 2 * k, 3] = a[:, k]
+        planes[:, 2 * k + 1, k] = 1.0   # x_k - hi_k <= 0
+        planes[:, 2 * k + 1, 3] = -b[:, k]
+    return make_regions(planes)
+
+
+def slab_region(normal, d_lo, d_hi):
+    """The slabs d_lo <= n.x <= d_hi ((N, 3) normals or one, scalars or N bounds) as regions of the two planes
+    {-n, d_lo}, {n, -d_hi}; d_lo == d_hi is the plane n.x = d itself, whose REGION_TRIANGLE list holds the triangles
+    it cuts.  Numpy in, a REGION_DTYPE array out."""
+    n = np.asarray(normal, np.float32).reshape(-1, 3)
+    lo = np.broadcast_to(np.asarray(d_lo, np.float32), (len(n),))
+    hi = np.broadcast_to(np.asarray(d_hi, np.float32), (len(n),))
+    planes = np.zeros((len(n), 2, 4), np.float32)
+    planes[:, 0, :3] = -n
+    planes[:, 0, 3] = lo
+    planes[:, 1, :3] = n
+    planes[:, 1, 3] = -hi
+    return make_regions(planes)
+
+
+def frustum_planes(wvp):
+    """The six planes (6, 4) float32 -- left, right, bottom, top, near, far -- of the view volume of a row-vector
+    WVP ([x y z 1] . WVP = clip) with D3D depth: -w <= x <= w, -w <= y <= w, 0 <= z <= w, each as {n, d} with the
+    inside n.p + d <= 0.  They are planes of the WVP's input space, so they fit a context whose BVH was built with
+    an identity camera.  Computed in float64 from the matrix, rounded once."""
+    m = np.asarray(wvp, np.float64).reshape(4, 4)
+    cx, cy, cz, cw = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    return np.stack([-(cw + cx), -(cw - cx), -(cw + cy), -(cw - cy), -cz, -(cw - cz)]).astype(np.float32)
+
+
+def check_region_planes(regions, device=None):
+    """Context.region's input check: ("torch", regions) for an (N, 24) float32 contiguous CUDA tensor (on `device`
+    when given), ("numpy", REGION_DTYPE array) for a C-contiguous REGION_DTYPE array, (N, 24) float32 array or
+    (N, P <= 6, 4) float32 array (packed with make_regions); ValueError for anything else.  Calls nothing in the
+    library."""
+    if _is_tensor(regions):
+        import torch
+        if regions.dtype != torch.float32 or regions.dim() != 2 or regions.shape[1] != 24:
+            raise ValueError(f"region: regions must be an (N, 24) float32 tensor (make_regions), got "
+                             f"{tuple(regions.shape)} {regions.dtype}")
+        if not regions.is_cuda:
+            raise ValueError("region: a torch tensor of regions must be on the context's GPU (numpy arrays take the "
+                             "host path)")
+        if device is not None and regions.device.index != device:
+            raise ValueError(f"region: regions on {regions.device}, the context on device {device}")
+        if not regions.is_contiguous():
+            raise ValueError("region: regions must be contiguous")
+        return "torch", regions
+    if not isinstance(regions, np.ndarray):
+        raise ValueError("region: regions must be a torch CUDA tensor or a numpy array")
+    if regions.dtype == _L.REGION_DTYPE:
+        if regions.ndim != 1:
+            raise ValueError(f"region: a REGION_DTYPE array must be one-dimensional, got shape {regions.shape}")
+    elif regions.dtype == np.float32 and regions.ndim == 3 and regions.shape[1] <= 6 and regions.shape[2] == 4:
+        return "numpy", make_regions(regions)
+    elif regions.dtype != np.float32 or regions.ndim != 2 or regions.shape[1] != 24:
+        raise ValueError(f"region: regions must be REGION_DTYPE, (N, 24) or (N, P <= 6, 4) float32, got "
+                         f"{regions.shape} {regions.dtype}")
+    if not regions.flags["C_CONTIGUOUS"]:
+        raise ValueError("region: regions must be C-contiguous")
+    return "numpy", regions.view(_L.REGION_DTYPE).reshape(-1)
+
+
 def make_tris(vertices):
     """Packs (N, 3, 3) or (N, 9) triangle vertices {v0, v1, v2} as triangle queries: a torch tensor gives an (N, 12)
     float32 tensor on its device, anything else a TRI_DTYPE array (include/rtbvh.h rtbvh_tri).  The triangles live
@@ -882,6 +982,86 @@ class Context:
         out = np.zeros(4, np.uint64)
         self._check(_L.lib().rtbvh_overlap_counts(self._h, _L.ptr(out)))
         return dict(zip(("boxes", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+
+    # -- region queries --
+    def region(self, regions, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
+        """rtbvh_region_async / rtbvh_region_host: for each region of up to six planes every triangle whose leaf box
+        reaches the inner side of every plane and, with REGION_TRIANGLE, that has on every plane a vertex on the
+        inner side (the header's conservative vertex test; exact for a slab), as (offsets, ids) in CSR form: region
+        k's triangle ids are ids[offsets[k]:offsets[k + 1]], in the last build's sort order (read_sorted), and
+        offsets[n] is the total.
+
+        `regions`: make_regions' / box_region's / slab_region's output, or (N, P <= 6, 4) float32 planes (numpy).
+        Inputs, outputs, `capacity`, `sizes_only` and `stream` are Context.overlap's: numpy goes through the
+        synchronous host entry, a torch CUDA (N, 24) tensor to the device entry.  mode: REGION_COUNT,
+        REGION_TRIANGLE, REGION_NO_ACCEPT (REGION_SIZES and REGION_FILL are this method's to set).  ValueError for
+        a wrong shape, dtype, device or layout."""
+        kind, rg = check_region_planes(regions, getattr(self, "device", None))
+        if mode & (_L.REGION_SIZES | _L.REGION_FILL):
+            raise ValueError("region: REGION_SIZES and REGION_FILL are set by region itself")
+        if mode & ~(_L.REGION_COUNT | _L.REGION_TRIANGLE | _L.REGION_NO_ACCEPT):
+            raise ValueError(f"region: unknown mode bits {mode:#x}")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError(f"region: capacity must be a non-negative integer, got {capacity!r}")
+        if sizes_only and capacity is not None:
+            raise ValueError("region: sizes_only takes no capacity")
+        n = len(rg)
+        L = _L.lib()
+        if kind == "numpy":
+            offsets = np.zeros(n + 1, np.uint64)
+            p, o = ctypes.c_void_p(rg.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
+            if capacity is not None:
+                ids = np.zeros(int(capacity), np.uint32)
+                self._check(L.rtbvh_region_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
+                return offsets, ids[:min(int(offsets[n]), len(ids))]
+            self._check(L.rtbvh_region_host(self._h, p, n, o, None, 0, mode | _L.REGION_SIZES))
+            if sizes_only:
+                return offsets
+            ids = np.zeros(int(offsets[n]), np.uint32)
+            self._check(L.rtbvh_region_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
+                                            mode | _L.REGION_FILL))
+            return offsets, ids
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=rg.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(rg.device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(rg.device).synchronize()
+        s = ctypes.c_void_p(handle) if handle else None
+        p, o = ctypes.c_void_p(rg.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
+
+        def call(ids, m):
+            self._check(L.rtbvh_region_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
+                                             and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
+            if handle == 0:
+                self.synchronize()
+
+        if capacity is not None:
+            ids = torch.empty(int(capacity), dtype=torch.int32, device=rg.device)
+            call(ids, mode)
+            return offsets, ids
+        call(None, mode | _L.REGION_SIZES)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=rg.device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        ids = torch.empty(total, dtype=torch.int32, device=rg.device)
+        call(ids, mode | _L.REGION_FILL)
+        return offsets, ids
+
+    def region_counts(self) -> dict:
+        """rtbvh_region_counts: regions, ids (the total), internal-node steps, leaf steps and subtrees taken whole
+        (summed over the passes) and the ids that came from those subtrees, of the last REGION_COUNT query (the
+        other queries' counts are kept apart)."""
+        out = np.zeros(6, np.uint64)
+        self._check(_L.lib().rtbvh_region_counts(self._h, _L.ptr(out)))
+        return dict(zip(("regions", "ids", "internal_steps", "leaf_steps", "accepted_subtrees", "accepted_ids"),
+                        (int(v) for v in out)))
 
     # -- self-collision queries --
     def collide(self, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None, device: bool = False):
