@@ -1127,11 +1127,32 @@ enum {
     RTBVH_REGION_SIZES = 1u << 4,    /* write dev_offsets only; dev_ids may be NULL */
     RTBVH_REGION_FILL = 1u << 5,     /* dev_offsets is INPUT (from a SIZES call for the same regions, tree and
                                         TRIANGLE bit): write the ids only */
-    RTBVH_REGION_NO_ACCEPT = 1u << 6 /* never take a subtree whole: descend to every leaf.  The same bytes; for
-                                        A/B runs and tests */
-    /* SIZES | FILL together and every other bit: RTBVH_ERR_INVALID_ARG.  There is no SORT mode: a region has no
-       centre. */
+    RTBVH_REGION_NO_ACCEPT = 1u << 6, /* never take a subtree whole: descend to every leaf.  The same bytes; for
+                                         A/B runs and tests */
+    /* Bits 16..19: the split field (below).  0: one lane walks one region. */
+    RTBVH_REGION_SPLIT_SHIFT = 16,
+    RTBVH_REGION_SPLIT_AUTO = 15u << 16
+    /* SIZES | FILL together, the split field values 13 and 14 and every other bit: RTBVH_ERR_INVALID_ARG.  There is
+       no SORT mode: a region has no centre. */
 };
+/* The split field: the same lists from many lanes, for few and large regions (one frustum, a slicer's layers).
+ * A value v = 1..12 at bits 16..19 of `mode` (v << RTBVH_REGION_SPLIT_SHIFT) cuts each region into at most K = 2^v
+ * pieces; RTBVH_REGION_SPLIT_AUTO (v = 15) takes K = 4096.  Either way K is then halved until
+ * n * K <= RTBVH_REGION_SPLIT_MAX_PIECES, so the field is an upper limit, and K = 1 (many regions) is the plain path.
+ * A piece is a subtree of the BVH: one run of the sort order.  The library expands each region's frontier from the
+ * root, in order and on the device -- a node is replaced by those of its two children the region enters, a child the
+ * region holds whole becomes a finished range -- until K pieces are reached, then walks one piece a lane and lays the
+ * pieces' lists end to end.  The offsets, the ids and their order, `capacity`, the FILL rule above, the NaN word and
+ * its ordering, both tree forms, n == 0 and every error are those of the plain query, byte for byte; SIZES and FILL
+ * pair up with or without the field in all four ways.  A FILL call with the field computes the pieces and their
+ * sizes again, into the context's buffers, and fills against the caller's offsets.
+ * The context owns the piece buffers (16 B a piece slot, n * K slots): the first query with a field and each larger one waits on
+ * the host for the outstanding queries and allocates, as RTBVH_QUERY_SORT's buffers do.
+ * Stack limit: a piece's walk starts at its own node with an empty stack, so under rtbvh_config.stack_limit a split
+ * query may lose FEWER subtrees than the plain one.  Its lists are then subsequences of the true lists, both passes
+ * of a call lose the same subtrees, and RTBVH_ERR_STACK_OVERFLOW is reported as above.  Without an overflow the bytes
+ * are the plain query's. */
+#define RTBVH_REGION_SPLIT_MAX_PIECES (1u << 20)
 /* n regions at dev_regions (16-B aligned), n + 1 offsets at dev_offsets (8-B aligned) and room for `capacity` ids at
  * dev_ids (device memory of the context's device), enqueued on `stream` (hipStream_t, NULL = the context stream).
  * Mode 0 runs the sizes pass, a scan of the offsets on the device and the fill pass in one call, with no host round
@@ -1156,6 +1177,13 @@ rtbvh_status rtbvh_region_host(rtbvh_ctx* ctx, const rtbvh_region* regions, uint
  * leaf steps, subtrees taken whole (these three summed over the passes the call ran) and the ids that came from
  * them (counted once).  Its own words.  RTBVH_ERR_NOT_READY before any counting region query. */
 rtbvh_status rtbvh_region_counts(rtbvh_ctx* ctx, uint64_t out[6]);
+/* With a split field, rtbvh_region_counts counts regions (not pieces) and ids once; the internal-node steps include
+ * the expansion's node tests (made once a call, where the plain query makes them once a pass), and the subtrees
+ * taken whole include the ranges the expansion finished.
+ * The last RTBVH_REGION_COUNT query that had a split field (waits for it): out[0] the K used (1: the plain path ran,
+ * the other words are 0), out[1] the non-empty pieces, out[2] the node tests the expansion made, out[3] the longest
+ * single piece walk in node + leaf steps.  RTBVH_ERR_NOT_READY before any such query. */
+rtbvh_status rtbvh_region_split_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- signed-distance queries: the nearest triangle, and on which side of the surface the point is ----
  * (No reference equivalent.)  Same points (rtbvh_point: {point.xyz, max_dist2}) and the same space as the

@@ -16,11 +16,13 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    CROSS_COUNT, CROSS_FILL, CROSS_SIZES, CROSS_SORT, TRI_DTYPE,
                    CLEARANCE_COUNT, CLEARANCE_DTYPE, CLEARANCE_SORT,
                    REGION_COUNT, REGION_DTYPE, REGION_FILL, REGION_NO_ACCEPT, REGION_SIZES, REGION_TRIANGLE,
+                   REGION_SPLIT_AUTO, REGION_SPLIT_MAX_PIECES, REGION_SPLIT_SHIFT,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, box_region, check_cross_tris, check_nearest_points, check_overlap_boxes,
                        check_query_rays, check_region_planes, check_vertex_array, comm_destroy, comm_unique_id,
-                       frustum_planes, make_boxes, make_points, make_rays, make_regions, make_tris, save_bmp, slab_region)
+                       frustum_planes, make_boxes, make_points, make_rays, make_regions, make_tris, region_split, save_bmp,
+                       slab_region)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
                     camera_reference, load_npz, load_obj, synthetic)
 
@@ -45,5 +47,6 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "TRI_DTYPE", "CROSS_SORT", "CROSS_COUNT", "CROSS_SIZES", "CROSS_FILL", "make_tris", "check_cross_tris",
            "CLEARANCE_DTYPE", "CLEARANCE_SORT", "CLEARANCE_COUNT",
            "REGION_DTYPE", "REGION_COUNT", "REGION_TRIANGLE", "REGION_SIZES", "REGION_FILL", "REGION_NO_ACCEPT",
+           "REGION_SPLIT_SHIFT", "REGION_SPLIT_AUTO", "REGION_SPLIT_MAX_PIECES", "region_split",
            "make_regions", "box_region", "slab_region", "frustum_planes", "check_region_planes",
            "check_query_rays", "check_vertex_array"]

@@ -56,7 +56,7 @@ EXPORTS = [
     "rtbvh_collide_async", "rtbvh_collide_host", "rtbvh_collide_counts",
     "rtbvh_cross_async", "rtbvh_cross_host", "rtbvh_cross_first_async", "rtbvh_cross_first_host", "rtbvh_cross_counts",
     "rtbvh_clearance_async", "rtbvh_clearance_host", "rtbvh_clearance_counts",
-    "rtbvh_region_async", "rtbvh_region_host", "rtbvh_region_counts",
+    "rtbvh_region_async", "rtbvh_region_host", "rtbvh_region_counts", "rtbvh_region_split_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -114,6 +114,8 @@ CLEARANCE_SORT, CLEARANCE_COUNT = 2, 4   # RTBVH_CLEARANCE_*
 REGION_DTYPE = np.dtype([("plane", "<f4", (6, 4))])
 assert REGION_DTYPE.itemsize == 96
 REGION_COUNT, REGION_TRIANGLE, REGION_SIZES, REGION_FILL, REGION_NO_ACCEPT = 4, 8, 16, 32, 64   # RTBVH_REGION_*
+# the split field of a region mode (bits 16..19: at most 2^v pieces a region, 15 automatic) and the bound on n * K
+REGION_SPLIT_SHIFT, REGION_SPLIT_AUTO, REGION_SPLIT_MAX_PIECES = 16, 15 << 16, 1 << 20
 
 
 class Config(ctypes.Structure):
@@ -309,6 +311,7 @@ def lib() -> ctypes.CDLL:
         "rtbvh_region_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_region_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_region_counts": (i32, [vp, vp]),
+        "rtbvh_region_split_counts": (i32, [vp, vp]),
         "rtbvh_update_vertices_async": (i32, [vp, vp, u32, vp, u32, u32, u32, vp]),
         "rtbvh_update_vertices_host": (i32, [vp, vp, u32, vp, u32, u32, u32]),
         "rtbvh_refit_async": (i32, [vp]),

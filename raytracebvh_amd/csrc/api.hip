@@ -364,6 +364,12 @@ struct rtbvh_ctx {
     // recorded behind it for the region queries of that tree on other streams
     uint64_t nan_epoch = 0;
     Event ev_nan;
+    // Split region queries: the pieces, their offsets and that scan's block sums, grown on demand under the sort
+    // buffers' rule.  split_counted: the split count block holds a counting split query's words, split_k its K.
+    Grown<uint2> d_pieces;
+    Grown<unsigned long long> d_poff, d_pscan;
+    bool split_counted = false;
+    uint64_t split_k = 0;
 };
 
 namespace {
@@ -3373,12 +3379,17 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
                                 uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     constexpr uint32_t ALL = RTBVH_REGION_COUNT | RTBVH_REGION_TRIANGLE | RTBVH_REGION_SIZES | RTBVH_REGION_FILL |
-                             RTBVH_REGION_NO_ACCEPT;
+                             RTBVH_REGION_NO_ACCEPT | RTBVH_REGION_SPLIT_AUTO;
     constexpr uint32_t BOTH = RTBVH_REGION_SIZES | RTBVH_REGION_FILL;
     if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "region: bad mode bits");
+    const uint32_t field = (mode >> RTBVH_REGION_SPLIT_SHIFT) & 15u;
+    if (field > REGION_SPLIT_MAX_SHIFT && field != 15u)
+        return fail(c, RTBVH_ERR_INVALID_ARG, "region: split field 13 or 14");
     if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "region: 2^31 regions or more");
     const bool sizes = !(mode & RTBVH_REGION_FILL), fill = !(mode & RTBVH_REGION_SIZES);
     static_assert(sizeof(rtbvh_region) == 96, "region query layout");
+    static_assert(REGION_SPLIT_MAX_PIECES == RTBVH_REGION_SPLIT_MAX_PIECES && REGION_SPLIT_MAX_SHIFT == 12,
+                  "the split field's documented bounds");
     if (n == 0) {
         if (!dev_offsets || !sizes) return RTBVH_OK;
         HIPC(c, hipSetDevice(c->cfg.device));
@@ -3393,6 +3404,11 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool count = (mode & RTBVH_REGION_COUNT) != 0, tri = (mode & RTBVH_REGION_TRIANGLE) != 0;
     const uint32_t N = (uint32_t)n;
+    // The split field is an upper limit: K = 2^kshift pieces a region, the largest with n * K <= the product bound
+    // (automatic: from 4096 down).  K = 1 is the plain path.
+    uint32_t kshift = field == 15u ? REGION_SPLIT_MAX_SHIFT : field;
+    while (kshift > 0 && ((uint64_t)N << kshift) > REGION_SPLIT_MAX_PIECES) kshift--;
+    const uint32_t slots = N << kshift;
     if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
     if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
     if (!c->ev_nan) HIPC(c, hipEventCreateWithFlags(c->ev_nan.out(), hipEventDisableTiming));
@@ -3400,6 +3416,14 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
         // (as rtbvh_overlap_async: earlier queries scan in the old buffer)
         HIPC(c, hipEventSynchronize(c->ev_query));
         HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
+    }
+    if (kshift && !(c->d_pieces.has(slots) && c->d_poff.has((size_t)slots + 1) &&
+                    c->d_pscan.has(scan_sums_words(slots)))) {
+        // (the first split query and each larger one: earlier ones still read the old buffers)
+        HIPC(c, hipEventSynchronize(c->ev_query));
+        HIPC(c, c->d_pieces.reserve(slots));
+        HIPC(c, c->d_poff.reserve((size_t)slots + 1));
+        HIPC(c, c->d_pscan.reserve(scan_sums_words(slots)));
     }
     if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
     if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
@@ -3433,22 +3457,51 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
     a.overflow = c->d_ovf;
     const uint32_t lim = c->cfg.stack_limit;
     a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_ids = true;
-        launch_region(a, false, count, tri, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
+    const bool split_field = field != 0u;
+    if (count && split_field)
+        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REGION_SPLIT_AT, 0, sizeof(uint64_t) * REGION_SPLIT_COUNT_WORDS, s));
+    if (kshift) {
+        // [expansion], [piece sizes + scan], then the caller's offsets (not RTBVH_REGION_FILL: those are input) and
+        // [piece fill]: a launch sequence fixed by (n, K, mode), all on the caller's stream
+        RegionSplitArgs sa{};
+        sa.pieces = c->d_pieces;
+        sa.poff = c->d_poff;
+        sa.kshift = kshift;
+        sa.split = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_REGION_SPLIT_AT);
+        sa.r = a;
+        launch_region_expand(sa, count, s);
         HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_ids = !sizes;
-        launch_region(a, true, count, tri, s);
+        sa.r.count_ids = sizes;
+        launch_region_piece(sa, false, count, tri, s);
+        scan_offsets(sa.poff, slots, c->d_pscan, s);
+        if (sizes) launch_region_offsets(sa.poff, a.offsets, N, kshift, s);
+        if (fill) {
+            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+            sa.r.count_ids = !sizes;
+            launch_region_piece(sa, true, count, tri, s);
+        }
+    } else {
+        if (sizes) {
+            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+            a.count_ids = true;
+            launch_region(a, false, count, tri, s);
+            scan_offsets(a.offsets, N, c->d_qscan, s);
+        }
+        if (fill) {
+            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+            a.count_ids = !sizes;
+            launch_region(a, true, count, tri, s);
+        }
     }
     rtbvh_status st = check_launch(c, "region kernels");
     HIPC(c, hipEventRecord(c->ev_query, s));
     c->query_busy = true;
     c->query_ovf = true;
     if (count && !st) c->region_counted = true;
+    if (count && split_field && !st) {
+        c->split_counted = true;
+        c->split_k = 1ull << kshift;
+    }
     return st;
 }
 
@@ -3495,6 +3548,17 @@ rtbvh_status rtbvh_region_counts(rtbvh_ctx* c, uint64_t out[6]) {
     HIPC(c, hipSetDevice(c->cfg.device));
     HIPC(c, hipEventSynchronize(c->ev_query));
     HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_REGION_AT, sizeof(uint64_t) * REGION_COUNT_WORDS,
+                      hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+
+rtbvh_status rtbvh_region_split_counts(rtbvh_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->split_counted) return fail(c, RTBVH_ERR_NOT_READY, "no counting region query with a split field yet");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->ev_query));
+    out[0] = c->split_k;
+    HIPC(c, hipMemcpy(out + 1, c->d_qscratch + QUERY_REGION_SPLIT_AT, sizeof(uint64_t) * REGION_SPLIT_COUNT_WORDS,
                       hipMemcpyDeviceToHost));
     return RTBVH_OK;
 }

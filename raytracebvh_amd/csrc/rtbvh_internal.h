@@ -689,9 +689,38 @@ struct RegionArgs {
 constexpr uint32_t REGION_COUNT_WORDS = 6;
 constexpr uint32_t QUERY_REGION_AT = QUERY_CLEARANCE_AT + 2 * QUERY_COUNT_WORDS;
 constexpr uint32_t QUERY_LEAF_NAN_AT = QUERY_REGION_AT + 2 * REGION_COUNT_WORDS;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_LEAF_NAN_AT + 2;
-static_assert(QUERY_REGION_AT % 2 == 0, "the count block's 8-byte words");
+// the split region queries' own count block (three 8-byte words: non-empty pieces, the expansion's node tests, the
+// longest piece walk), behind the leaf-NaN word
+constexpr uint32_t REGION_SPLIT_COUNT_WORDS = 3;
+constexpr uint32_t QUERY_REGION_SPLIT_AT = QUERY_LEAF_NAN_AT + 2;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_REGION_SPLIT_AT + 2 * REGION_SPLIT_COUNT_WORDS;
+static_assert(QUERY_REGION_AT % 2 == 0 && QUERY_REGION_SPLIT_AT % 2 == 0, "the count block's 8-byte words");
 void launch_region(const RegionArgs& a, bool fill, bool count, bool tri, hipStream_t s);
+
+// ---- split region queries (trace.hip k_region_expand, k_region_piece; the split field of rtbvh_region_async) ----
+// A region is cut along the tree into at most K = 1 << kshift pieces, slots [r * K, r * K + K) of `pieces` in
+// leaf-range order.  A piece {a, b}: b == 0 EMPTY; b == REGION_PIECE_NODE the subtree of walk node a (LEAF_BIT | j:
+// the one leaf j), walked like a region from its own node; any other b the leaf range [a, a + b) taken whole.
+// k_region_expand writes them (one wave a region); k_region_piece walks one piece a lane: its sizes pass stores
+// piece p's count at poff[p + 1], scan_offsets makes offsets of them, launch_region_offsets copies every K-th into
+// the caller's offsets, and its fill pass stores piece p's ids from offsets[r] + (poff[p] - poff[r * K]).
+constexpr uint32_t REGION_PIECE_NODE = 0xFFFFFFFFu;
+constexpr uint32_t REGION_SPLIT_MAX_SHIFT = 12;         // K <= 4096: the frontier's two lists fill 64 KB of LDS
+constexpr uint32_t REGION_SPLIT_MAX_PIECES = 1u << 20;  // n * K <= this: RTBVH_REGION_SPLIT_MAX_PIECES (api.hip)
+constexpr uint32_t REGION_SPLIT_ROUNDS = 64;            // the expansion's rounds: each expands one node at least
+struct RegionSplitArgs {
+    RegionArgs r;             // r.n regions; r.offsets the caller's
+    uint2* pieces;            // [n << kshift]
+    unsigned long long* poff; // [(n << kshift) + 1]
+    uint32_t kshift;
+    unsigned long long* split;      // RTBVH_REGION_COUNT: [3] non-empty pieces, the expansion's node tests, the
+                                    //   longest piece walk (zeroed)
+};
+void launch_region_expand(const RegionSplitArgs& a, bool count, hipStream_t s);
+void launch_region_piece(const RegionSplitArgs& a, bool fill, bool count, bool tri, hipStream_t s);
+// offsets[r] = poff[r << kshift], r = 0 .. n
+void launch_region_offsets(const unsigned long long* poff, unsigned long long* offsets, uint32_t n, uint32_t kshift,
+                           hipStream_t s);
 // *word (zeroed by the caller) = 1 if any of the T leaf records holds a NaN in its box words 10..15
 void launch_leaf_nan(const float4* leaf, uint32_t T, uint32_t* word, hipStream_t s);
 

@@ -3762,9 +3762,16 @@ __device__ __forceinline__ bool planes_vertices(const float (&pl)[24], f3 a, f3 
 // FILL = false counts a region's members and stores the count at offsets[r + 1]; FILL = true stores the ids at
 // offsets[r] + i while that is below min(offsets[r + 1], capacity), as k_overlap: whatever the offsets hold, no
 // store -- a lane's own or the wave's range copy -- leaves the region's segment or the first `capacity` ids.
-template <bool FILL, bool COUNT, bool NB, bool TRI>
-__global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) void k_region(RegionArgs a) {
-    const uint32_t n = a.n, T = a.T;
+// SPLIT (k_region_piece): the queue holds the n << kshift piece slots k_region_expand filled instead of the n
+// regions.  A lane takes one piece: a NODE piece starts the same step loop at its own node with an empty stack (the
+// node's box is known to enter), a RANGE piece is the accept at the claim, an EMPTY slot is no work.  The sizes pass
+// stores piece p's count at poff[p + 1]; the fill pass starts piece p of region r at offsets[r] + (poff[p] -
+// poff[r << kshift]) and clamps every store like the plain walk.  msteps: the longest piece walk (COUNT).
+template <bool FILL, bool COUNT, bool NB, bool TRI, bool SPLIT>
+__device__ __forceinline__ void region_walk(const RegionArgs& a, const uint2* __restrict__ pieces,
+                                            unsigned long long* __restrict__ poff, uint32_t kshift,
+                                            unsigned long long* __restrict__ msteps) {
+    const uint32_t n = SPLIT ? a.n << kshift : a.n, T = a.T;
     const uint32_t lane = lane_id();
     const int limit = a.stack_limit;
     const float4* __restrict__ leaf = a.leaf;
@@ -3777,6 +3784,7 @@ __global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) v
     unsigned long long nids = 0, naccids = 0;
     bool has = false;
     uint32_t r = 0, cnt = 0;
+    uint32_t slot = 0, psteps = 0, pmax = 0;   // SPLIT: the piece's slot; with COUNT its steps, and the most of any
     unsigned long long pos = 0, end = 0;   // FILL: the next id's index and the end of the region's segment
     uint32_t plo = 0, plen = 0;            // FILL: an accepted range still to copy, leaves [plo, plo + plen)
     Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (hit, best, bl unused)
@@ -3789,6 +3797,44 @@ __global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) v
     Refill rf;
     while (true) {
         refill_claim(rf, a.next, n, has, [&](uint32_t k) {   // this lane takes the k-th region
+            if (SPLIT) {   // ... the k-th piece slot
+                slot = k;
+                r = k >> kshift;
+                const uint2 item = pieces[k];
+                if (COUNT && a.count_ids && (k & ((1u << kshift) - 1u)) == 0) nregions++;   // (its region's first slot)
+                if (item.y == 0u) {   // EMPTY
+                    if (!FILL) poff[(size_t)k + 1] = 0;
+                    return;
+                }
+                const float4* src = a.regions + 6 * (size_t)r;
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    const float4 p = src[i];
+                    pl[4 * i] = p.x; pl[4 * i + 1] = p.y; pl[4 * i + 2] = p.z; pl[4 * i + 3] = p.w;
+                }
+                has = true;
+                cnt = 0;
+                if (COUNT) psteps = 0;
+                if (FILL) {
+                    pos = a.offsets[r] + (poff[k] - poff[(size_t)r << kshift]);
+                    const unsigned long long e = a.offsets[(size_t)r + 1];
+                    end = e < a.capacity ? e : a.capacity;
+                }
+                w = walk_start(item.x, T);   // a NODE piece: from its own node (LEAF_BIT | j: the leaf step alone)
+                if (item.y != REGION_PIECE_NODE) {   // a RANGE piece: every leaf of [item.x, item.x + item.y), no step
+                    w.sp = -1;
+                    cnt = item.y;
+                    if (FILL) {
+                        plo = item.x;
+                        plen = item.y;
+                    }
+                    if (COUNT) {
+                        nacc++;
+                        if (a.count_ids) naccids += item.y;
+                    }
+                }
+                return;
+            }
             r = k;
             const float4* src = a.regions + 6 * (size_t)r;
             bool finite = true;
@@ -3860,6 +3906,7 @@ __global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) v
                 q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
                 q3 = v4f{0.f, 0.f, 0.f, 0.f};
             }
+            if (SPLIT && COUNT) psteps++;
             if (--w.guard == 0) {
                 c.overflow++;
                 done = true;
@@ -3948,8 +3995,12 @@ __global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) v
             }
         }
         if (done) {
-            if (!FILL) a.offsets[(size_t)r + 1] = cnt;
+            if (!FILL) {
+                if (SPLIT) poff[(size_t)slot + 1] = cnt;
+                else a.offsets[(size_t)r + 1] = cnt;
+            }
             if (COUNT && a.count_ids) nids += cnt;
+            if (SPLIT && COUNT) pmax = psteps > pmax ? psteps : pmax;
             has = false;
         }
     }
@@ -3962,6 +4013,160 @@ __global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) v
             if (v[6]) atomicAdd(a.overflow, v[6]);
         }
     }
+    if (SPLIT && COUNT) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t o = __shfl_xor(pmax, off, 64);
+            pmax = o > pmax ? o : pmax;
+        }
+        if (lane == 0 && pmax) atomicMax(msteps, (unsigned long long)pmax);
+    }
+}
+template <bool FILL, bool COUNT, bool NB, bool TRI>
+__global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) void k_region(RegionArgs a) {
+    region_walk<FILL, COUNT, NB, TRI, false>(a, nullptr, nullptr, 0u, nullptr);
+}
+template <bool FILL, bool COUNT, bool NB, bool TRI>
+__global__ __launch_bounds__(BLOCK, COUNT ? REGION_COUNT_WAVES : REGION_WAVES) void k_region_piece(RegionSplitArgs sa) {
+    region_walk<FILL, COUNT, NB, TRI, true>(sa.r, sa.pieces, sa.poff, sa.kshift, sa.split + 2);
+}
+
+// The expansion of a split region query: one wave a region, the ordered frontier in LDS as two lists of K pieces
+// (16 B x K: 64 KB at K = 4096), read from one and written to the other each round.  A wave needs no barrier between
+// its own rounds and no hand-off to another wave; the kernel boundary hands the pieces to k_region_piece.  A region
+// holds at most K pieces whatever the wave count, so a workgroup of four waves would only share the same passes of 64
+// items among them at the price of a barrier per pass.
+// A round replaces the first K - len NODE pieces (each adds one piece net at most, so the list still fits) by the
+// outcome of planes_box on their two children, left then right: dropped, RANGE (internal, inside, accepts on), or
+// NODE (a leaf child: LEAF_BIT | j).  Ranks by ballot: the order of the list is the order of the leaves, whatever
+// ran when.  It ends when no NODE is left, the list is full, or after REGION_SPLIT_ROUNDS rounds (a chain of one-leaf
+// children adds one piece a round); k_region_piece walks the NODEs that remain.
+template <bool NB>
+__global__ __launch_bounds__(64) void k_region_expand(RegionSplitArgs sa, bool count) {
+    extern __shared__ uint2 s_front[];
+    const RegionArgs& a = sa.r;
+    const uint32_t K = 1u << sa.kshift, r = blockIdx.x, lane = threadIdx.x, T = a.T;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    const bool acc_on = a.accept && *a.leaf_nan == 0u;
+    uint2 *A = s_front, *B = s_front + K;
+    float pl[24];
+    bool finite = true;
+    {
+        const float4* src = a.regions + 6 * (size_t)r;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const float4 p = src[i];
+            pl[4 * i] = p.x; pl[4 * i + 1] = p.y; pl[4 * i + 2] = p.z; pl[4 * i + 3] = p.w;
+            finite &= fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY && fabsf(p.w) < INFINITY;
+        }
+    }
+    uint32_t len = 0, tests = 0;   // (len: the same in every lane)
+    {   // the root, as k_region's claim
+        bool enter = false, inside = false;
+        if (finite) {
+            if (T == 1) enter = true;
+            else planes_box(pl, mk(a.rootbox[0], a.rootbox[1], a.rootbox[2]), mk(a.rootbox[3], a.rootbox[4], a.rootbox[5]),
+                            enter, inside);
+        }
+        if (enter) {
+            len = 1;
+            if (lane == 0)
+                A[0] = T > 1 && inside && acc_on ? make_uint2(0u, T)
+                                                 : make_uint2(NB ? nbt.root(T) : rec.root(T), REGION_PIECE_NODE);
+        }
+    }
+    __syncthreads();
+    for (uint32_t round = 0; round < REGION_SPLIT_ROUNDS && len > 0 && len < K; round++) {
+        const uint32_t budget = K - len;
+        uint32_t nnode = 0, nout = 0;
+        for (uint32_t base = 0; base < len; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < len;
+            const uint2 item = valid ? A[i] : make_uint2(0u, 0u);
+            const bool isnode = valid && item.y == REGION_PIECE_NODE && !(item.x & LEAF_BIT);
+            const uint64_t nm = __ballot(isnode);
+            const bool expand = isnode && nnode + lane_rank(nm) < budget;
+            nnode += (uint32_t)__popcll(nm);
+            uint2 o0 = item, o1 = make_uint2(0u, 0u);
+            uint32_t no = valid ? 1u : 0u;
+            if (expand) {
+                uint32_t cl, cr, lid, rid;
+                f3 llo, lhi, rlo, rhi;
+                if (!NB) {
+                    const v4f* rr = reinterpret_cast<const v4f*>(a.inner + item.x);
+                    const v4f q0 = rr[0], q1 = rr[1], q2 = rr[2], q3 = rr[3];
+                    const uint32_t own = __float_as_uint(q3.z);
+                    lid = __float_as_uint(q3.x);
+                    rid = __float_as_uint(q3.y);
+                    cl = child_slot(lid, own, 0);
+                    cr = child_slot(rid, own, 1);
+                    llo = mk(q0.x, q0.y, q2.x); lhi = mk(q0.z, q0.w, q2.y);
+                    rlo = mk(q1.x, q1.y, q2.z); rhi = mk(q1.z, q1.w, q2.w);
+                } else {
+                    const ChildPair ch = nbt.children(item.x);
+                    cl = lid = ch.cl;
+                    cr = rid = ch.cr;
+                    llo = mk(ch.llo.x, ch.llo.y, ch.lz0); lhi = mk(ch.lhi.x, ch.lhi.y, ch.lz1);
+                    rlo = mk(ch.rlo.x, ch.rlo.y, ch.rz0); rhi = mk(ch.rhi.x, ch.rhi.y, ch.rz1);
+                }
+                tests++;
+                bool lh, li, rh, ri;
+                planes_box(pl, llo, lhi, lh, li);
+                planes_box(pl, rlo, rhi, rh, ri);
+                no = 0;
+                if (lh) {
+                    o0 = make_uint2(cl, REGION_PIECE_NODE);
+                    if (li && acc_on && !(cl & LEAF_BIT)) {
+                        const uint4 t = a.topo[lid];
+                        o0 = make_uint2(t.z, t.w - t.z + 1);
+                    }
+                    no = 1;
+                }
+                if (rh) {
+                    uint2 o = make_uint2(cr, REGION_PIECE_NODE);
+                    if (ri && acc_on && !(cr & LEAF_BIT)) {
+                        const uint4 t = a.topo[rid];
+                        o = make_uint2(t.z, t.w - t.z + 1);
+                    }
+                    if (no) o1 = o;
+                    else o0 = o;
+                    no++;
+                }
+            }
+            const uint64_t m1 = __ballot(no >= 1u), m2 = __ballot(no == 2u);
+            const uint32_t at = nout + lane_rank(m1) + lane_rank(m2);   // (<= len + expanded <= K)
+            if (no >= 1u) B[at] = o0;
+            if (no == 2u) B[at + 1] = o1;
+            nout += (uint32_t)__popcll(m1) + (uint32_t)__popcll(m2);
+        }
+        __syncthreads();
+        uint2* t = A;
+        A = B;
+        B = t;
+        len = nout;
+        if (nnode == 0) break;   // (copied as it was: final)
+    }
+    uint2* out = sa.pieces + ((size_t)r << sa.kshift);
+    for (uint32_t i = lane; i < K; i += 64) out[i] = i < len ? A[i] : make_uint2(0u, 0u);
+    if (count) {
+        const unsigned long long t = wave_sum((unsigned long long)tests);
+        if (lane == 0) {
+            if (len) atomicAdd(&sa.split[0], (unsigned long long)len);
+            if (t) {
+                atomicAdd(&sa.split[1], t);
+                atomicAdd(&a.counts[2], t);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_region_offsets(const unsigned long long* __restrict__ poff,
+                                                          unsigned long long* __restrict__ offsets, uint32_t n,
+                                                          uint32_t kshift) {
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r <= n) offsets[r] = poff[(size_t)r << kshift];
 }
 
 // *word = 1 if a leaf box (words 10..15 of a leaf record) holds a NaN; the caller zeroes it first
@@ -4766,6 +4971,28 @@ void launch_region(const RegionArgs& a, bool fill, bool count, bool tri, hipStre
     with_bools([&](auto FILL, auto COUNT, auto NB, auto TRI) {
         hipLaunchKernelGGL((k_region<FILL, COUNT, NB, TRI>), dim3(blocks), dim3(BLOCK), 0, s, a);
     }, fill, count, a.nb, tri);
+}
+
+void launch_region_expand(const RegionSplitArgs& a, bool count, hipStream_t s) {
+    if (a.r.n == 0) return;
+    const size_t lds = 2 * sizeof(uint2) << a.kshift;   // (<= 64 KB: kshift <= REGION_SPLIT_MAX_SHIFT)
+    if (a.r.nb) hipLaunchKernelGGL(k_region_expand<true>, dim3(a.r.n), dim3(64), lds, s, a, count);
+    else hipLaunchKernelGGL(k_region_expand<false>, dim3(a.r.n), dim3(64), lds, s, a, count);
+}
+
+void launch_region_piece(const RegionSplitArgs& a, bool fill, bool count, bool tri, hipStream_t s) {
+    if (a.r.n == 0) return;
+    const uint32_t slots = a.r.n << a.kshift;
+    const uint32_t need = (slots + BLOCK - 1) / BLOCK, full = 256 * (count ? REGION_COUNT_WAVES : REGION_WAVES);
+    const uint32_t blocks = need < full ? need : full;
+    with_bools([&](auto FILL, auto COUNT, auto NB, auto TRI) {
+        hipLaunchKernelGGL((k_region_piece<FILL, COUNT, NB, TRI>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, fill, count, a.r.nb, tri);
+}
+
+void launch_region_offsets(const unsigned long long* poff, unsigned long long* offsets, uint32_t n, uint32_t kshift,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(k_region_offsets, dim3((n + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, poff, offsets, n, kshift);
 }
 
 void launch_leaf_nan(const float4* leaf, uint32_t T, uint32_t* word, hipStream_t s) {

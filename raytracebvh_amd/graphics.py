@@ -263,6 +263,14 @@ def frustum_planes(wvp):
     return np.stack([-(cw + cx), -(cw - cx), -(cw + cy), -(cw - cy), -cz, -(cw - cz)]).astype(np.float32)
 
 
+def region_split(k: int) -> int:
+    """The mode bits that cut each region of Context.region into at most k pieces along the tree (the header's split
+    field): k a power of two from 2 to 4096.  REGION_SPLIT_AUTO lets the library choose.  ValueError otherwise."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2 or k > 4096 or k & (k - 1):
+        raise ValueError(f"region_split: k must be a power of two from 2 to 4096, got {k!r}")
+    return (int(k).bit_length() - 1) << _L.REGION_SPLIT_SHIFT
+
+
 def check_region_planes(regions, device=None):
     """Context.region's input check: ("torch", regions) for an (N, 24) float32 contiguous CUDA tensor (on `device`
     when given), ("numpy", REGION_DTYPE array) for a C-contiguous REGION_DTYPE array, (N, 24) float32 array or
@@ -994,13 +1002,16 @@ class Context:
         `regions`: make_regions' / box_region's / slab_region's output, or (N, P <= 6, 4) float32 planes (numpy).
         Inputs, outputs, `capacity`, `sizes_only` and `stream` are Context.overlap's: numpy goes through the
         synchronous host entry, a torch CUDA (N, 24) tensor to the device entry.  mode: REGION_COUNT,
-        REGION_TRIANGLE, REGION_NO_ACCEPT (REGION_SIZES and REGION_FILL are this method's to set).  ValueError for
-        a wrong shape, dtype, device or layout."""
+        REGION_TRIANGLE, REGION_NO_ACCEPT, and region_split(k) or REGION_SPLIT_AUTO: the same lists with each region
+        cut into pieces along the tree and walked by many lanes -- for few, large regions (REGION_SIZES and
+        REGION_FILL are this method's to set).  ValueError for a wrong shape, dtype, device or layout."""
         kind, rg = check_region_planes(regions, getattr(self, "device", None))
         if mode & (_L.REGION_SIZES | _L.REGION_FILL):
             raise ValueError("region: REGION_SIZES and REGION_FILL are set by region itself")
-        if mode & ~(_L.REGION_COUNT | _L.REGION_TRIANGLE | _L.REGION_NO_ACCEPT):
+        if mode & ~(_L.REGION_COUNT | _L.REGION_TRIANGLE | _L.REGION_NO_ACCEPT | _L.REGION_SPLIT_AUTO):
             raise ValueError(f"region: unknown mode bits {mode:#x}")
+        if (mode >> _L.REGION_SPLIT_SHIFT) & 15 in (13, 14):
+            raise ValueError(f"region: split field {(mode >> _L.REGION_SPLIT_SHIFT) & 15} (region_split, REGION_SPLIT_AUTO)")
         if capacity is not None and (int(capacity) != capacity or capacity < 0):
             raise ValueError(f"region: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and capacity is not None:
@@ -1062,6 +1073,14 @@ class Context:
         self._check(_L.lib().rtbvh_region_counts(self._h, _L.ptr(out)))
         return dict(zip(("regions", "ids", "internal_steps", "leaf_steps", "accepted_subtrees", "accepted_ids"),
                         (int(v) for v in out)))
+
+    def region_split_counts(self) -> dict:
+        """rtbvh_region_split_counts: of the last REGION_COUNT query with a split field, the K used (1: the plain
+        path ran), the non-empty pieces, the node tests of the expansion and the longest single piece walk in
+        steps."""
+        out = np.zeros(4, np.uint64)
+        self._check(_L.lib().rtbvh_region_split_counts(self._h, _L.ptr(out)))
+        return dict(zip(("k", "pieces", "expansion_tests", "longest_piece_steps"), (int(v) for v in out)))
 
     # -- self-collision queries --
     def collide(self, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None, device: bool = False):
