@@ -202,6 +202,67 @@ struct LastTrace {
     bool walk_tree = false;          // its certified bounce passes walked the walk-only tree
 };
 
+// ---- the query chain ---------------------------------------------------------------------------------
+// Every rtbvh_*_async query entry, of whatever kind and on whatever stream, is one link of one chain.  The rules:
+//  - Shared: the scratch block (the walks' work counters at its head, then one count block a kind: KINDS) and
+//    the buffers grown on demand -- the walk order's sort, the offset scan's block sums, the certified ray
+//    query's re-trace list, RTBVH_ALLHITS_BY_T's lists, a split region query's pieces.  So a link runs alone.
+//  - Waits: a link waits on its stream for `ev`, recorded behind the link before it (`busy`: since the last
+//    build or host drain), and -- on a stream other than the context's -- for the last build (ev_built).  The
+//    next writer of the tree waits for `ev` (wait_queries); the host drains wait for it (sync_all).
+//  - Growth: a shared buffer is reallocated only after hipEventSynchronize(ev): earlier links use the old
+//    one.  The first link that needs a buffer and each larger one wait on the host there (reserve_shared).
+//  - Counts: a counting link zeroes and fills its kind's block only and sets counted[kind]; a link that does
+//    not count leaves every block alone.  The *_counts readers wait for `ev` and read one block.
+//  - Overflows: `ovf` says a link ran since the last rtbvh_synchronize, which then looks at the overflow word.
+// What a caller gets when several arguments are wrong is fixed too: query_rules.
+enum Kind : uint32_t {
+    K_QUERY, K_NEAREST, K_WITHIN, K_ALLHITS, K_OVERLAP, K_KNN, K_SIGNED, K_KHITS, K_COLLIDE, K_CROSS, K_CLEARANCE,
+    K_REGION, K_REGION_SPLIT, K_KINDS
+};
+struct KindRow {
+    uint32_t at, words;        // its count block: QueryChain::scratch + at, 8-byte words
+    const char* not_ready;     // what its reader answers before a counting query
+};
+constexpr KindRow KINDS[K_KINDS] = {
+    {QUERY_COUNTS_AT, QUERY_COUNT_WORDS, "no RTBVH_QUERY_COUNT query yet"},
+    {QUERY_NEAREST_AT, QUERY_COUNT_WORDS, "no RTBVH_NEAREST_COUNT query yet"},
+    {QUERY_WITHIN_AT, QUERY_COUNT_WORDS, "no RTBVH_WITHIN_COUNT query yet"},
+    {QUERY_ALLHITS_AT, QUERY_COUNT_WORDS, "no RTBVH_ALLHITS_COUNT query yet"},
+    {QUERY_OVERLAP_AT, QUERY_COUNT_WORDS, "no RTBVH_OVERLAP_COUNT query yet"},
+    {QUERY_KNN_AT, QUERY_COUNT_WORDS, "no RTBVH_KNN_COUNT query yet"},
+    {QUERY_SIGNED_AT, 2 * QUERY_COUNT_WORDS, "no RTBVH_SIGNED_COUNT query yet"},   // the ray pass's, the closest-point pass's
+    {QUERY_KHITS_AT, QUERY_COUNT_WORDS, "no RTBVH_KHITS_COUNT query yet"},
+    {QUERY_COLLIDE_AT, QUERY_COUNT_WORDS, "no RTBVH_COLLIDE_COUNT query yet"},
+    {QUERY_CROSS_AT, QUERY_COUNT_WORDS, "no RTBVH_CROSS_COUNT query yet"},
+    {QUERY_CLEARANCE_AT, QUERY_COUNT_WORDS, "no RTBVH_CLEARANCE_COUNT query yet"},
+    {QUERY_REGION_AT, REGION_COUNT_WORDS, "no RTBVH_REGION_COUNT query yet"},
+    {QUERY_REGION_SPLIT_AT, REGION_SPLIT_COUNT_WORDS, "no counting region query with a split field yet"},
+};
+static_assert(QUERY_SIGNED_NEAR_AT == QUERY_SIGNED_AT + 2 * QUERY_COUNT_WORDS, "the signed queries' two blocks are one");
+struct QueryChain {
+    DevBuf<uint32_t> scratch;                // [QUERY_ALLOC_WORDS]: the work counters, the ray queries' words, KINDS' blocks
+    Grown<uint32_t> sort;                    // a walk order: 6 arrays of cap / 6 words (keys and values: in, A, B),
+    Grown<uint32_t> sort_scratch;            //   and the sort's digit counts
+    Grown<uint32_t> redo;                    // RTBVH_QUERY_CERTIFIED: the re-trace list
+    Grown<unsigned long long> scan;          // the offset scan's block sums
+    Grown<uint32_t> order;                   // RTBVH_ALLHITS_BY_T: 2 arrays of cap / 2 words (each ray's stored hits, the
+                                             //   rays with long lists)
+    Grown<uint2> pieces;                     // split region queries: the pieces, their offsets and that scan's
+    Grown<unsigned long long> poff, pscan;   //   block sums
+    Event ev;                                // ev_query: recorded behind the last link
+    bool busy = false;                       // ... which no build or host drain has waited for yet
+    bool ovf = false;                        // a link ran since the last rtbvh_synchronize (its overflows)
+    bool counted[K_KINDS] = {};              // the kind's count block holds a counting query's counts
+    uint64_t fallback = 0;                   // K_QUERY: its rays, when it took the present kernel for all of them; or 0
+    uint64_t split_k = 0;                    // K_REGION_SPLIT: its K
+    // The region queries' leaf-NaN word (scratch + QUERY_LEAF_NAN_AT) is a product of the built tree, like a bin
+    // set: written on the stream of the first region query of a tree (nan_epoch: its bins_epoch), with ev_nan
+    // recorded behind it for the region queries of that tree on other streams
+    uint64_t nan_epoch = 0;
+    Event ev_nan;
+};
+
 struct rtbvh_ctx {
     rtbvh_config cfg{};
     // Members are destroyed last to first: the streams the context created stand first, so they outlive every
@@ -330,46 +391,7 @@ struct rtbvh_ctx {
     };
     std::deque<DealTab> deals;       // the MAX_DEALS most recently used (H, nranks, share), most recent first
     static constexpr size_t MAX_DEALS = 8;
-    // Ray queries (rtbvh_query_async), on any stream.  They share one scratch block (the walk's work counters and
-    // the count block) and the sort's buffers, so the library chains them: each waits for ev_query, recorded
-    // behind the one before it (query_busy: since the last build or synchronize).  The next build waits for it too.
-    DevBuf<uint32_t> d_qscratch;             // [QUERY_ALLOC_WORDS]: the ray queries' words, the closest-point counts,
-                                             //   the radius queries' counts, the all-hits queries' counts, the box
-                                             //   queries' counts
-    Grown<uint32_t> d_qsort;                 // RTBVH_QUERY_SORT: 6 arrays of cap / 6 words (keys and values: in, A, B),
-    Grown<uint32_t> d_qsort_scratch;         //   and the sort's digit counts; grown on demand
-    Grown<uint32_t> d_qredo;                 // RTBVH_QUERY_CERTIFIED: the re-trace list; grown on demand
-    Grown<unsigned long long> d_qscan;       // rtbvh_within_async, rtbvh_allhits_async, rtbvh_overlap_async: the offset
-                                             //   scan's block sums
-    Grown<uint32_t> d_qorder;                // RTBVH_ALLHITS_BY_T: 2 arrays of cap / 2 words (each ray's stored hits, the
-                                             //   rays with long lists); grown on demand
-    Event ev_query;
-    bool query_busy = false;
-    bool query_ovf = false;                  // a query ran since the last rtbvh_synchronize (its overflows)
-    bool query_counted = false;              // the count block holds a RTBVH_QUERY_COUNT query's counts
-    uint64_t query_fallback = 0;             // ... its rays, when it took the present kernel for all of them; or 0
-    bool nearest_counted = false;            // the closest-point count block holds a RTBVH_NEAREST_COUNT query's counts
-    bool within_counted = false;             // the radius queries' count block holds a RTBVH_WITHIN_COUNT query's counts
-    bool allhits_counted = false;            // the all-hits count block holds a RTBVH_ALLHITS_COUNT query's counts
-    bool overlap_counted = false;            // the box queries' count block holds a RTBVH_OVERLAP_COUNT query's counts
-    bool knn_counted = false;                // the k-nearest queries' count block holds a RTBVH_KNN_COUNT query's counts
-    bool signed_counted = false;             // the signed-distance queries' count block holds a RTBVH_SIGNED_COUNT query's counts
-    bool khits_counted = false;              // the first-k queries' count block holds a RTBVH_KHITS_COUNT query's counts
-    bool collide_counted = false;            // the self-collision queries' count block holds a RTBVH_COLLIDE_COUNT query's counts
-    bool cross_counted = false;              // the triangle queries' count block holds a RTBVH_CROSS_COUNT query's counts
-    bool clearance_counted = false;          // the clearance queries' count block holds a RTBVH_CLEARANCE_COUNT query's counts
-    bool region_counted = false;             // the region queries' count block holds a RTBVH_REGION_COUNT query's counts
-    // The region queries' leaf-NaN word (d_qscratch + QUERY_LEAF_NAN_AT) is a product of the built tree, like a bin
-    // set: written on the stream of the first region query of a tree (nan_epoch: its bins_epoch), with ev_nan
-    // recorded behind it for the region queries of that tree on other streams
-    uint64_t nan_epoch = 0;
-    Event ev_nan;
-    // Split region queries: the pieces, their offsets and that scan's block sums, grown on demand under the sort
-    // buffers' rule.  split_counted: the split count block holds a counting split query's words, split_k its K.
-    Grown<uint2> d_pieces;
-    Grown<unsigned long long> d_poff, d_pscan;
-    bool split_counted = false;
-    uint64_t split_k = 0;
+    QueryChain q;                    // the queries' shared state (above): last, so gone before every stream
 };
 
 namespace {
@@ -429,7 +451,7 @@ rtbvh_status drain_slots(rtbvh_ctx* c) {
 rtbvh_status sync_all(rtbvh_ctx* c) {
     HIPC(c, hipStreamSynchronize(c->stream));
     TRY(drain_slots(c));
-    if (c->query_busy) HIPC(c, hipEventSynchronize(c->ev_query));
+    if (c->q.busy) HIPC(c, hipEventSynchronize(c->q.ev));
     if (c->update_pending) HIPC(c, hipEventSynchronize(c->ev_update));   // (a vertex update on a caller stream)
     return RTBVH_OK;
 }
@@ -445,11 +467,11 @@ rtbvh_status wait_slots(rtbvh_ctx* c, hipStream_t s) {
 }
 
 // The next writer of the BVH on stream s (a build) waits for the outstanding ray queries, which read it.  (Never
-// inside a capture: rtbvh_compute_bvh's plain frame before it has cleared query_busy.)
+// inside a capture: rtbvh_compute_bvh's plain frame before it has cleared q.busy.)
 rtbvh_status wait_queries(rtbvh_ctx* c, hipStream_t s) {
-    if (c->query_busy) {
-        HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-        c->query_busy = false;
+    if (c->q.busy) {
+        HIPC(c, hipStreamWaitEvent(s, c->q.ev, 0));
+        c->q.busy = false;
     }
     return RTBVH_OK;
 }
@@ -1501,7 +1523,7 @@ rtbvh_status rtbvh_set_scene(rtbvh_ctx* c, const rtbvh_vertex* verts, uint32_t n
         if (mat_idx[t] >= nmats) return fail(c, RTBVH_ERR_INVALID_ARG, "set_scene: material index out of range");
     HIPC(c, hipSetDevice(c->cfg.device));
     TRY(sync_all(c));   // frames in flight and ray queries on caller streams read the old scene and BVH
-    c->query_busy = false;
+    c->q.busy = false;
     reset_tree(c);
     try {
         std::vector<float4> opos(nverts);
@@ -2045,15 +2067,15 @@ rtbvh_status rtbvh_trace_tiles(rtbvh_ctx* c, uint32_t W, uint32_t H, uint32_t bo
 rtbvh_status rtbvh_synchronize(rtbvh_ctx* c) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
     TRY(sync_all(c));
-    c->query_busy = false;
+    c->q.busy = false;
     // each trace ends by copying the never-reset overflow word into its slot's pinned word
     unsigned long long ovf = c->ovf_seen;
     for (uint32_t k = 0; k < rtbvh_ctx::MAXSPLIT; k++)
         if (c->h_ovf[k] > ovf) ovf = c->h_ovf[k];
-    if (c->query_ovf) {   // queries run on any stream: the word itself, once they are all done
+    if (c->q.ovf) {   // queries run on any stream: the word itself, once they are all done
         unsigned long long v = 0;
         HIPC(c, hipMemcpy(&v, c->d_ovf, sizeof(v), hipMemcpyDeviceToHost));
-        c->query_ovf = false;
+        c->q.ovf = false;
         if (v > ovf) ovf = v;
     }
     if (ovf > c->ovf_seen) {
@@ -2354,8 +2376,8 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
                                     rtbvh_node* out) {
     if (!c || !sorted_codes || !leaf_boxes || !out || n == 0 || n >= (1u << 30)) return RTBVH_ERR_INVALID_ARG;
     HIPC(c, hipSetDevice(c->cfg.device));
-    if (c->ev_query) HIPC(c, hipEventSynchronize(c->ev_query));   // (the scene's BVH buffers are reused)
-    c->query_busy = false;
+    if (c->q.ev) HIPC(c, hipEventSynchronize(c->q.ev));   // (the scene's BVH buffers are reused)
+    c->q.busy = false;
     TRY(ensure_build_capacity(c, n));
     DevBuf<float> d_boxes;
     DevBuf<rtbvh_node> d_out;
@@ -2381,23 +2403,291 @@ rtbvh_status rtbvh_build_from_codes(rtbvh_ctx* c, const uint32_t* sorted_codes, 
     return RTBVH_OK;
 }
 
+}  // extern "C"
+
+// ---- queries: the frame every kind shares ------------------------------------------------------------
+// The chain's rules stand at QueryChain.  A rtbvh_<kind>_async entry is: its rules (a *_rules call: the same for
+// its _host entry), enter_chain, the kind's words zeroed, fill_tree and the Args fields of its own,
+// [walk_order], its launches ([two_passes] for lists), leave_chain.  The walks read the tree form the last build
+// wrote (Tree::wrote NBOX: the topology and node boxes, else the node records), never a derived one.
+namespace {
+
+// What is wrong with a query call, in the order every kind keeps.  Ahead of this the kind has looked at its mode
+// bits, then at its own scalars (k; the region split field).  Then: 2^31 queries or more; no queries -- nothing
+// to do, *run stays false, whatever the pointers and the tree; a NULL array (null_msg: the kind's words for it);
+// no tree; a tree that is not of the geometry.
+rtbvh_status query_rules(rtbvh_ctx* c, const char* kind, const char* nouns, uint64_t n, const char* null_msg,
+                         bool* run) {
+    *run = false;
+    if (n >= (1ull << 31))
+        return fail(c, RTBVH_ERR_INVALID_ARG, std::string(kind) + ": 2^31 " + nouns + " or more");
+    if (n == 0) return RTBVH_OK;
+    if (null_msg) return fail(c, RTBVH_ERR_INVALID_ARG, null_msg);
+    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, std::string(kind) + " before build");
+    if (c->stale) return fail_stale(c, kind);
+    *run = true;
+    return RTBVH_OK;
+}
+
+// The kinds that answer one record (or k) a query
+struct RecordKind {
+    const char *name, *nouns, *bad_mode, *nulls;
+    uint32_t modes;
+};
+constexpr RecordKind QUERY{"query", "rays", "query: unknown mode bits", "query: NULL rays or hits",
+                           RTBVH_QUERY_ANY | RTBVH_QUERY_SORT | RTBVH_QUERY_COUNT | RTBVH_QUERY_CERTIFIED};
+constexpr RecordKind NEAREST{"nearest", "points", "nearest: unknown mode bits", "nearest: NULL points or results",
+                             RTBVH_NEAREST_SORT | RTBVH_NEAREST_COUNT};
+constexpr RecordKind KNN{"knn", "points", "knn: unknown mode bits", "knn: NULL points or pairs",
+                         RTBVH_KNN_SORT | RTBVH_KNN_COUNT};
+constexpr RecordKind KHITS{"khits", "rays", "khits: unknown mode bits", "khits: NULL rays or hits",
+                           RTBVH_KHITS_SORT | RTBVH_KHITS_COUNT};
+constexpr RecordKind SIGNED{"signed", "points", "signed: unknown mode bits", "signed: NULL points or results",
+                            RTBVH_SIGNED_SORT | RTBVH_SIGNED_COUNT | RTBVH_SIGNED_VOTE3 | RTBVH_SIGNED_INSIDE_ONLY};
+constexpr RecordKind CROSS_FIRST{"cross_first", "triangles", "cross_first: bad mode bits",
+                                 "cross_first: NULL triangles or output", RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT};
+constexpr RecordKind CLEARANCE{"clearance", "triangles", "clearance: bad mode bits",
+                               "clearance: NULL triangles or results", RTBVH_CLEARANCE_SORT | RTBVH_CLEARANCE_COUNT};
+// bad_scalar: what is wrong with the kind's own scalar (k), or null
+rtbvh_status record_rules(rtbvh_ctx* c, const RecordKind& k, uint32_t mode, const char* bad_scalar, const void* in,
+                          uint64_t n, const void* out, bool* run) {
+    if (mode & ~k.modes) return fail(c, RTBVH_ERR_INVALID_ARG, k.bad_mode);
+    if (bad_scalar) return fail(c, RTBVH_ERR_INVALID_ARG, bad_scalar);
+    return query_rules(c, k.name, k.nouns, n, !in || !out ? k.nulls : nullptr, run);
+}
+
+// The kinds that answer offsets and lists (CSR): one call, or a SIZES call and a FILL call
+struct ListKind {
+    const char *name, *nouns, *items;
+    uint32_t modes, sizes, fill;   // every mode bit; the two of which a call takes one at the most
+    bool own_queries = false;      // the tree's triangles are the queries: no array and no n of the caller's
+};
+constexpr ListKind WITHIN{"within", "points", "pairs",
+                          RTBVH_WITHIN_SORT | RTBVH_WITHIN_COUNT | RTBVH_WITHIN_SIZES | RTBVH_WITHIN_FILL,
+                          RTBVH_WITHIN_SIZES, RTBVH_WITHIN_FILL};
+constexpr ListKind ALLHITS{"allhits", "rays", "hits",
+                           RTBVH_ALLHITS_SORT | RTBVH_ALLHITS_COUNT | RTBVH_ALLHITS_BY_T | RTBVH_ALLHITS_SIZES |
+                               RTBVH_ALLHITS_FILL,
+                           RTBVH_ALLHITS_SIZES, RTBVH_ALLHITS_FILL};
+constexpr ListKind OVERLAP{"overlap", "boxes", "ids",
+                           RTBVH_OVERLAP_SORT | RTBVH_OVERLAP_COUNT | RTBVH_OVERLAP_TRIANGLE | RTBVH_OVERLAP_SIZES |
+                               RTBVH_OVERLAP_FILL,
+                           RTBVH_OVERLAP_SIZES, RTBVH_OVERLAP_FILL};
+constexpr ListKind CROSS{"cross", "triangles", "ids",
+                         RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT | RTBVH_CROSS_SIZES | RTBVH_CROSS_FILL, RTBVH_CROSS_SIZES,
+                         RTBVH_CROSS_FILL};
+constexpr ListKind REGION{"region", "regions", "ids",
+                          RTBVH_REGION_COUNT | RTBVH_REGION_TRIANGLE | RTBVH_REGION_SIZES | RTBVH_REGION_FILL |
+                              RTBVH_REGION_NO_ACCEPT | RTBVH_REGION_SPLIT_AUTO,
+                          RTBVH_REGION_SIZES, RTBVH_REGION_FILL};
+constexpr ListKind COLLIDE{"collide", "", "ids",
+                           RTBVH_COLLIDE_COUNT | RTBVH_COLLIDE_TRIANGLE | RTBVH_COLLIDE_SIZES | RTBVH_COLLIDE_FILL |
+                               RTBVH_COLLIDE_SYMMETRIC,
+                           RTBVH_COLLIDE_SIZES, RTBVH_COLLIDE_FILL, true};
+// bad_scalar: as record_rules'.  A kind with own_queries has neither `in` nor `n` to check: what is left of the
+// order is mode, NULL offsets, NULL items, the tree.
+rtbvh_status list_rules(rtbvh_ctx* c, const ListKind& k, uint32_t mode, const char* bad_scalar, const void* in,
+                        uint64_t n, const void* offsets, const void* items, uint64_t capacity, bool* run) {
+    const std::string name = k.name;
+    if ((mode & ~k.modes) || (mode & k.sizes && mode & k.fill))
+        return fail(c, RTBVH_ERR_INVALID_ARG, name + ": bad mode bits");
+    if (bad_scalar) return fail(c, RTBVH_ERR_INVALID_ARG, bad_scalar);
+    const bool own = k.own_queries;
+    std::string nulls;
+    if (own ? !offsets : !in || !offsets)
+        nulls = own ? name + ": NULL offsets" : name + ": NULL " + k.nouns + " or offsets";
+    else if (!(mode & k.sizes) && capacity > 0 && !items) nulls = name + ": NULL " + k.items;
+    // (own queries: any count that passes the rules on n)
+    return query_rules(c, k.name, k.nouns, own ? 1 : n, nulls.empty() ? nullptr : nulls.c_str(), run);
+}
+// ... whose call without queries stores offsets[0] = 0, unless the offsets are input
+rtbvh_status store_no_lists(rtbvh_ctx* c, uint64_t* dev_offsets, bool fill_only, void* stream) {
+    if (!dev_offsets || fill_only) return RTBVH_OK;
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
+    return RTBVH_OK;
+}
+
+// What a link needs of the buffers grown on demand: counts of queries, 0 for none
+struct Need {
+    uint32_t sort = 0;     // a walk order over this many ([keys + sort])
+    uint32_t scan = 0;     // an offset scan over this many
+    uint32_t redo = 0;     // a certified ray query's re-trace list
+    uint32_t order = 0;    // RTBVH_ALLHITS_BY_T over this many rays
+    uint32_t pieces = 0;   // a split region query's piece slots
+};
+// The growth rule: the first link that needs a buffer and each larger one wait on the host for the links before
+// them, which use the old buffers (and hipMalloc blocks too), as include/rtbvh.h says
+rtbvh_status reserve_shared(rtbvh_ctx* c, const Need& n) {
+    QueryChain& q = c->q;
+    const size_t sort = n.sort ? 6 * (size_t)n.sort : 0, digits = n.sort ? sort_scratch_words(n.sort) : 0;
+    const size_t scan = scan_sums_words(n.scan), order = 2 * (size_t)n.order;
+    const size_t poff = n.pieces ? (size_t)n.pieces + 1 : 0, pscan = scan_sums_words(n.pieces);
+    if (q.sort.has(sort) && q.sort_scratch.has(digits) && q.scan.has(scan) && q.redo.has(n.redo) && q.order.has(order) &&
+        q.pieces.has(n.pieces) && q.poff.has(poff) && q.pscan.has(pscan))
+        return RTBVH_OK;
+    HIPC(c, hipEventSynchronize(q.ev));
+    HIPC(c, q.sort.reserve(sort));
+    HIPC(c, q.sort_scratch.reserve(digits));
+    HIPC(c, q.scan.reserve(scan));
+    HIPC(c, q.redo.reserve(n.redo));
+    HIPC(c, q.order.reserve(order));
+    HIPC(c, q.pieces.reserve(n.pieces));
+    HIPC(c, q.poff.reserve(poff));
+    HIPC(c, q.pscan.reserve(pscan));
+    return RTBVH_OK;
+}
+
+// A link enters the chain on *s, the caller's stream or the context's: the shared buffers, then the waits for the
+// last build and for the link before.  `derive`: a tree form to derive between the two (the QNodes of a build
+// that wrote none, once: behind the earlier links, none of which reads them).
+rtbvh_status enter_chain(rtbvh_ctx* c, void* stream, const Need& need, hipStream_t* s, uint32_t derive = 0) {
+    QueryChain& q = c->q;
+    HIPC(c, hipSetDevice(c->cfg.device));
+    *s = stream ? (hipStream_t)stream : c->stream;
+    if (!q.scratch) HIPC(c, q.scratch.alloc(QUERY_ALLOC_WORDS));
+    if (!q.ev) HIPC(c, hipEventCreateWithFlags(q.ev.out(), hipEventDisableTiming));
+    TRY(reserve_shared(c, need));
+    if (*s != c->stream) HIPC(c, hipStreamWaitEvent(*s, c->ev_built, 0));
+    if (derive) TRY(ensure_form(c, (Form)derive, *s));
+    if (q.busy) HIPC(c, hipStreamWaitEvent(*s, q.ev, 0));
+    return RTBVH_OK;
+}
+// ... and leaves it: the next link waits for what was enqueued up to here
+rtbvh_status leave_chain(rtbvh_ctx* c, Kind k, bool count, const char* what, hipStream_t s) {
+    const rtbvh_status st = check_launch(c, what);
+    HIPC(c, hipEventRecord(c->q.ev, s));
+    c->q.busy = true;
+    c->q.ovf = true;
+    if (count && !st) c->q.counted[k] = true;
+    return st;
+}
+
+// Every walk launch needs the work counters zeroed again
+rtbvh_status zero_work(rtbvh_ctx* c, hipStream_t s) {
+    HIPC(c, hipMemsetAsync(c->q.scratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+    return RTBVH_OK;
+}
+// A counting link zeroes its kind's block (a link that does not count leaves the last counting one's words alone)
+rtbvh_status zero_counts(rtbvh_ctx* c, Kind k, bool count, hipStream_t s) {
+    if (count) HIPC(c, hipMemsetAsync(c->q.scratch + KINDS[k].at, 0, sizeof(uint64_t) * KINDS[k].words, s));
+    return RTBVH_OK;
+}
+
+// The fields every kind's Args has: the tree, the work counters, a count block, the stack
+template <typename Args>
+void fill_tree(const rtbvh_ctx* c, Args& a, uint32_t counts_at) {
+    a.inner = c->d_rec;
+    a.topo = c->d_topo;
+    a.nbox = c->d_nbox;
+    a.nb = c->tree.wrote == NBOX;
+    a.leaf = c->d_leaf;
+    a.T = c->T;
+    a.next = c->q.scratch;
+    a.counts = reinterpret_cast<unsigned long long*>(c->q.scratch + counts_at);
+    a.overflow = c->d_ovf;
+    const uint32_t lim = c->cfg.stack_limit;
+    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
+}
+
+// [keys + sort]: the walk order of N queries by their kind's 30-bit keys, one permutation for every pass of the call
+using KeysFn = void (*)(const float4*, uint32_t, const float*, uint32_t*, uint32_t*, hipStream_t);
+const uint32_t* walk_order(rtbvh_ctx* c, KeysFn keys, const float4* queries, uint32_t N, hipStream_t s) {
+    uint32_t* q = c->q.sort;
+    const size_t m = c->q.sort.cap / 6;
+    keys(queries, N, c->d_rootbox, q, q + m, s);
+    return radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->q.sort_scratch, s).vals;
+}
+
+// [sizes + scan], then [fill]: pass(fill, count_items) sets the Args field that says whether the pass counts its
+// items -- the sizes pass does; the fill pass of a FILL call does -- and launches
+template <typename Pass>
+rtbvh_status two_passes(rtbvh_ctx* c, bool sizes, bool fill, unsigned long long* offsets, uint32_t N, hipStream_t s,
+                        Pass pass) {
+    if (sizes) {
+        TRY(zero_work(c, s));
+        pass(false, true);
+        scan_offsets(offsets, N, c->q.scan, s);
+    }
+    if (fill) {
+        TRY(zero_work(c, s));
+        pass(true, !sizes);
+    }
+    return RTBVH_OK;
+}
+
+// A host entry of a record kind: the inputs and behind them the outputs in one allocation (an input record is a
+// multiple of 16 bytes), call(inputs, outputs) -- the kind's async entry on the context stream -- and the records
+// back.  They are complete (knn, khits: the best found) when rtbvh_synchronize reports RTBVH_ERR_STACK_OVERFLOW.
+template <typename Call>
+rtbvh_status host_records(rtbvh_ctx* c, const std::string& name, const void* in, size_t in_bytes, void* out,
+                          size_t out_bytes, Call call) {
+    HIPC(c, hipSetDevice(c->cfg.device));
+    DevBuf<char> d;
+    HIPC(c, d.alloc(in_bytes + out_bytes));
+    if (hipMemcpy(d, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: upload failed");
+    TRY(call(d.h, d.h + in_bytes));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, name + "_host: sync");
+    if (hipMemcpy(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: download failed");
+    return rtbvh_synchronize(c);
+}
+// A host entry of a list kind: n + 1 offsets and behind them the inputs (8- and 16-byte aligned), the items apart;
+// call(inputs, offsets, items, capacity).  FILL takes the offsets up, every other call brings them back; SIZES has
+// no items; min(offsets[n], capacity) items come back.
+template <typename Call>
+rtbvh_status host_lists(rtbvh_ctx* c, const ListKind& k, uint32_t mode, const void* in, size_t in_bytes, uint64_t n,
+                        uint64_t* offsets, void* items, size_t item_bytes, uint64_t capacity, Call call) {
+    const std::string name = k.name;
+    const bool fill_only = (mode & k.fill) != 0;
+    HIPC(c, hipSetDevice(c->cfg.device));
+    const size_t off_bytes = (size_t)(n + 1) * sizeof(uint64_t), in_at = (off_bytes + 15) & ~(size_t)15;
+    DevBuf<char> d, ditems;
+    HIPC(c, d.alloc(in_at + in_bytes));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
+    if (in_bytes && hipMemcpy(d + in_at, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: upload failed");
+    if (fill_only && hipMemcpy(doff, offsets, off_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: upload failed");
+    if (mode & k.sizes) capacity = 0;
+    if (capacity) HIPC(c, ditems.alloc((size_t)capacity * item_bytes));
+    if (capacity && fill_only)   // (offsets of another tree, mode or input leave gaps: zeros, not what the allocation held)
+        HIPC(c, hipMemsetAsync(ditems, 0, (size_t)capacity * item_bytes, c->stream));
+    TRY(call(d.h + in_at, doff, ditems.h, capacity));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, name + "_host: sync");
+    if (!fill_only && hipMemcpy(offsets, doff, off_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: download failed");
+    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
+    if (m && hipMemcpy(items, ditems, (size_t)m * item_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RTBVH_ERR_HIP, name + "_host: download failed");
+    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+}
+
+// A *_counts reader: `words` of the scratch block at `at`, behind the chain
+rtbvh_status read_counts(rtbvh_ctx* c, Kind k, uint64_t* out, uint32_t at, uint32_t words) {
+    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
+    if (!c->q.counted[k]) return fail(c, RTBVH_ERR_NOT_READY, KINDS[k].not_ready);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    HIPC(c, hipEventSynchronize(c->q.ev));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "count block words");
+    HIPC(c, hipMemcpy(out, c->q.scratch + at, sizeof(uint64_t) * words, hipMemcpyDeviceToHost));
+    return RTBVH_OK;
+}
+rtbvh_status kind_counts(rtbvh_ctx* c, Kind k, uint64_t* out) { return read_counts(c, k, out, KINDS[k].at, KINDS[k].words); }
+
+}  // namespace
+
+extern "C" {
+
 // ---- ray queries -------------------------------------------------------------------------------------
-// The walk reads the tree form the last build wrote (Tree::wrote NBOX: the topology and node boxes, else the node
-// records), never a derived one.  Queries on any stream are chained by ev_query (they share the scratch block
-// and the sort's buffers); each waits for the last build (ev_built), the next build for them (wait_queries).
 rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, rtbvh_hit* dev_hits,
                                uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_QUERY_ANY | RTBVH_QUERY_SORT | RTBVH_QUERY_COUNT | RTBVH_QUERY_CERTIFIED))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "query: unknown mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "query: 2^31 rays or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "query: NULL rays or hits");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "query before build");
-    if (c->stale) return fail_stale(c, "query");
+    bool run;
+    TRY(record_rules(c, QUERY, mode, nullptr, dev_rays, n, dev_hits, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "query record layouts");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool any = (mode & RTBVH_QUERY_ANY) != 0, sort = (mode & RTBVH_QUERY_SORT) != 0;
     const bool count = (mode & RTBVH_QUERY_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
@@ -2405,1003 +2695,449 @@ rtbvh_status rtbvh_query_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t
     // tree, the full stack); otherwise the present kernel for every ray -- the same hits either way
     const bool limited = c->cfg.stack_limit != 0 && c->cfg.stack_limit < (uint32_t)STACK_SIZE;
     const bool cert = (mode & RTBVH_QUERY_CERTIFIED) != 0 && c->tree.clz64 && !limited;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
-        // earlier queries sort in the old buffers: the first RTBVH_QUERY_SORT query and each larger one wait
-        // for them on the host here (and hipMalloc blocks too), as include/rtbvh.h says
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-    }
-    if (cert && !c->d_qredo.has((size_t)n)) {   // (earlier queries list in the old buffer: as the sort's)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qredo.reserve((size_t)n));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    // the QNodes of a build that wrote none, derived once (behind the earlier queries: none reads them)
-    if (cert) TRY(ensure_form(c, QNODES, s));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
+    Need need;
+    need.sort = sort ? N : 0;
+    need.redo = cert ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s, cert ? QNODES : 0));
+    uint32_t* scratch = c->q.scratch;
     // the work counters; behind them a counting query's count block and walk counts, a certified query's list
     // length and its re-trace's work counters
-    // (a query that does not count leaves the last counting query's words alone)
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * (count ? QUERY_REDO_N_AT : QUERY_COUNTS_AT), s));
+    HIPC(c, hipMemsetAsync(scratch, 0, sizeof(uint32_t) * (count ? QUERY_REDO_N_AT : QUERY_COUNTS_AT), s));
     if (cert)
-        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REDO_N_AT, 0,
-                               sizeof(uint32_t) * (QUERY_SCRATCH_WORDS - QUERY_REDO_N_AT), s));
+        HIPC(c, hipMemsetAsync(scratch + QUERY_REDO_N_AT, 0, sizeof(uint32_t) * (QUERY_SCRATCH_WORDS - QUERY_REDO_N_AT), s));
     QueryArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_COUNTS_AT);
     a.rays = reinterpret_cast<const float4*>(dev_rays);
     a.hits = reinterpret_cast<float4*>(dev_hits);
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_COUNTS_AT);
-    a.walk = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_WALK_AT);
+    a.walk = reinterpret_cast<unsigned long long*>(scratch + QUERY_WALK_AT);
     a.qnode = c->d_qnode;
     a.tclip = c->d_tclip;
-    a.redo = c->d_qredo;
-    a.redo_n = c->d_qscratch + QUERY_REDO_N_AT;
-    a.next2 = c->d_qscratch + QUERY_NEXT2_AT;
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
+    a.redo = c->q.redo;
+    a.redo_n = scratch + QUERY_REDO_N_AT;
+    a.next2 = scratch + QUERY_NEXT2_AT;
+    if (sort) a.perm = walk_order(c, launch_query_keys, a.rays, N, s);
     if (cert) launch_query_certified(a, any, count, s);
     else launch_query(a, any, count, s);
-    rtbvh_status st = check_launch(c, "query kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) {
-        c->query_counted = true;
-        c->query_fallback = cert ? 0 : n;
-    }
+    const rtbvh_status st = leave_chain(c, K_QUERY, count, "query kernels", s);
+    if (count && !st) c->q.fallback = cert ? 0 : n;
     return st;
 }
 
 rtbvh_status rtbvh_query_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, rtbvh_hit* hits, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !rays || !hits || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
-        return rtbvh_query_async(c, rays, n, hits, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;
-    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_ray) + sizeof(rtbvh_hit))));
-    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d.h);
-    rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d + (size_t)n * sizeof(rtbvh_ray));
-    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "query_host: upload failed");
-    TRY(rtbvh_query_async(c, dr, n, dh, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "query_host: sync");
-    if (hipMemcpy(hits, dh, (size_t)n * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "query_host: download failed");
-    return rtbvh_synchronize(c);   // (the hits are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, QUERY, mode, nullptr, rays, n, hits, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, QUERY.name, rays, (size_t)n * sizeof(rtbvh_ray), hits, (size_t)n * sizeof(rtbvh_hit),
+                        [&](char* in, char* out) {
+                            return rtbvh_query_async(c, reinterpret_cast<const rtbvh_ray*>(in), n,
+                                                     reinterpret_cast<rtbvh_hit*>(out), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_query_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->query_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_QUERY_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "count block words");
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_COUNTS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_query_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_QUERY, out); }
 
 rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->query_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_QUERY_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
     // certified, redone, uncovered from the walk; a query that took the present kernel wrote none (zeroed)
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WALK_AT, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost));
-    out[3] = c->query_fallback;
+    TRY(read_counts(c, K_QUERY, out, QUERY_WALK_AT, 3));
+    out[3] = c->q.fallback;
     return RTBVH_OK;
 }
 
 // ---- closest-point queries ---------------------------------------------------------------------------
-// rtbvh_query_async's rules, one for one: any stream, behind the last build (ev_built), a link of the ev_query
-// chain (the work counters and the sort's buffers are the ray queries'), the tree form the last build wrote --
-// never the quantized nodes, whose boxes are grown.  The count block is its own (QUERY_NEAREST_AT): a closest-point
-// query leaves the last counting ray query's words alone, and a ray query these.
+// Never the quantized nodes, whose boxes are grown.
 rtbvh_status rtbvh_nearest_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, rtbvh_nearest* dev_out,
                                  uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_NEAREST_SORT | RTBVH_NEAREST_COUNT))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: unknown mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: 2^31 points or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_points || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "nearest: NULL points or results");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "nearest before build");
-    if (c->stale) return fail_stale(c, "nearest");
+    bool run;
+    TRY(record_rules(c, NEAREST, mode, nullptr, dev_points, n, dev_out, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_nearest) == 32, "closest-point record layouts");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_NEAREST_SORT) != 0, count = (mode & RTBVH_NEAREST_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_NEAREST_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_NEAREST, count, s));
     NearestArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_NEAREST_AT);
     a.points = reinterpret_cast<const float4*>(dev_points);
     a.out = reinterpret_cast<float4*>(dev_out);
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_NEAREST_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
+    if (sort) a.perm = walk_order(c, launch_nearest_keys, a.points, N, s);
     launch_nearest(a, count, s);
-    rtbvh_status st = check_launch(c, "nearest kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->nearest_counted = true;
-    return st;
+    return leave_chain(c, K_NEAREST, count, "nearest kernels", s);
 }
 
 rtbvh_status rtbvh_nearest_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, rtbvh_nearest* out, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !points || !out || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
-        return rtbvh_nearest_async(c, points, n, out, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;
-    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_point) + sizeof(rtbvh_nearest))));
-    rtbvh_nearest* dn = reinterpret_cast<rtbvh_nearest*>(d.h);
-    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + (size_t)n * sizeof(rtbvh_nearest));
-    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "nearest_host: upload failed");
-    TRY(rtbvh_nearest_async(c, dp, n, dn, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "nearest_host: sync");
-    if (hipMemcpy(out, dn, (size_t)n * sizeof(rtbvh_nearest), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "nearest_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, NEAREST, mode, nullptr, points, n, out, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, NEAREST.name, points, (size_t)n * sizeof(rtbvh_point), out, (size_t)n * sizeof(rtbvh_nearest),
+                        [&](char* in, char* res) {
+                            return rtbvh_nearest_async(c, reinterpret_cast<const rtbvh_point*>(in), n,
+                                                       reinterpret_cast<rtbvh_nearest*>(res), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->nearest_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_NEAREST_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_NEAREST_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_nearest_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_NEAREST, out); }
 
 // ---- radius queries ------------------------------------------------------------------------------------
-// rtbvh_nearest_async's rules and its place in the ev_query chain; [keys + sort], then [sizes + scan], then [fill],
-// all on the caller's stream.  Each walk launch needs the work counters zeroed again.  Its count block is
-// QUERY_WITHIN_AT.
 rtbvh_status rtbvh_within_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, uint64_t* dev_offsets,
                                 rtbvh_pair* dev_pairs, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_WITHIN_SORT | RTBVH_WITHIN_COUNT | RTBVH_WITHIN_SIZES | RTBVH_WITHIN_FILL;
-    constexpr uint32_t BOTH = RTBVH_WITHIN_SIZES | RTBVH_WITHIN_FILL;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "within: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "within: 2^31 points or more");
+    bool run;
+    TRY(list_rules(c, WITHIN, mode, nullptr, dev_points, n, dev_offsets, dev_pairs, capacity, &run));
     const bool sizes = !(mode & RTBVH_WITHIN_FILL), fill = !(mode & RTBVH_WITHIN_SIZES);
+    if (!run) return store_no_lists(c, dev_offsets, !sizes, stream);
     static_assert(sizeof(rtbvh_pair) == 8 && sizeof(uint64_t) == sizeof(unsigned long long), "radius query layouts");
-    if (n == 0) {
-        if (!dev_offsets || !sizes) return RTBVH_OK;
-        HIPC(c, hipSetDevice(c->cfg.device));
-        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
-        return RTBVH_OK;
-    }
-    if (!dev_points || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "within: NULL points or offsets");
-    if (fill && capacity > 0 && !dev_pairs) return fail(c, RTBVH_ERR_INVALID_ARG, "within: NULL pairs");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "within before build");
-    if (c->stale) return fail_stale(c, "within");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_WITHIN_SORT) != 0, count = (mode & RTBVH_WITHIN_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
-    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
-    if (grow_sort || grow_scan) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort and scan in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        if (grow_sort) {
-            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-        }
-        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_WITHIN_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    need.scan = sizes ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_WITHIN, count, s));
     WithinArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_WITHIN_AT);
     a.points = reinterpret_cast<const float4*>(dev_points);
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
     a.pairs = reinterpret_cast<uint2*>(dev_pairs);
     a.capacity = capacity;
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_WITHIN_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {   // one permutation for both passes
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_pairs = true;
-        launch_within(a, false, count, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_pairs = !sizes;
-        launch_within(a, true, count, s);
-    }
-    rtbvh_status st = check_launch(c, "within kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->within_counted = true;
-    return st;
+    if (sort) a.perm = walk_order(c, launch_nearest_keys, a.points, N, s);
+    TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+        a.count_pairs = count_items;
+        launch_within(a, fill_pass, count, s);
+    }));
+    return leave_chain(c, K_WITHIN, count, "within kernels", s);
 }
 
 rtbvh_status rtbvh_within_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, uint64_t* offsets,
                                rtbvh_pair* pairs, uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_WITHIN_FILL) != 0, sizes_only = (mode & RTBVH_WITHIN_SIZES) != 0;
-    if (n == 0) {   // (nothing to stage)
-        const rtbvh_status st = rtbvh_within_async(c, points, 0, nullptr, pairs, capacity, mode, nullptr);
-        if (!st && offsets && !fill_only) offsets[0] = 0;
-        return st;
+    bool run;
+    TRY(list_rules(c, WITHIN, mode, nullptr, points, n, offsets, pairs, capacity, &run));
+    if (!run) {   // (nothing to stage)
+        if (offsets && !(mode & RTBVH_WITHIN_FILL)) offsets[0] = 0;
+        return RTBVH_OK;
     }
-    if (n >= (1ull << 31) || !points || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !pairs) ||
-        !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_within_async(c, points, n, offsets, pairs, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // offsets, then points: 8- and 16-B aligned
-    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_point)));
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
-    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + off_bytes);
-    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "within_host: upload failed");
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "within_host: upload failed");
-    DevBuf<rtbvh_pair> dpairs;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dpairs.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another tree or bound leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dpairs, 0, (size_t)capacity * sizeof(rtbvh_pair), c->stream));
-    TRY(rtbvh_within_async(c, dp, n, doff, dpairs, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "within_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "within_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(pairs, dpairs, (size_t)m * sizeof(rtbvh_pair), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "within_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    return host_lists(c, WITHIN, mode, points, (size_t)n * sizeof(rtbvh_point), n, offsets, pairs, sizeof(rtbvh_pair),
+                      capacity, [&](char* in, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_within_async(c, reinterpret_cast<const rtbvh_point*>(in), n, off,
+                                                    reinterpret_cast<rtbvh_pair*>(items), cap, mode, nullptr);
+                      });
 }
 
-rtbvh_status rtbvh_within_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->within_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_WITHIN_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_WITHIN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
-
+rtbvh_status rtbvh_within_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_WITHIN, out); }
 
 // ---- all-hits ray queries --------------------------------------------------------------------------------
-// rtbvh_within_async's structure with rtbvh_query_async's rays and sort keys: [keys + sort], [sizes + scan],
-// [fill], then for RTBVH_ALLHITS_BY_T the ordering pass, all on the caller's stream.  Its count block is
-// QUERY_ALLHITS_AT.  The ordering pass takes the work counters' first word (the walks are over) for the length of
-// its list.
+// The two passes, then for RTBVH_ALLHITS_BY_T the ordering pass, which takes the work counters' first word (the
+// walks are over) for the length of its list.
 rtbvh_status rtbvh_allhits_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, uint64_t* dev_offsets,
                                  rtbvh_hit* dev_hits, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_ALLHITS_SORT | RTBVH_ALLHITS_COUNT | RTBVH_ALLHITS_BY_T | RTBVH_ALLHITS_SIZES |
-                             RTBVH_ALLHITS_FILL;
-    constexpr uint32_t BOTH = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_FILL;
-    constexpr uint32_t SIZES_BY_T = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_BY_T;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH || (mode & SIZES_BY_T) == SIZES_BY_T)
-        return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: 2^31 rays or more");
+    constexpr uint32_t SIZES_BY_T = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_BY_T;   // (nothing stored: nothing to order)
+    bool run;
+    TRY(list_rules(c, ALLHITS, mode, (mode & SIZES_BY_T) == SIZES_BY_T ? "allhits: bad mode bits" : nullptr, dev_rays, n,
+                   dev_offsets, dev_hits, capacity, &run));
     const bool sizes = !(mode & RTBVH_ALLHITS_FILL), fill = !(mode & RTBVH_ALLHITS_SIZES);
-    if (n == 0) {
-        if (!dev_offsets || !sizes) return RTBVH_OK;
-        HIPC(c, hipSetDevice(c->cfg.device));
-        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
-        return RTBVH_OK;
-    }
-    if (!dev_rays || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: NULL rays or offsets");
-    if (fill && capacity > 0 && !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "allhits: NULL hits");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "allhits before build");
-    if (c->stale) return fail_stale(c, "allhits");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!run) return store_no_lists(c, dev_offsets, !sizes, stream);
     const bool sort = (mode & RTBVH_ALLHITS_SORT) != 0, count = (mode & RTBVH_ALLHITS_COUNT) != 0;
     const bool by_t = (mode & RTBVH_ALLHITS_BY_T) != 0 && capacity > 0;   // (nothing stored: nothing to order)
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
-    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
-    const bool grow_order = by_t && !c->d_qorder.has(2 * (size_t)n);
-    if (grow_sort || grow_scan || grow_order) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort, scan and order in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        if (grow_sort) {
-            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-        }
-        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-        if (grow_order) HIPC(c, c->d_qorder.reserve(2 * (size_t)n));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_ALLHITS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    need.scan = sizes ? N : 0;
+    need.order = by_t ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_ALLHITS, count, s));
     AllhitsArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_ALLHITS_AT);
     a.rays = reinterpret_cast<const float4*>(dev_rays);
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
     a.hits = reinterpret_cast<float4*>(dev_hits);
     a.capacity = capacity;
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_ALLHITS_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {   // one permutation for both passes
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
+    if (sort) a.perm = walk_order(c, launch_query_keys, a.rays, N, s);
+    uint32_t* ord = c->q.order;
+    TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+        a.count_hits = count_items;
+        if (fill_pass && by_t) a.written = ord;
+        launch_allhits(a, fill_pass, count, s);
+    }));
+    if (fill && by_t) {
+        HIPC(c, hipMemsetAsync(c->q.scratch, 0, sizeof(uint32_t), s));   // the list's length
+        launch_allhits_order(a.hits, a.offsets, ord, N, ord + c->q.order.cap / 2, c->q.scratch, s);
     }
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_hits = true;
-        launch_allhits(a, false, count, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_hits = !sizes;
-        uint32_t* ord = c->d_qorder;
-        if (by_t) a.written = ord;
-        launch_allhits(a, true, count, s);
-        if (by_t) {
-            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t), s));   // the list's length
-            launch_allhits_order(a.hits, a.offsets, ord, N, ord + c->d_qorder.cap / 2, c->d_qscratch, s);
-        }
-    }
-    rtbvh_status st = check_launch(c, "allhits kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->allhits_counted = true;
-    return st;
+    return leave_chain(c, K_ALLHITS, count, "allhits kernels", s);
 }
 
 rtbvh_status rtbvh_allhits_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, uint64_t* offsets, rtbvh_hit* hits,
                                 uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_ALLHITS_FILL) != 0, sizes_only = (mode & RTBVH_ALLHITS_SIZES) != 0;
-    if (n == 0) {   // (nothing to stage)
-        const rtbvh_status st = rtbvh_allhits_async(c, rays, 0, nullptr, hits, capacity, mode, nullptr);
-        if (!st && offsets && !fill_only) offsets[0] = 0;
-        return st;
+    constexpr uint32_t SIZES_BY_T = RTBVH_ALLHITS_SIZES | RTBVH_ALLHITS_BY_T;
+    bool run;
+    TRY(list_rules(c, ALLHITS, mode, (mode & SIZES_BY_T) == SIZES_BY_T ? "allhits: bad mode bits" : nullptr, rays, n,
+                   offsets, hits, capacity, &run));
+    if (!run) {   // (nothing to stage)
+        if (offsets && !(mode & RTBVH_ALLHITS_FILL)) offsets[0] = 0;
+        return RTBVH_OK;
     }
-    if (n >= (1ull << 31) || !rays || !offsets || (fill_only && sizes_only) ||
-        (sizes_only && (mode & RTBVH_ALLHITS_BY_T)) || (!sizes_only && capacity > 0 && !hits) || !c->tree.built ||
-        c->stale)   // (the query's checks)
-        return rtbvh_allhits_async(c, rays, n, offsets, hits, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // rays, then offsets: 16- and 8-B aligned
-    HIPC(c, d.alloc((size_t)n * sizeof(rtbvh_ray) + (size_t)(n + 1) * sizeof(uint64_t)));
-    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d.h);
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d + (size_t)n * sizeof(rtbvh_ray));
-    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "allhits_host: upload failed");
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "allhits_host: upload failed");
-    DevBuf<rtbvh_hit> dhits;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dhits.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another tree or bound leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dhits, 0, (size_t)capacity * sizeof(rtbvh_hit), c->stream));
-    TRY(rtbvh_allhits_async(c, dr, n, doff, dhits, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "allhits_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "allhits_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(hits, dhits, (size_t)m * sizeof(rtbvh_hit), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "allhits_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    return host_lists(c, ALLHITS, mode, rays, (size_t)n * sizeof(rtbvh_ray), n, offsets, hits, sizeof(rtbvh_hit), capacity,
+                      [&](char* in, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_allhits_async(c, reinterpret_cast<const rtbvh_ray*>(in), n, off,
+                                                     reinterpret_cast<rtbvh_hit*>(items), cap, mode, nullptr);
+                      });
 }
 
-rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->allhits_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_ALLHITS_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_ALLHITS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_allhits_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_ALLHITS, out); }
 
 // ---- box-overlap queries -------------------------------------------------------------------------------
-// rtbvh_within_async's rules, one for one, and its place in the ev_query chain; [keys + sort], then
-// [sizes + scan], then [fill], all on the caller's stream.  Its count block is QUERY_OVERLAP_AT.
 rtbvh_status rtbvh_overlap_async(rtbvh_ctx* c, const rtbvh_box* dev_boxes, uint64_t n, uint64_t* dev_offsets,
                                  uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_OVERLAP_SORT | RTBVH_OVERLAP_COUNT | RTBVH_OVERLAP_TRIANGLE | RTBVH_OVERLAP_SIZES |
-                             RTBVH_OVERLAP_FILL;
-    constexpr uint32_t BOTH = RTBVH_OVERLAP_SIZES | RTBVH_OVERLAP_FILL;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: 2^31 boxes or more");
+    bool run;
+    TRY(list_rules(c, OVERLAP, mode, nullptr, dev_boxes, n, dev_offsets, dev_ids, capacity, &run));
     const bool sizes = !(mode & RTBVH_OVERLAP_FILL), fill = !(mode & RTBVH_OVERLAP_SIZES);
+    if (!run) return store_no_lists(c, dev_offsets, !sizes, stream);
     static_assert(sizeof(rtbvh_box) == 32 && sizeof(uint64_t) == sizeof(unsigned long long), "box query layouts");
-    if (n == 0) {
-        if (!dev_offsets || !sizes) return RTBVH_OK;
-        HIPC(c, hipSetDevice(c->cfg.device));
-        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
-        return RTBVH_OK;
-    }
-    if (!dev_boxes || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: NULL boxes or offsets");
-    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "overlap: NULL ids");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "overlap before build");
-    if (c->stale) return fail_stale(c, "overlap");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_OVERLAP_SORT) != 0, count = (mode & RTBVH_OVERLAP_COUNT) != 0;
     const bool tri = (mode & RTBVH_OVERLAP_TRIANGLE) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)));
-    const bool grow_scan = sizes && !c->d_qscan.has(scan_sums_words(N));
-    if (grow_sort || grow_scan) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort and scan in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        if (grow_sort) {
-            HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-        }
-        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_OVERLAP_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    need.scan = sizes ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_OVERLAP, count, s));
     OverlapArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_OVERLAP_AT);
     a.boxes = reinterpret_cast<const float4*>(dev_boxes);
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
     a.ids = dev_ids;
     a.capacity = capacity;
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_OVERLAP_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {   // one permutation for both passes
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_overlap_keys(a.boxes, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_ids = true;
-        launch_overlap(a, false, count, tri, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_ids = !sizes;
-        launch_overlap(a, true, count, tri, s);
-    }
-    rtbvh_status st = check_launch(c, "overlap kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->overlap_counted = true;
-    return st;
+    if (sort) a.perm = walk_order(c, launch_overlap_keys, a.boxes, N, s);
+    TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+        a.count_ids = count_items;
+        launch_overlap(a, fill_pass, count, tri, s);
+    }));
+    return leave_chain(c, K_OVERLAP, count, "overlap kernels", s);
 }
 
 rtbvh_status rtbvh_overlap_host(rtbvh_ctx* c, const rtbvh_box* boxes, uint64_t n, uint64_t* offsets, uint32_t* ids,
                                 uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_OVERLAP_FILL) != 0, sizes_only = (mode & RTBVH_OVERLAP_SIZES) != 0;
-    if (n == 0) {   // (nothing to stage)
-        const rtbvh_status st = rtbvh_overlap_async(c, boxes, 0, nullptr, ids, capacity, mode, nullptr);
-        if (!st && offsets && !fill_only) offsets[0] = 0;
-        return st;
+    bool run;
+    TRY(list_rules(c, OVERLAP, mode, nullptr, boxes, n, offsets, ids, capacity, &run));
+    if (!run) {   // (nothing to stage)
+        if (offsets && !(mode & RTBVH_OVERLAP_FILL)) offsets[0] = 0;
+        return RTBVH_OK;
     }
-    if (n >= (1ull << 31) || !boxes || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
-        !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_overlap_async(c, boxes, n, offsets, ids, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // offsets, then boxes: 8- and 16-B aligned
-    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_box)));
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
-    rtbvh_box* db = reinterpret_cast<rtbvh_box*>(d + off_bytes);
-    if (hipMemcpy(db, boxes, (size_t)n * sizeof(rtbvh_box), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "overlap_host: upload failed");
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "overlap_host: upload failed");
-    DevBuf<uint32_t> dids;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another tree or other boxes leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
-    TRY(rtbvh_overlap_async(c, db, n, doff, dids, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "overlap_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "overlap_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "overlap_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    return host_lists(c, OVERLAP, mode, boxes, (size_t)n * sizeof(rtbvh_box), n, offsets, ids, sizeof(uint32_t), capacity,
+                      [&](char* in, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_overlap_async(c, reinterpret_cast<const rtbvh_box*>(in), n, off,
+                                                     reinterpret_cast<uint32_t*>(items), cap, mode, nullptr);
+                      });
 }
 
-rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->overlap_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_OVERLAP_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_OVERLAP_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_overlap_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_OVERLAP, out); }
 
 // ---- self-collision queries ----------------------------------------------------------------------------
-// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain, with the tree's T leaves for
-// queries: [sizes + scan], then [fill], all on the caller's stream.  Its count block is QUERY_COLLIDE_AT.
+// The tree's T leaves are the queries: no walk order.
 rtbvh_status rtbvh_collide_async(rtbvh_ctx* c, uint64_t* dev_offsets, uint32_t* dev_ids, uint64_t capacity,
                                  uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_COLLIDE_COUNT | RTBVH_COLLIDE_TRIANGLE | RTBVH_COLLIDE_SIZES | RTBVH_COLLIDE_FILL |
-                             RTBVH_COLLIDE_SYMMETRIC;
-    constexpr uint32_t BOTH = RTBVH_COLLIDE_SIZES | RTBVH_COLLIDE_FILL;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: bad mode bits");
+    bool run;
+    TRY(list_rules(c, COLLIDE, mode, nullptr, nullptr, 0, dev_offsets, dev_ids, capacity, &run));
     const bool sizes = !(mode & RTBVH_COLLIDE_FILL), fill = !(mode & RTBVH_COLLIDE_SIZES);
-    if (!dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: NULL offsets");
-    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "collide: NULL ids");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "collide before build");
-    if (c->stale) return fail_stale(c, "collide");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool count = (mode & RTBVH_COLLIDE_COUNT) != 0, tri = (mode & RTBVH_COLLIDE_TRIANGLE) != 0;
     const bool sym = (mode & RTBVH_COLLIDE_SYMMETRIC) != 0;
     const uint32_t N = c->T;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sizes && !c->d_qscan.has(scan_sums_words(N))) {
-        // (as rtbvh_overlap_async: earlier queries scan in the old buffer)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_COLLIDE_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.scan = sizes ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_COLLIDE, count, s));
     CollideArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = N;
+    fill_tree(c, a, QUERY_COLLIDE_AT);
     a.idx = c->d_idx;
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
     a.ids = dev_ids;
     a.capacity = capacity;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_COLLIDE_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_ids = true;
-        launch_collide(a, false, count, tri, sym, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_ids = !sizes;
-        launch_collide(a, true, count, tri, sym, s);
-    }
-    rtbvh_status st = check_launch(c, "collide kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->collide_counted = true;
-    return st;
+    TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+        a.count_ids = count_items;
+        launch_collide(a, fill_pass, count, tri, sym, s);
+    }));
+    return leave_chain(c, K_COLLIDE, count, "collide kernels", s);
 }
 
 rtbvh_status rtbvh_collide_host(rtbvh_ctx* c, uint64_t* offsets, uint32_t* ids, uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_COLLIDE_FILL) != 0, sizes_only = (mode & RTBVH_COLLIDE_SIZES) != 0;
-    if (!offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) || !c->tree.built ||
-        c->stale)   // (the query's checks)
-        return rtbvh_collide_async(c, offsets, ids, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    const uint64_t n = c->T;
-    DevBuf<uint64_t> doff;
-    HIPC(c, doff.alloc((size_t)(n + 1)));
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "collide_host: upload failed");
-    DevBuf<uint32_t> dids;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another mode or tree leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
-    TRY(rtbvh_collide_async(c, doff, dids, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "collide_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "collide_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "collide_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(list_rules(c, COLLIDE, mode, nullptr, nullptr, 0, offsets, ids, capacity, &run));
+    return host_lists(c, COLLIDE, mode, nullptr, 0, c->T, offsets, ids, sizeof(uint32_t), capacity,
+                      [&](char*, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_collide_async(c, off, reinterpret_cast<uint32_t*>(items), cap, mode, nullptr);
+                      });
 }
 
-rtbvh_status rtbvh_collide_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->collide_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_COLLIDE_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_COLLIDE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_collide_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_COLLIDE, out); }
 
 // ---- triangle queries ----------------------------------------------------------------------------------
-// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain; [keys + sort], then
-// [sizes + scan], then [fill], all on the caller's stream.  rtbvh_cross_first_async is [keys + sort] and one launch,
-// with no scan.  Their count block is QUERY_CROSS_AT.
-namespace {
-// the tree, the queries, the walk order (sort: grows the shared sort buffers) and the counters of a k_cross launch
-rtbvh_status cross_args(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint32_t N, bool sort, bool grow_scan, bool count,
-                        hipStream_t s, CrossArgs& a) {
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    const bool grow_sort = sort && !(c->d_qsort.has(6 * (size_t)N) && c->d_qsort_scratch.has(sort_scratch_words(N)));
-    if (grow_sort || grow_scan) {
-        // (as rtbvh_overlap_async: earlier queries sort and scan in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        if (grow_sort) {
-            HIPC(c, c->d_qsort.reserve(6 * (size_t)N));
-            HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-        }
-        if (grow_scan) HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_CROSS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
-    a.tris = reinterpret_cast<const float4*>(dev_tris);
-    a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_CROSS_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {   // one permutation for every pass of the call
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_cross_keys(a.tris, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
-    return RTBVH_OK;
-}
-}  // namespace
-
+// rtbvh_cross_first_async is [keys + sort] and one launch, with no scan; it shares the count block.
 rtbvh_status rtbvh_cross_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, uint64_t* dev_offsets,
                                uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT | RTBVH_CROSS_SIZES | RTBVH_CROSS_FILL;
-    constexpr uint32_t BOTH = RTBVH_CROSS_SIZES | RTBVH_CROSS_FILL;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: 2^31 triangles or more");
+    bool run;
+    TRY(list_rules(c, CROSS, mode, nullptr, dev_tris, n, dev_offsets, dev_ids, capacity, &run));
     const bool sizes = !(mode & RTBVH_CROSS_FILL), fill = !(mode & RTBVH_CROSS_SIZES);
+    if (!run) return store_no_lists(c, dev_offsets, !sizes, stream);
     static_assert(sizeof(rtbvh_tri) == 48 && sizeof(uint64_t) == sizeof(unsigned long long), "triangle query layouts");
-    if (n == 0) {
-        if (!dev_offsets || !sizes) return RTBVH_OK;
-        HIPC(c, hipSetDevice(c->cfg.device));
-        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
-        return RTBVH_OK;
-    }
-    if (!dev_tris || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: NULL triangles or offsets");
-    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "cross: NULL ids");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "cross before build");
-    if (c->stale) return fail_stale(c, "cross");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_CROSS_SORT) != 0, count = (mode & RTBVH_CROSS_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
+    Need need;
+    need.sort = sort ? N : 0;
+    need.scan = sizes ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_CROSS, count, s));
     CrossArgs a{};
-    TRY(cross_args(c, dev_tris, N, sort, sizes && !c->d_qscan.has(scan_sums_words(N)), count, s, a));
+    fill_tree(c, a, QUERY_CROSS_AT);
+    a.tris = reinterpret_cast<const float4*>(dev_tris);
+    a.n = N;
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
     a.ids = dev_ids;
     a.capacity = capacity;
-    if (sizes) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-        a.count_ids = true;
-        launch_cross(a, CROSS_PASS_SIZES, count, s);
-        scan_offsets(a.offsets, N, c->d_qscan, s);
-    }
-    if (fill) {
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-        a.count_ids = !sizes;
-        launch_cross(a, CROSS_PASS_FILL, count, s);
-    }
-    rtbvh_status st = check_launch(c, "cross kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->cross_counted = true;
-    return st;
+    if (sort) a.perm = walk_order(c, launch_cross_keys, a.tris, N, s);
+    TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+        a.count_ids = count_items;
+        launch_cross(a, fill_pass ? CROSS_PASS_FILL : CROSS_PASS_SIZES, count, s);
+    }));
+    return leave_chain(c, K_CROSS, count, "cross kernels", s);
 }
 
 rtbvh_status rtbvh_cross_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, uint64_t* offsets, uint32_t* ids,
                               uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_CROSS_FILL) != 0, sizes_only = (mode & RTBVH_CROSS_SIZES) != 0;
-    if (n == 0) {   // (nothing to stage)
-        const rtbvh_status st = rtbvh_cross_async(c, tris, 0, nullptr, ids, capacity, mode, nullptr);
-        if (!st && offsets && !fill_only) offsets[0] = 0;
-        return st;
+    bool run;
+    TRY(list_rules(c, CROSS, mode, nullptr, tris, n, offsets, ids, capacity, &run));
+    if (!run) {   // (nothing to stage)
+        if (offsets && !(mode & RTBVH_CROSS_FILL)) offsets[0] = 0;
+        return RTBVH_OK;
     }
-    if (n >= (1ull << 31) || !tris || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
-        !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_cross_async(c, tris, n, offsets, ids, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // offsets, then triangles: 8- and 16-B aligned
-    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_tri)));
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
-    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d + off_bytes);
-    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_host: upload failed");
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_host: upload failed");
-    DevBuf<uint32_t> dids;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another tree or other triangles leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
-    TRY(rtbvh_cross_async(c, dt, n, doff, dids, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "cross_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    return host_lists(c, CROSS, mode, tris, (size_t)n * sizeof(rtbvh_tri), n, offsets, ids, sizeof(uint32_t), capacity,
+                      [&](char* in, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_cross_async(c, reinterpret_cast<const rtbvh_tri*>(in), n, off,
+                                                   reinterpret_cast<uint32_t*>(items), cap, mode, nullptr);
+                      });
 }
 
 rtbvh_status rtbvh_cross_first_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, uint32_t* dev_first,
                                      uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(RTBVH_CROSS_SORT | RTBVH_CROSS_COUNT)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: 2^31 triangles or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_tris || !dev_first) return fail(c, RTBVH_ERR_INVALID_ARG, "cross_first: NULL triangles or output");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "cross_first before build");
-    if (c->stale) return fail_stale(c, "cross_first");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    bool run;
+    TRY(record_rules(c, CROSS_FIRST, mode, nullptr, dev_tris, n, dev_first, &run));
+    if (!run) return RTBVH_OK;
     const bool sort = (mode & RTBVH_CROSS_SORT) != 0, count = (mode & RTBVH_CROSS_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_counts(c, K_CROSS, count, s));
     CrossArgs a{};
-    TRY(cross_args(c, dev_tris, (uint32_t)n, sort, false, count, s, a));
+    fill_tree(c, a, QUERY_CROSS_AT);
+    a.tris = reinterpret_cast<const float4*>(dev_tris);
+    a.n = N;
     a.first = dev_first;
     a.count_ids = true;
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
+    if (sort) a.perm = walk_order(c, launch_cross_keys, a.tris, N, s);
+    TRY(zero_work(c, s));
     launch_cross(a, CROSS_PASS_FIRST, count, s);
-    rtbvh_status st = check_launch(c, "cross_first kernel");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->cross_counted = true;
-    return st;
+    return leave_chain(c, K_CROSS, count, "cross_first kernel", s);
 }
 
 rtbvh_status rtbvh_cross_first_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, uint32_t* first, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !tris || !first || !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_cross_first_async(c, tris, n, first, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // triangles, then the output
-    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_tri) + sizeof(uint32_t))));
-    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d.h);
-    uint32_t* df = reinterpret_cast<uint32_t*>(d + (size_t)n * sizeof(rtbvh_tri));
-    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_first_host: upload failed");
-    TRY(rtbvh_cross_first_async(c, dt, n, df, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "cross_first_host: sync");
-    if (hipMemcpy(first, df, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "cross_first_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, CROSS_FIRST, mode, nullptr, tris, n, first, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, CROSS_FIRST.name, tris, (size_t)n * sizeof(rtbvh_tri), first, (size_t)n * sizeof(uint32_t),
+                        [&](char* in, char* out) {
+                            return rtbvh_cross_first_async(c, reinterpret_cast<const rtbvh_tri*>(in), n,
+                                                           reinterpret_cast<uint32_t*>(out), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_cross_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->cross_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_CROSS_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CROSS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_cross_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_CROSS, out); }
 
 // ---- clearance queries ---------------------------------------------------------------------------------
-// rtbvh_cross_first_async's rules, one for one, and its place in the ev_query chain: cross_args' waits, tree forms,
-// [keys + sort] and stack limit, then one launch.  The count block is its own (QUERY_CLEARANCE_AT); cross_args zeroes
-// the triangle queries' block for a counting call, so the counting is set up here.
+// The triangle queries' inputs and walk order, one launch, a count block of its own.
 rtbvh_status rtbvh_clearance_async(rtbvh_ctx* c, const rtbvh_tri* dev_tris, uint64_t n, float max_dist2,
                                    rtbvh_clearance* dev_out, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_CLEARANCE_SORT | RTBVH_CLEARANCE_COUNT))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: bad mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: 2^31 triangles or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_tris || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "clearance: NULL triangles or results");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "clearance before build");
-    if (c->stale) return fail_stale(c, "clearance");
+    bool run;
+    TRY(record_rules(c, CLEARANCE, mode, nullptr, dev_tris, n, dev_out, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_clearance) == 32, "clearance record layout");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_CLEARANCE_SORT) != 0, count = (mode & RTBVH_CLEARANCE_COUNT) != 0;
-    CrossArgs x{};
-    TRY(cross_args(c, dev_tris, (uint32_t)n, sort, false, false, s, x));
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_CLEARANCE_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    const uint32_t N = (uint32_t)n;
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
     ClearanceArgs a{};
-    a.inner = x.inner;
-    a.topo = x.topo;
-    a.nbox = x.nbox;
-    a.nb = x.nb;
-    a.leaf = x.leaf;
-    a.T = x.T;
-    a.tris = x.tris;
+    fill_tree(c, a, QUERY_CLEARANCE_AT);
+    a.tris = reinterpret_cast<const float4*>(dev_tris);
     a.max_dist2 = max_dist2;
     a.out = reinterpret_cast<float4*>(dev_out);
-    a.n = x.n;
-    a.perm = x.perm;
-    a.next = x.next;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_CLEARANCE_AT);
-    a.overflow = x.overflow;
-    a.stack_limit = x.stack_limit;
+    a.n = N;
+    if (sort) a.perm = walk_order(c, launch_cross_keys, a.tris, N, s);
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_CLEARANCE, count, s));
     launch_clearance(a, count, s);
-    rtbvh_status st = check_launch(c, "clearance kernel");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->clearance_counted = true;
-    return st;
+    return leave_chain(c, K_CLEARANCE, count, "clearance kernel", s);
 }
 
 rtbvh_status rtbvh_clearance_host(rtbvh_ctx* c, const rtbvh_tri* tris, uint64_t n, float max_dist2, rtbvh_clearance* out,
                                   uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !tris || !out || !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_clearance_async(c, tris, n, max_dist2, out, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // triangles, then the results: both 16-B aligned
-    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_tri) + sizeof(rtbvh_clearance))));
-    rtbvh_tri* dt = reinterpret_cast<rtbvh_tri*>(d.h);
-    rtbvh_clearance* dr = reinterpret_cast<rtbvh_clearance*>(d + (size_t)n * sizeof(rtbvh_tri));
-    if (hipMemcpy(dt, tris, (size_t)n * sizeof(rtbvh_tri), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "clearance_host: upload failed");
-    TRY(rtbvh_clearance_async(c, dt, n, max_dist2, dr, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "clearance_host: sync");
-    if (hipMemcpy(out, dr, (size_t)n * sizeof(rtbvh_clearance), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "clearance_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, CLEARANCE, mode, nullptr, tris, n, out, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, CLEARANCE.name, tris, (size_t)n * sizeof(rtbvh_tri), out, (size_t)n * sizeof(rtbvh_clearance),
+                        [&](char* in, char* res) {
+                            return rtbvh_clearance_async(c, reinterpret_cast<const rtbvh_tri*>(in), n, max_dist2,
+                                                         reinterpret_cast<rtbvh_clearance*>(res), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->clearance_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_CLEARANCE_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_CLEARANCE_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_CLEARANCE, out); }
 
 // ---- region queries --------------------------------------------------------------------------------------
-// rtbvh_overlap_async's rules, one for one, and its place in the ev_query chain (no sort: a region has no centre):
-// [the leaf-NaN word, once a tree], then [sizes + scan], then [fill], all on the caller's stream.  Its count block
-// is QUERY_REGION_AT.
+// No walk order (a region has no centre): [the leaf-NaN word, once a tree], then the two passes -- or, split, the
+// pieces' passes.
 rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, uint64_t n, uint64_t* dev_offsets,
                                 uint32_t* dev_ids, uint64_t capacity, uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    constexpr uint32_t ALL = RTBVH_REGION_COUNT | RTBVH_REGION_TRIANGLE | RTBVH_REGION_SIZES | RTBVH_REGION_FILL |
-                             RTBVH_REGION_NO_ACCEPT | RTBVH_REGION_SPLIT_AUTO;
-    constexpr uint32_t BOTH = RTBVH_REGION_SIZES | RTBVH_REGION_FILL;
-    if ((mode & ~ALL) || (mode & BOTH) == BOTH) return fail(c, RTBVH_ERR_INVALID_ARG, "region: bad mode bits");
     const uint32_t field = (mode >> RTBVH_REGION_SPLIT_SHIFT) & 15u;
-    if (field > REGION_SPLIT_MAX_SHIFT && field != 15u)
-        return fail(c, RTBVH_ERR_INVALID_ARG, "region: split field 13 or 14");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "region: 2^31 regions or more");
+    bool run;
+    TRY(list_rules(c, REGION, mode, field > REGION_SPLIT_MAX_SHIFT && field != 15u ? "region: split field 13 or 14" : nullptr,
+                   dev_regions, n, dev_offsets, dev_ids, capacity, &run));
     const bool sizes = !(mode & RTBVH_REGION_FILL), fill = !(mode & RTBVH_REGION_SIZES);
+    if (!run) return store_no_lists(c, dev_offsets, !sizes, stream);
     static_assert(sizeof(rtbvh_region) == 96, "region query layout");
     static_assert(REGION_SPLIT_MAX_PIECES == RTBVH_REGION_SPLIT_MAX_PIECES && REGION_SPLIT_MAX_SHIFT == 12,
                   "the split field's documented bounds");
-    if (n == 0) {
-        if (!dev_offsets || !sizes) return RTBVH_OK;
-        HIPC(c, hipSetDevice(c->cfg.device));
-        HIPC(c, hipMemsetAsync(dev_offsets, 0, sizeof(uint64_t), stream ? (hipStream_t)stream : c->stream));
-        return RTBVH_OK;
-    }
-    if (!dev_regions || !dev_offsets) return fail(c, RTBVH_ERR_INVALID_ARG, "region: NULL regions or offsets");
-    if (fill && capacity > 0 && !dev_ids) return fail(c, RTBVH_ERR_INVALID_ARG, "region: NULL ids");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "region before build");
-    if (c->stale) return fail_stale(c, "region");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool count = (mode & RTBVH_REGION_COUNT) != 0, tri = (mode & RTBVH_REGION_TRIANGLE) != 0;
     const uint32_t N = (uint32_t)n;
     // The split field is an upper limit: K = 2^kshift pieces a region, the largest with n * K <= the product bound
@@ -3409,41 +3145,26 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
     uint32_t kshift = field == 15u ? REGION_SPLIT_MAX_SHIFT : field;
     while (kshift > 0 && ((uint64_t)N << kshift) > REGION_SPLIT_MAX_PIECES) kshift--;
     const uint32_t slots = N << kshift;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (!c->ev_nan) HIPC(c, hipEventCreateWithFlags(c->ev_nan.out(), hipEventDisableTiming));
-    if (sizes && !c->d_qscan.has(scan_sums_words(N))) {
-        // (as rtbvh_overlap_async: earlier queries scan in the old buffer)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qscan.reserve(scan_sums_words(N)));
-    }
-    if (kshift && !(c->d_pieces.has(slots) && c->d_poff.has((size_t)slots + 1) &&
-                    c->d_pscan.has(scan_sums_words(slots)))) {
-        // (the first split query and each larger one: earlier ones still read the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_pieces.reserve(slots));
-        HIPC(c, c->d_poff.reserve((size_t)slots + 1));
-        HIPC(c, c->d_pscan.reserve(scan_sums_words(slots)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    uint32_t* nan_word = c->d_qscratch + QUERY_LEAF_NAN_AT;
-    if (c->nan_epoch != c->bins_epoch) {   // the first region query of this tree writes the word, behind the tree
+    QueryChain& q = c->q;
+    Need need;
+    need.scan = sizes ? N : 0;
+    need.pieces = kshift ? slots : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    // (behind enter_chain's hipSetDevice: an event of the context's device)
+    if (!q.ev_nan) HIPC(c, hipEventCreateWithFlags(q.ev_nan.out(), hipEventDisableTiming));
+    uint32_t* nan_word = q.scratch + QUERY_LEAF_NAN_AT;
+    if (q.nan_epoch != c->bins_epoch) {   // the first region query of this tree writes the word, behind the tree
         HIPC(c, hipMemsetAsync(nan_word, 0, sizeof(uint32_t), s));
         launch_leaf_nan(c->d_leaf, c->T, nan_word, s);
-        HIPC(c, hipEventRecord(c->ev_nan, s));
-        c->nan_epoch = c->bins_epoch;
+        HIPC(c, hipEventRecord(q.ev_nan, s));
+        q.nan_epoch = c->bins_epoch;
     } else {
-        HIPC(c, hipStreamWaitEvent(s, c->ev_nan, 0));   // (written on another stream, perhaps)
+        HIPC(c, hipStreamWaitEvent(s, q.ev_nan, 0));   // (written on another stream, perhaps)
     }
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REGION_AT, 0, sizeof(uint64_t) * REGION_COUNT_WORDS, s));
+    TRY(zero_counts(c, K_REGION, count, s));
     RegionArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_REGION_AT);
     a.rootbox = c->d_rootbox;
     a.regions = reinterpret_cast<const float4*>(dev_regions);
     a.offsets = reinterpret_cast<unsigned long long*>(dev_offsets);
@@ -3452,55 +3173,38 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
     a.n = N;
     a.accept = !(mode & RTBVH_REGION_NO_ACCEPT);
     a.leaf_nan = nan_word;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_REGION_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    const bool split_field = field != 0u;
-    if (count && split_field)
-        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_REGION_SPLIT_AT, 0, sizeof(uint64_t) * REGION_SPLIT_COUNT_WORDS, s));
+    const bool count_split = count && field != 0u;
+    TRY(zero_counts(c, K_REGION_SPLIT, count_split, s));
     if (kshift) {
         // [expansion], [piece sizes + scan], then the caller's offsets (not RTBVH_REGION_FILL: those are input) and
         // [piece fill]: a launch sequence fixed by (n, K, mode), all on the caller's stream
         RegionSplitArgs sa{};
-        sa.pieces = c->d_pieces;
-        sa.poff = c->d_poff;
+        sa.pieces = q.pieces;
+        sa.poff = q.poff;
         sa.kshift = kshift;
-        sa.split = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_REGION_SPLIT_AT);
+        sa.split = reinterpret_cast<unsigned long long*>(q.scratch + QUERY_REGION_SPLIT_AT);
         sa.r = a;
         launch_region_expand(sa, count, s);
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+        TRY(zero_work(c, s));
         sa.r.count_ids = sizes;
         launch_region_piece(sa, false, count, tri, s);
-        scan_offsets(sa.poff, slots, c->d_pscan, s);
+        scan_offsets(sa.poff, slots, q.pscan, s);
         if (sizes) launch_region_offsets(sa.poff, a.offsets, N, kshift, s);
         if (fill) {
-            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
+            TRY(zero_work(c, s));
             sa.r.count_ids = !sizes;
             launch_region_piece(sa, true, count, tri, s);
         }
     } else {
-        if (sizes) {
-            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-            a.count_ids = true;
-            launch_region(a, false, count, tri, s);
-            scan_offsets(a.offsets, N, c->d_qscan, s);
-        }
-        if (fill) {
-            HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));
-            a.count_ids = !sizes;
-            launch_region(a, true, count, tri, s);
-        }
+        TRY(two_passes(c, sizes, fill, a.offsets, N, s, [&](bool fill_pass, bool count_items) {
+            a.count_ids = count_items;
+            launch_region(a, fill_pass, count, tri, s);
+        }));
     }
-    rtbvh_status st = check_launch(c, "region kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->region_counted = true;
-    if (count && split_field && !st) {
-        c->split_counted = true;
-        c->split_k = 1ull << kshift;
+    const rtbvh_status st = leave_chain(c, K_REGION, count, "region kernels", s);
+    if (count_split && !st) {
+        q.counted[K_REGION_SPLIT] = true;
+        q.split_k = 1ull << kshift;
     }
     return st;
 }
@@ -3508,261 +3212,132 @@ rtbvh_status rtbvh_region_async(rtbvh_ctx* c, const rtbvh_region* dev_regions, u
 rtbvh_status rtbvh_region_host(rtbvh_ctx* c, const rtbvh_region* regions, uint64_t n, uint64_t* offsets, uint32_t* ids,
                                uint64_t capacity, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    const bool fill_only = (mode & RTBVH_REGION_FILL) != 0, sizes_only = (mode & RTBVH_REGION_SIZES) != 0;
-    if (n == 0) {   // (nothing to stage)
-        const rtbvh_status st = rtbvh_region_async(c, regions, 0, nullptr, ids, capacity, mode, nullptr);
-        if (!st && offsets && !fill_only) offsets[0] = 0;
-        return st;
+    const uint32_t field = (mode >> RTBVH_REGION_SPLIT_SHIFT) & 15u;
+    bool run;
+    TRY(list_rules(c, REGION, mode, field > REGION_SPLIT_MAX_SHIFT && field != 15u ? "region: split field 13 or 14" : nullptr,
+                   regions, n, offsets, ids, capacity, &run));
+    if (!run) {   // (nothing to stage)
+        if (offsets && !(mode & RTBVH_REGION_FILL)) offsets[0] = 0;
+        return RTBVH_OK;
     }
-    if (n >= (1ull << 31) || !regions || !offsets || (fill_only && sizes_only) || (!sizes_only && capacity > 0 && !ids) ||
-        !c->tree.built || c->stale)   // (the query's checks)
-        return rtbvh_region_async(c, regions, n, offsets, ids, capacity, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // offsets, then regions: 8- and 16-B aligned
-    const size_t off_bytes = ((size_t)(n + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    HIPC(c, d.alloc(off_bytes + (size_t)n * sizeof(rtbvh_region)));
-    uint64_t* doff = reinterpret_cast<uint64_t*>(d.h);
-    rtbvh_region* dr = reinterpret_cast<rtbvh_region*>(d + off_bytes);
-    if (hipMemcpy(dr, regions, (size_t)n * sizeof(rtbvh_region), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "region_host: upload failed");
-    if (fill_only && hipMemcpy(doff, offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "region_host: upload failed");
-    DevBuf<uint32_t> dids;   // (SIZES: none)
-    if (sizes_only) capacity = 0;
-    if (capacity) HIPC(c, dids.alloc((size_t)capacity));
-    if (capacity && fill_only)   // (offsets of another tree or other regions leave gaps: zeros, not what the allocation held)
-        HIPC(c, hipMemsetAsync(dids, 0, (size_t)capacity * sizeof(uint32_t), c->stream));
-    TRY(rtbvh_region_async(c, dr, n, doff, dids, capacity, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "region_host: sync");
-    if (!fill_only && hipMemcpy(offsets, doff, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "region_host: download failed");
-    const uint64_t m = offsets[n] < capacity ? offsets[n] : capacity;
-    if (m && hipMemcpy(ids, dids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "region_host: download failed");
-    return rtbvh_synchronize(c);   // (the results are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    return host_lists(c, REGION, mode, regions, (size_t)n * sizeof(rtbvh_region), n, offsets, ids, sizeof(uint32_t),
+                      capacity, [&](char* in, uint64_t* off, char* items, uint64_t cap) {
+                          return rtbvh_region_async(c, reinterpret_cast<const rtbvh_region*>(in), n, off,
+                                                    reinterpret_cast<uint32_t*>(items), cap, mode, nullptr);
+                      });
 }
 
-rtbvh_status rtbvh_region_counts(rtbvh_ctx* c, uint64_t out[6]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->region_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_REGION_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_REGION_AT, sizeof(uint64_t) * REGION_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_region_counts(rtbvh_ctx* c, uint64_t out[6]) { return kind_counts(c, K_REGION, out); }
 
 rtbvh_status rtbvh_region_split_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->split_counted) return fail(c, RTBVH_ERR_NOT_READY, "no counting region query with a split field yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    out[0] = c->split_k;
-    HIPC(c, hipMemcpy(out + 1, c->d_qscratch + QUERY_REGION_SPLIT_AT, sizeof(uint64_t) * REGION_SPLIT_COUNT_WORDS,
-                      hipMemcpyDeviceToHost));
+    if (!out) return RTBVH_ERR_INVALID_ARG;
+    TRY(kind_counts(c, K_REGION_SPLIT, out + 1));
+    out[0] = c->q.split_k;
     return RTBVH_OK;
 }
 
 // ---- k-nearest queries ---------------------------------------------------------------------------------
-// rtbvh_nearest_async's rules and its place in the ev_query chain; one walk, no second pass.  Its count block is
-// QUERY_KNN_AT.
+// One walk, no second pass.
 rtbvh_status rtbvh_knn_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, uint32_t k, rtbvh_pair* dev_pairs,
                              uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_KNN_SORT | RTBVH_KNN_COUNT))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "knn: unknown mode bits");
-    if (k == 0 || k > RTBVH_KNN_MAX_K) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: k must be 1 .. RTBVH_KNN_MAX_K");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: 2^31 points or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_points || !dev_pairs) return fail(c, RTBVH_ERR_INVALID_ARG, "knn: NULL points or pairs");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "knn before build");
-    if (c->stale) return fail_stale(c, "knn");
+    bool run;
+    TRY(record_rules(c, KNN, mode, k == 0 || k > RTBVH_KNN_MAX_K ? "knn: k must be 1 .. RTBVH_KNN_MAX_K" : nullptr,
+                     dev_points, n, dev_pairs, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_pair) == 8, "k-nearest record layouts");
     static_assert(RTBVH_KNN_MAX_K == KNN_MAX_K, "the largest list of k_knn");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_KNN_SORT) != 0, count = (mode & RTBVH_KNN_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_KNN_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_KNN, count, s));
     KnnArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_KNN_AT);
     a.points = reinterpret_cast<const float4*>(dev_points);
     a.pairs = reinterpret_cast<uint2*>(dev_pairs);
     a.n = N;
     a.k = k;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_KNN_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
+    if (sort) a.perm = walk_order(c, launch_nearest_keys, a.points, N, s);
     launch_knn(a, count, s);
-    rtbvh_status st = check_launch(c, "knn kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->knn_counted = true;
-    return st;
+    return leave_chain(c, K_KNN, count, "knn kernels", s);
 }
 
 rtbvh_status rtbvh_knn_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, uint32_t k, rtbvh_pair* pairs,
                             uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || k == 0 || k > RTBVH_KNN_MAX_K || !points || !pairs || !c->tree.built ||
-        c->stale)   // (nothing to stage: the query's checks)
-        return rtbvh_knn_async(c, points, n, k, pairs, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;
-    const size_t out_bytes = (size_t)n * k * sizeof(rtbvh_pair);
-    HIPC(c, d.alloc(out_bytes + (size_t)n * sizeof(rtbvh_point)));
-    rtbvh_pair* dk = reinterpret_cast<rtbvh_pair*>(d.h);
-    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + out_bytes);
-    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "knn_host: upload failed");
-    TRY(rtbvh_knn_async(c, dp, n, k, dk, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "knn_host: sync");
-    if (hipMemcpy(pairs, dk, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "knn_host: download failed");
-    return rtbvh_synchronize(c);   // (the lists are the best found when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, KNN, mode, k == 0 || k > RTBVH_KNN_MAX_K ? "knn: k must be 1 .. RTBVH_KNN_MAX_K" : nullptr, points,
+                     n, pairs, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, KNN.name, points, (size_t)n * sizeof(rtbvh_point), pairs, (size_t)n * k * sizeof(rtbvh_pair),
+                        [&](char* in, char* out) {
+                            return rtbvh_knn_async(c, reinterpret_cast<const rtbvh_point*>(in), n, k,
+                                                   reinterpret_cast<rtbvh_pair*>(out), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_knn_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->knn_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_KNN_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_KNN_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS, hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_knn_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_KNN, out); }
 
 // ---- signed-distance queries ---------------------------------------------------------------------------
-// rtbvh_nearest_async's rules and its place in the ev_query chain, as one link: the closest-point pass (k_nearest,
-// unless RTBVH_SIGNED_INSIDE_ONLY) and the ray pass (k_signed) over the same walk order, on the same stream.  Its count
-// blocks are QUERY_SIGNED_AT (the ray pass) and QUERY_SIGNED_NEAR_AT (the closest-point pass).
+// One link: the closest-point pass (k_nearest, unless RTBVH_SIGNED_INSIDE_ONLY) and the ray pass (k_signed) over the
+// same walk order, on the same stream.  Its count blocks are QUERY_SIGNED_AT (the ray pass) and
+// QUERY_SIGNED_NEAR_AT (the closest-point pass), zeroed together (INSIDE_ONLY: the second stays zero).
 rtbvh_status rtbvh_signed_async(rtbvh_ctx* c, const rtbvh_point* dev_points, uint64_t n, rtbvh_signed* dev_out,
                                 uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_SIGNED_SORT | RTBVH_SIGNED_COUNT | RTBVH_SIGNED_VOTE3 | RTBVH_SIGNED_INSIDE_ONLY))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "signed: unknown mode bits");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "signed: 2^31 points or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_points || !dev_out) return fail(c, RTBVH_ERR_INVALID_ARG, "signed: NULL points or results");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "signed before build");
-    if (c->stale) return fail_stale(c, "signed");
+    bool run;
+    TRY(record_rules(c, SIGNED, mode, nullptr, dev_points, n, dev_out, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_point) == 16 && sizeof(rtbvh_signed) == 32, "signed-distance record layouts");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_SIGNED_SORT) != 0, count = (mode & RTBVH_SIGNED_COUNT) != 0;
     const bool vote3 = (mode & RTBVH_SIGNED_VOTE3) != 0, near = !(mode & RTBVH_SIGNED_INSIDE_ONLY);
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
-        // (as RTBVH_KNN_SORT: earlier queries sort in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-    if (count)   // both passes' blocks (INSIDE_ONLY: the closest-point pass's stays zero)
-        HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_SIGNED_AT, 0, sizeof(uint64_t) * 2 * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_SIGNED, count, s));
     SignedArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_SIGNED_AT);
     a.points = reinterpret_cast<const float4*>(dev_points);
     a.out = reinterpret_cast<float4*>(dev_out);
     a.n = N;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_SIGNED_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_nearest_keys(a.points, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
+    if (sort) a.perm = walk_order(c, launch_nearest_keys, a.points, N, s);
     if (near) {   // the closest-point pass: rtbvh_nearest's kernel into the same records, in the same order
         NearestArgs na{};
-        na.inner = a.inner;
-        na.topo = a.topo;
-        na.nbox = a.nbox;
-        na.nb = a.nb;
-        na.leaf = a.leaf;
-        na.T = a.T;
+        fill_tree(c, na, QUERY_SIGNED_NEAR_AT);
         na.points = a.points;
         na.out = a.out;
         na.n = N;
         na.perm = a.perm;
-        na.next = a.next;
-        na.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_SIGNED_NEAR_AT);
-        na.overflow = a.overflow;
-        na.stack_limit = a.stack_limit;
         launch_nearest(na, count, s);
-        HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters, again
+        TRY(zero_work(c, s));   // the work counters, again
     }
     launch_signed(a, count, near, vote3, s);
-    rtbvh_status st = check_launch(c, "signed kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->signed_counted = true;
-    return st;
+    return leave_chain(c, K_SIGNED, count, "signed kernels", s);
 }
 
 rtbvh_status rtbvh_signed_host(rtbvh_ctx* c, const rtbvh_point* points, uint64_t n, rtbvh_signed* out, uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || !points || !out || !c->tree.built || c->stale)   // (nothing to stage: the query's checks)
-        return rtbvh_signed_async(c, points, n, out, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;
-    HIPC(c, d.alloc((size_t)n * (sizeof(rtbvh_point) + sizeof(rtbvh_signed))));
-    rtbvh_signed* dn = reinterpret_cast<rtbvh_signed*>(d.h);
-    rtbvh_point* dp = reinterpret_cast<rtbvh_point*>(d + (size_t)n * sizeof(rtbvh_signed));
-    if (hipMemcpy(dp, points, (size_t)n * sizeof(rtbvh_point), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "signed_host: upload failed");
-    TRY(rtbvh_signed_async(c, dp, n, dn, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "signed_host: sync");
-    if (hipMemcpy(out, dn, (size_t)n * sizeof(rtbvh_signed), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "signed_host: download failed");
-    return rtbvh_synchronize(c);   // (the records are complete when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, SIGNED, mode, nullptr, points, n, out, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, SIGNED.name, points, (size_t)n * sizeof(rtbvh_point), out, (size_t)n * sizeof(rtbvh_signed),
+                        [&](char* in, char* res) {
+                            return rtbvh_signed_async(c, reinterpret_cast<const rtbvh_point*>(in), n,
+                                                      reinterpret_cast<rtbvh_signed*>(res), mode, nullptr);
+                        });
 }
 
 rtbvh_status rtbvh_signed_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->signed_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_SIGNED_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
+    if (!out) return RTBVH_ERR_INVALID_ARG;
     uint64_t w[2 * QUERY_COUNT_WORDS];   // {points, inside, steps} of the ray pass, {points, found, steps} of the other
-    HIPC(c, hipMemcpy(w, c->d_qscratch + QUERY_SIGNED_AT, sizeof(w), hipMemcpyDeviceToHost));
+    TRY(kind_counts(c, K_SIGNED, w));
     out[0] = w[0];
     out[1] = w[1];
     out[2] = w[2] + w[QUERY_COUNT_WORDS + 2];
@@ -3771,96 +3346,49 @@ rtbvh_status rtbvh_signed_counts(rtbvh_ctx* c, uint64_t out[4]) {
 }
 
 // ---- first-k ray queries -------------------------------------------------------------------------------
-// rtbvh_knn_async's rules, one for one, with the ray queries' rays and sort keys; one walk, no second pass.  Its
-// count block is QUERY_KHITS_AT.
+// One walk, no second pass.
 rtbvh_status rtbvh_khits_async(rtbvh_ctx* c, const rtbvh_ray* dev_rays, uint64_t n, uint32_t k, rtbvh_hit* dev_hits,
                                uint32_t mode, void* stream) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (mode & ~(uint32_t)(RTBVH_KHITS_SORT | RTBVH_KHITS_COUNT))
-        return fail(c, RTBVH_ERR_INVALID_ARG, "khits: unknown mode bits");
-    if (k == 0 || k > RTBVH_KHITS_MAX_K) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: k must be 1 .. RTBVH_KHITS_MAX_K");
-    if (n >= (1ull << 31)) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: 2^31 rays or more");
-    if (n == 0) return RTBVH_OK;
-    if (!dev_rays || !dev_hits) return fail(c, RTBVH_ERR_INVALID_ARG, "khits: NULL rays or hits");
-    if (!c->tree.built) return fail(c, RTBVH_ERR_NOT_READY, "khits before build");
-    if (c->stale) return fail_stale(c, "khits");
+    bool run;
+    TRY(record_rules(c, KHITS, mode, k == 0 || k > RTBVH_KHITS_MAX_K ? "khits: k must be 1 .. RTBVH_KHITS_MAX_K" : nullptr,
+                     dev_rays, n, dev_hits, &run));
+    if (!run) return RTBVH_OK;
     static_assert(sizeof(rtbvh_ray) == 32 && sizeof(rtbvh_hit) == 16, "first-k record layouts");
     static_assert(RTBVH_KHITS_MAX_K == KHITS_MAX_K, "the largest list of k_khits");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool sort = (mode & RTBVH_KHITS_SORT) != 0, count = (mode & RTBVH_KHITS_COUNT) != 0;
     const uint32_t N = (uint32_t)n;
-    if (!c->d_qscratch) HIPC(c, c->d_qscratch.alloc(QUERY_ALLOC_WORDS));
-    if (!c->ev_query) HIPC(c, hipEventCreateWithFlags(c->ev_query.out(), hipEventDisableTiming));
-    if (sort && !(c->d_qsort.has(6 * (size_t)n) && c->d_qsort_scratch.has(sort_scratch_words(N)))) {
-        // (as RTBVH_QUERY_SORT: earlier queries sort in the old buffers)
-        HIPC(c, hipEventSynchronize(c->ev_query));
-        HIPC(c, c->d_qsort.reserve(6 * (size_t)n));
-        HIPC(c, c->d_qsort_scratch.reserve(sort_scratch_words(N)));
-    }
-    if (s != c->stream) HIPC(c, hipStreamWaitEvent(s, c->ev_built, 0));
-    if (c->query_busy) HIPC(c, hipStreamWaitEvent(s, c->ev_query, 0));
-    HIPC(c, hipMemsetAsync(c->d_qscratch, 0, sizeof(uint32_t) * QUERY_COUNTS_AT, s));   // the work counters
-    if (count) HIPC(c, hipMemsetAsync(c->d_qscratch + QUERY_KHITS_AT, 0, sizeof(uint64_t) * QUERY_COUNT_WORDS, s));
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_KHITS, count, s));
     KhitsArgs a{};
-    a.inner = c->d_rec;
-    a.topo = c->d_topo;
-    a.nbox = c->d_nbox;
-    a.nb = c->tree.wrote == NBOX;
-    a.leaf = c->d_leaf;
-    a.T = c->T;
+    fill_tree(c, a, QUERY_KHITS_AT);
     a.rays = reinterpret_cast<const float4*>(dev_rays);
     a.hits = reinterpret_cast<float4*>(dev_hits);
     a.n = N;
     a.k = k;
-    a.next = c->d_qscratch;
-    a.counts = reinterpret_cast<unsigned long long*>(c->d_qscratch + QUERY_KHITS_AT);
-    a.overflow = c->d_ovf;
-    const uint32_t lim = c->cfg.stack_limit;
-    a.stack_limit = lim && lim < (uint32_t)STACK_SIZE ? (int)lim : STACK_SIZE;
-    if (sort) {
-        uint32_t* q = c->d_qsort;
-        const size_t m = c->d_qsort.cap / 6;
-        launch_query_keys(a.rays, N, c->d_rootbox, q, q + m, s);
-        a.perm = radix_sort_pairs(q, q + m, q + 2 * m, q + 3 * m, q + 4 * m, q + 5 * m, N, 30, c->d_qsort_scratch, s).vals;
-    }
+    if (sort) a.perm = walk_order(c, launch_query_keys, a.rays, N, s);
     launch_khits(a, count, s);
-    rtbvh_status st = check_launch(c, "khits kernels");
-    HIPC(c, hipEventRecord(c->ev_query, s));
-    c->query_busy = true;
-    c->query_ovf = true;
-    if (count && !st) c->khits_counted = true;
-    return st;
+    return leave_chain(c, K_KHITS, count, "khits kernels", s);
 }
 
 rtbvh_status rtbvh_khits_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, uint32_t k, rtbvh_hit* hits,
                               uint32_t mode) {
     if (!c) return RTBVH_ERR_INVALID_ARG;
-    if (n == 0 || n >= (1ull << 31) || k == 0 || k > RTBVH_KHITS_MAX_K || !rays || !hits || !c->tree.built ||
-        c->stale)   // (nothing to stage: the query's checks)
-        return rtbvh_khits_async(c, rays, n, k, hits, mode, nullptr);
-    HIPC(c, hipSetDevice(c->cfg.device));
-    DevBuf<char> d;   // hits, then rays: both 16-B aligned
-    const size_t out_bytes = (size_t)n * k * sizeof(rtbvh_hit);
-    HIPC(c, d.alloc(out_bytes + (size_t)n * sizeof(rtbvh_ray)));
-    rtbvh_hit* dh = reinterpret_cast<rtbvh_hit*>(d.h);
-    rtbvh_ray* dr = reinterpret_cast<rtbvh_ray*>(d + out_bytes);
-    if (hipMemcpy(dr, rays, (size_t)n * sizeof(rtbvh_ray), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "khits_host: upload failed");
-    TRY(rtbvh_khits_async(c, dr, n, k, dh, mode, nullptr));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTBVH_ERR_HIP, "khits_host: sync");
-    if (hipMemcpy(hits, dh, out_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RTBVH_ERR_HIP, "khits_host: download failed");
-    return rtbvh_synchronize(c);   // (the lists are the best found when it reports RTBVH_ERR_STACK_OVERFLOW)
+    bool run;
+    TRY(record_rules(c, KHITS, mode, k == 0 || k > RTBVH_KHITS_MAX_K ? "khits: k must be 1 .. RTBVH_KHITS_MAX_K" : nullptr,
+                     rays, n, hits, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, KHITS.name, rays, (size_t)n * sizeof(rtbvh_ray), hits, (size_t)n * k * sizeof(rtbvh_hit),
+                        [&](char* in, char* out) {
+                            return rtbvh_khits_async(c, reinterpret_cast<const rtbvh_ray*>(in), n, k,
+                                                     reinterpret_cast<rtbvh_hit*>(out), mode, nullptr);
+                        });
 }
 
-rtbvh_status rtbvh_khits_counts(rtbvh_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return RTBVH_ERR_INVALID_ARG;
-    if (!c->khits_counted) return fail(c, RTBVH_ERR_NOT_READY, "no RTBVH_KHITS_COUNT query yet");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    HIPC(c, hipEventSynchronize(c->ev_query));
-    HIPC(c, hipMemcpy(out, c->d_qscratch + QUERY_KHITS_AT, sizeof(uint64_t) * QUERY_COUNT_WORDS, hipMemcpyDeviceToHost));
-    return RTBVH_OK;
-}
+rtbvh_status rtbvh_khits_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_KHITS, out); }
 
 }  // extern "C"

@@ -548,6 +548,88 @@ class Context:
         L = _L.lib()
         self._check(L.rtbvh_refit(self._h) if sync else L.rtbvh_refit_async(self._h))
 
+    # -- what the query methods share --
+    def _stream(self, stream, device):
+        """(stream, handle) of a query's `stream`: a torch stream or a hipStream_t handle; None: the current torch
+        stream on `device`.  Torch's legacy default stream (handle 0), which the library cannot name, is
+        synchronised here: the call then runs on the context stream (_enqueue)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        handle = int(getattr(stream, "cuda_stream", stream) or 0)
+        if handle == 0:
+            torch.cuda.default_stream(device).synchronize()
+        return stream, handle
+
+    def _enqueue(self, handle, entry, *args):
+        """One device entry, entry(ctx, *args, stream), on _stream's handle; the context stream (handle 0) is
+        synchronised behind it."""
+        self._check(entry(self._h, *args, ctypes.c_void_p(handle) if handle else None))
+        if handle == 0:
+            self.synchronize()
+
+    def _async(self, entry, stream, device, *args):
+        self._enqueue(self._stream(stream, device)[1], entry, *args)
+
+    def _lists(self, host, dev, inp, n, item, shape, tdtype, sizes, fill, mode, sizes_mode, capacity, sizes_only,
+               stream, on_device=None):
+        """A query that answers (offsets, items) in CSR form through its `host` or `dev` entry.  `inp`: the checked
+        queries, a numpy array (the host entry) or a CUDA tensor (the device entry), or None for the entries that
+        take none (then on_device says which); `n`: how many lists.  The items: numpy dtype `item` on the host, a
+        (capacity,) + `shape` tensor of torch dtype `tdtype` on the device.  With `capacity` one call in `mode`;
+        without, a call with the kind's `sizes` bit (in `sizes_mode`), one read of the total -- on the device path
+        one .item(), the only synchronisation -- and a call with its `fill` bit; sizes_only: the offsets alone."""
+        if on_device is None:
+            on_device = _is_tensor(inp)
+        if not on_device:
+            offsets = np.zeros(n + 1, np.uint64)
+            head = (self._h,) if inp is None else (self._h, ctypes.c_void_p(inp.ctypes.data), n)
+            head += (ctypes.c_void_p(offsets.ctypes.data),)
+            if capacity is not None:
+                items = np.zeros(int(capacity), item)
+                self._check(host(*head, ctypes.c_void_p(items.ctypes.data), len(items), mode))
+                return offsets, items[:min(int(offsets[n]), len(items))]
+            self._check(host(*head, None, 0, sizes_mode | sizes))
+            if sizes_only:
+                return offsets
+            items = np.zeros(int(offsets[n]), item)
+            self._check(host(*head, ctypes.c_void_p(items.ctypes.data), len(items), mode | fill))
+            return offsets, items
+        import torch
+        device = torch.device("cuda", self.device) if inp is None else inp.device
+        tdtype = getattr(torch, tdtype)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=device)
+        stream, handle = self._stream(stream, device)
+        head = () if inp is None else (ctypes.c_void_p(inp.data_ptr()), n)
+        head += (ctypes.c_void_p(offsets.data_ptr()),)
+
+        def call(items, m):
+            self._enqueue(handle, dev, *head, ctypes.c_void_p(items.data_ptr()) if items is not None and items.numel()
+                          else None, 0 if items is None else items.shape[0], m)
+
+        if capacity is not None:
+            items = torch.empty((int(capacity),) + shape, dtype=tdtype, device=device)
+            call(items, mode)
+            return offsets, items
+        call(None, sizes_mode | sizes)
+        if sizes_only:
+            return offsets
+        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=device)
+            with torch.cuda.stream(ts):
+                total = int(offsets[n].item())
+        else:
+            total = int(offsets[n].item())
+        items = torch.empty((total,) + shape, dtype=tdtype, device=device)
+        call(items, mode | fill)
+        return offsets, items
+
+    def _counts(self, name, fields):
+        """rtbvh_<name>_counts as a dict of `fields`."""
+        out = np.zeros(len(fields), np.uint64)
+        self._check(getattr(_L.lib(), f"rtbvh_{name}_counts")(self._h, _L.ptr(out)))
+        return dict(zip(fields, (int(v) for v in out)))
+
     # -- ray queries --
     def query(self, rays, mode: int = 0, out=None, stream=None):
         """rtbvh_query_async / rtbvh_query_host: the closest hit (or with QUERY_ANY any hit) of each ray, in the
@@ -578,30 +660,19 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 4) and
                   out.device == rays.device and out.is_contiguous()):
             raise ValueError(f"query: out must be a contiguous ({n}, 4) float32 tensor on {rays.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(rays.device).synchronize()
-        self._check(L.rtbvh_query_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
-                                        mode, ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_query_async, stream, rays.device, ctypes.c_void_p(rays.data_ptr()), n,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def query_counts(self) -> dict:
         """rtbvh_query_counts: rays, hits, internal and leaf visits of the last QUERY_COUNT query."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_query_counts(self._h, _L.ptr(out)))
-        return dict(zip(("rays", "hits", "internal_visits", "leaf_visits"), (int(v) for v in out)))
+        return self._counts("query", ("rays", "hits", "internal_visits", "leaf_visits"))
 
     def query_walk_counts(self) -> dict:
         """rtbvh_query_walk_counts: how the rays of the last QUERY_COUNT query were answered -- certified by the
         4-wide walk (QUERY_CERTIFIED), redone or uncovered (re-traced in the reference order), or fallback (a query
         that took the plain kernel for every ray).  The four sum to the query's rays."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_query_walk_counts(self._h, _L.ptr(out)))
-        return dict(zip(("certified", "redone", "uncovered", "fallback"), (int(v) for v in out)))
+        return self._counts("query_walk", ("certified", "redone", "uncovered", "fallback"))
 
     # -- closest-point queries --
     def nearest(self, points, max_dist2=float("inf"), mode: int = 0, out=None, stream=None):
@@ -634,24 +705,14 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and
                   out.device == pts.device and out.is_contiguous()):
             raise ValueError(f"nearest: out must be a contiguous ({n}, 8) float32 tensor on {pts.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(pts.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(pts.device).synchronize()
-        self._check(_L.lib().rtbvh_nearest_async(self._h, ctypes.c_void_p(pts.data_ptr()), n,
-                                                 ctypes.c_void_p(out.data_ptr()), mode,
-                                                 ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_nearest_async, stream, pts.device, ctypes.c_void_p(pts.data_ptr()), n,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def nearest_counts(self) -> dict:
         """rtbvh_nearest_counts: points, results found, internal-node and leaf steps of the last NEAREST_COUNT
         query (the ray queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_nearest_counts(self._h, _L.ptr(out)))
-        return dict(zip(("points", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("nearest", ("points", "found", "internal_steps", "leaf_steps"))
 
     # -- radius queries --
     def within(self, points, max_dist2=float("inf"), mode: int = 0, capacity=None, stream=None):
@@ -673,57 +734,14 @@ class Context:
             raise ValueError("within: WITHIN_SIZES and WITHIN_FILL are set by within itself")
         if capacity is not None and (int(capacity) != capacity or capacity < 0):
             raise ValueError(f"within: capacity must be a non-negative integer, got {capacity!r}")
-        n = len(pts)
         L = _L.lib()
-        if kind == "numpy":
-            offsets = np.zeros(n + 1, np.uint64)
-            p, o = ctypes.c_void_p(pts.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                pairs = np.zeros(int(capacity), _L.PAIR_DTYPE)
-                self._check(L.rtbvh_within_host(self._h, p, n, o, ctypes.c_void_p(pairs.ctypes.data), len(pairs), mode))
-                return offsets, pairs[:min(int(offsets[n]), len(pairs))]
-            self._check(L.rtbvh_within_host(self._h, p, n, o, None, 0, mode | _L.WITHIN_SIZES))
-            pairs = np.zeros(int(offsets[n]), _L.PAIR_DTYPE)
-            self._check(L.rtbvh_within_host(self._h, p, n, o, ctypes.c_void_p(pairs.ctypes.data), len(pairs),
-                                            mode | _L.WITHIN_FILL))
-            return offsets, pairs
-        import torch
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=pts.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(pts.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(pts.device).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        p, o = ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
-
-        def call(pairs, m):
-            self._check(L.rtbvh_within_async(self._h, p, n, o, ctypes.c_void_p(pairs.data_ptr()) if pairs is not None
-                                             and pairs.numel() else None, 0 if pairs is None else pairs.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            pairs = torch.empty((int(capacity), 2), dtype=torch.float32, device=pts.device)
-            call(pairs, mode)
-            return offsets, pairs
-        call(None, mode | _L.WITHIN_SIZES)
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=pts.device)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        pairs = torch.empty((total, 2), dtype=torch.float32, device=pts.device)
-        call(pairs, mode | _L.WITHIN_FILL)
-        return offsets, pairs
+        return self._lists(L.rtbvh_within_host, L.rtbvh_within_async, pts, len(pts), _L.PAIR_DTYPE, (2,), "float32",
+                           _L.WITHIN_SIZES, _L.WITHIN_FILL, mode, mode, capacity, False, stream)
 
     def within_counts(self) -> dict:
         """rtbvh_within_counts: points, pairs (the total), internal-node and leaf steps (summed over the passes) of
         the last WITHIN_COUNT query (the ray and closest-point counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_within_counts(self._h, _L.ptr(out)))
-        return dict(zip(("points", "pairs", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("within", ("points", "pairs", "internal_steps", "leaf_steps"))
 
     # -- k-nearest queries --
     def knn(self, points, k, max_dist2=float("inf"), mode: int = 0, out=None, stream=None):
@@ -757,24 +775,14 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, k, 2) and
                   out.device == pts.device and out.is_contiguous()):
             raise ValueError(f"knn: out must be a contiguous ({n}, {k}, 2) float32 tensor on {pts.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(pts.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(pts.device).synchronize()
-        self._check(_L.lib().rtbvh_knn_async(self._h, ctypes.c_void_p(pts.data_ptr()), n, k,
-                                             ctypes.c_void_p(out.data_ptr()), mode,
-                                             ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_knn_async, stream, pts.device, ctypes.c_void_p(pts.data_ptr()), n, k,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def knn_counts(self) -> dict:
         """rtbvh_knn_counts: points, pairs found, internal-node and leaf steps of the last KNN_COUNT query (the other
         queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_knn_counts(self._h, _L.ptr(out)))
-        return dict(zip(("points", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("knn", ("points", "found", "internal_steps", "leaf_steps"))
 
     # -- all-hits ray queries --
     def allhits(self, rays, mode: int = 0, capacity=None, stream=None, sizes_only: bool = False):
@@ -801,61 +809,15 @@ class Context:
             raise ValueError(f"allhits: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and (capacity is not None or mode & _L.ALLHITS_BY_T):
             raise ValueError("allhits: sizes_only takes no capacity and no ALLHITS_BY_T")
-        n = len(rays)
         L = _L.lib()
-        if kind == "numpy":
-            offsets = np.zeros(n + 1, np.uint64)
-            p, o = ctypes.c_void_p(rays.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                hits = np.zeros(int(capacity), _L.HIT_DTYPE)
-                self._check(L.rtbvh_allhits_host(self._h, p, n, o, ctypes.c_void_p(hits.ctypes.data), len(hits), mode))
-                return offsets, hits[:min(int(offsets[n]), len(hits))]
-            self._check(L.rtbvh_allhits_host(self._h, p, n, o, None, 0, (mode & ~_L.ALLHITS_BY_T) | _L.ALLHITS_SIZES))
-            if sizes_only:
-                return offsets
-            hits = np.zeros(int(offsets[n]), _L.HIT_DTYPE)
-            self._check(L.rtbvh_allhits_host(self._h, p, n, o, ctypes.c_void_p(hits.ctypes.data), len(hits),
-                                             mode | _L.ALLHITS_FILL))
-            return offsets, hits
-        import torch
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(rays.device).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        p, o = ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
-
-        def call(hits, m):
-            self._check(L.rtbvh_allhits_async(self._h, p, n, o, ctypes.c_void_p(hits.data_ptr()) if hits is not None
-                                              and hits.numel() else None, 0 if hits is None else hits.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            hits = torch.empty((int(capacity), 4), dtype=torch.float32, device=rays.device)
-            call(hits, mode)
-            return offsets, hits
-        call(None, (mode & ~_L.ALLHITS_BY_T) | _L.ALLHITS_SIZES)
-        if sizes_only:
-            return offsets
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=rays.device)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        hits = torch.empty((total, 4), dtype=torch.float32, device=rays.device)
-        call(hits, mode | _L.ALLHITS_FILL)
-        return offsets, hits
+        return self._lists(L.rtbvh_allhits_host, L.rtbvh_allhits_async, rays, len(rays), _L.HIT_DTYPE, (4,), "float32",
+                           _L.ALLHITS_SIZES, _L.ALLHITS_FILL, mode, mode & ~_L.ALLHITS_BY_T, capacity, sizes_only,
+                           stream)
 
     def allhits_counts(self) -> dict:
         """rtbvh_allhits_counts: rays, hits (the total), internal-node and leaf steps (summed over the passes) of
         the last ALLHITS_COUNT query (the other queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_allhits_counts(self._h, _L.ptr(out)))
-        return dict(zip(("rays", "hits", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("allhits", ("rays", "hits", "internal_steps", "leaf_steps"))
 
     # -- first-k ray queries --
     def khits(self, rays, k, mode: int = 0, out=None, stream=None):
@@ -890,24 +852,14 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, k, 4) and
                   out.device == rays.device and out.is_contiguous()):
             raise ValueError(f"khits: out must be a contiguous ({n}, {k}, 4) float32 tensor on {rays.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(rays.device).synchronize()
-        self._check(_L.lib().rtbvh_khits_async(self._h, ctypes.c_void_p(rays.data_ptr()), n, k,
-                                               ctypes.c_void_p(out.data_ptr()), mode,
-                                               ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_khits_async, stream, rays.device, ctypes.c_void_p(rays.data_ptr()), n, k,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def khits_counts(self) -> dict:
         """rtbvh_khits_counts: rays, hits found, internal-node and leaf steps of the last KHITS_COUNT query (the other
         queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_khits_counts(self._h, _L.ptr(out)))
-        return dict(zip(("rays", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("khits", ("rays", "found", "internal_steps", "leaf_steps"))
 
     # -- box-overlap queries --
     def overlap(self, boxes, hi=None, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
@@ -935,61 +887,14 @@ class Context:
             raise ValueError(f"overlap: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and capacity is not None:
             raise ValueError("overlap: sizes_only takes no capacity")
-        n = len(bx)
         L = _L.lib()
-        if kind == "numpy":
-            offsets = np.zeros(n + 1, np.uint64)
-            p, o = ctypes.c_void_p(bx.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                ids = np.zeros(int(capacity), np.uint32)
-                self._check(L.rtbvh_overlap_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
-                return offsets, ids[:min(int(offsets[n]), len(ids))]
-            self._check(L.rtbvh_overlap_host(self._h, p, n, o, None, 0, mode | _L.OVERLAP_SIZES))
-            if sizes_only:
-                return offsets
-            ids = np.zeros(int(offsets[n]), np.uint32)
-            self._check(L.rtbvh_overlap_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
-                                             mode | _L.OVERLAP_FILL))
-            return offsets, ids
-        import torch
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=bx.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(bx.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(bx.device).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        p, o = ctypes.c_void_p(bx.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
-
-        def call(ids, m):
-            self._check(L.rtbvh_overlap_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
-                                              and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            ids = torch.empty(int(capacity), dtype=torch.int32, device=bx.device)
-            call(ids, mode)
-            return offsets, ids
-        call(None, mode | _L.OVERLAP_SIZES)
-        if sizes_only:
-            return offsets
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=bx.device)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        ids = torch.empty(total, dtype=torch.int32, device=bx.device)
-        call(ids, mode | _L.OVERLAP_FILL)
-        return offsets, ids
+        return self._lists(L.rtbvh_overlap_host, L.rtbvh_overlap_async, bx, len(bx), np.uint32, (), "int32",
+                           _L.OVERLAP_SIZES, _L.OVERLAP_FILL, mode, mode, capacity, sizes_only, stream)
 
     def overlap_counts(self) -> dict:
         """rtbvh_overlap_counts: boxes, ids (the total), internal-node and leaf steps (summed over the passes) of
         the last OVERLAP_COUNT query (the other queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_overlap_counts(self._h, _L.ptr(out)))
-        return dict(zip(("boxes", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("overlap", ("boxes", "ids", "internal_steps", "leaf_steps"))
 
     # -- region queries --
     def region(self, regions, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
@@ -1016,71 +921,22 @@ class Context:
             raise ValueError(f"region: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and capacity is not None:
             raise ValueError("region: sizes_only takes no capacity")
-        n = len(rg)
         L = _L.lib()
-        if kind == "numpy":
-            offsets = np.zeros(n + 1, np.uint64)
-            p, o = ctypes.c_void_p(rg.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                ids = np.zeros(int(capacity), np.uint32)
-                self._check(L.rtbvh_region_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
-                return offsets, ids[:min(int(offsets[n]), len(ids))]
-            self._check(L.rtbvh_region_host(self._h, p, n, o, None, 0, mode | _L.REGION_SIZES))
-            if sizes_only:
-                return offsets
-            ids = np.zeros(int(offsets[n]), np.uint32)
-            self._check(L.rtbvh_region_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
-                                            mode | _L.REGION_FILL))
-            return offsets, ids
-        import torch
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=rg.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(rg.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(rg.device).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        p, o = ctypes.c_void_p(rg.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
-
-        def call(ids, m):
-            self._check(L.rtbvh_region_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
-                                             and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            ids = torch.empty(int(capacity), dtype=torch.int32, device=rg.device)
-            call(ids, mode)
-            return offsets, ids
-        call(None, mode | _L.REGION_SIZES)
-        if sizes_only:
-            return offsets
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=rg.device)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        ids = torch.empty(total, dtype=torch.int32, device=rg.device)
-        call(ids, mode | _L.REGION_FILL)
-        return offsets, ids
+        return self._lists(L.rtbvh_region_host, L.rtbvh_region_async, rg, len(rg), np.uint32, (), "int32",
+                           _L.REGION_SIZES, _L.REGION_FILL, mode, mode, capacity, sizes_only, stream)
 
     def region_counts(self) -> dict:
         """rtbvh_region_counts: regions, ids (the total), internal-node steps, leaf steps and subtrees taken whole
         (summed over the passes) and the ids that came from those subtrees, of the last REGION_COUNT query (the
         other queries' counts are kept apart)."""
-        out = np.zeros(6, np.uint64)
-        self._check(_L.lib().rtbvh_region_counts(self._h, _L.ptr(out)))
-        return dict(zip(("regions", "ids", "internal_steps", "leaf_steps", "accepted_subtrees", "accepted_ids"),
-                        (int(v) for v in out)))
+        return self._counts("region",
+                            ("regions", "ids", "internal_steps", "leaf_steps", "accepted_subtrees", "accepted_ids"))
 
     def region_split_counts(self) -> dict:
         """rtbvh_region_split_counts: of the last REGION_COUNT query with a split field, the K used (1: the plain
         path ran), the non-empty pieces, the node tests of the expansion and the longest single piece walk in
         steps."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_region_split_counts(self._h, _L.ptr(out)))
-        return dict(zip(("k", "pieces", "expansion_tests", "longest_piece_steps"), (int(v) for v in out)))
+        return self._counts("region_split", ("k", "pieces", "expansion_tests", "longest_piece_steps"))
 
     # -- self-collision queries --
     def collide(self, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None, device: bool = False):
@@ -1106,57 +962,12 @@ class Context:
             raise ValueError(f"collide: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and capacity is not None:
             raise ValueError("collide: sizes_only takes no capacity")
-        n = self.num_tris
+        if not device and stream is not None:
+            raise ValueError("collide: a stream goes with device=True")
         L = _L.lib()
-        if not device:
-            if stream is not None:
-                raise ValueError("collide: a stream goes with device=True")
-            offsets = np.zeros(n + 1, np.uint64)
-            o = ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                ids = np.zeros(int(capacity), np.uint32)
-                self._check(L.rtbvh_collide_host(self._h, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
-                return offsets, ids[:min(int(offsets[n]), len(ids))]
-            self._check(L.rtbvh_collide_host(self._h, o, None, 0, mode | _L.COLLIDE_SIZES))
-            if sizes_only:
-                return offsets
-            ids = np.zeros(int(offsets[n]), np.uint32)
-            self._check(L.rtbvh_collide_host(self._h, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
-                                             mode | _L.COLLIDE_FILL))
-            return offsets, ids
-        import torch
-        dev = torch.device("cuda", self.device)
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(dev).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        o = ctypes.c_void_p(offsets.data_ptr())
-
-        def call(ids, m):
-            self._check(L.rtbvh_collide_async(self._h, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
-                                              and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            ids = torch.empty(int(capacity), dtype=torch.int32, device=dev)
-            call(ids, mode)
-            return offsets, ids
-        call(None, mode | _L.COLLIDE_SIZES)
-        if sizes_only:
-            return offsets
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=dev)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        ids = torch.empty(total, dtype=torch.int32, device=dev)
-        call(ids, mode | _L.COLLIDE_FILL)
-        return offsets, ids
+        return self._lists(L.rtbvh_collide_host, L.rtbvh_collide_async, None, self.num_tris, np.uint32, (), "int32",
+                           _L.COLLIDE_SIZES, _L.COLLIDE_FILL, mode, mode, capacity, sizes_only, stream,
+                           on_device=device)
 
     def collide_pairs(self, triangle: bool = True) -> np.ndarray:
         """The member pairs as a (P, 2) uint32 array of triangle ids (i, j), expanded from collide()'s default CSR
@@ -1168,9 +979,7 @@ class Context:
     def collide_counts(self) -> dict:
         """rtbvh_collide_counts: triangles, entries (the total), internal-node and leaf steps (summed over the
         passes) of the last COLLIDE_COUNT query (the other queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_collide_counts(self._h, _L.ptr(out)))
-        return dict(zip(("triangles", "entries", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("collide", ("triangles", "entries", "internal_steps", "leaf_steps"))
 
     # -- triangle queries --
     def cross(self, tris, mode: int = 0, capacity=None, sizes_only: bool = False, stream=None):
@@ -1197,56 +1006,11 @@ class Context:
             raise ValueError(f"cross: capacity must be a non-negative integer, got {capacity!r}")
         if sizes_only and capacity is not None:
             raise ValueError("cross: sizes_only takes no capacity")
-        n = len(tr)
+        if kind == "numpy" and stream is not None:
+            raise ValueError("cross: a stream goes with a torch tensor of triangles")
         L = _L.lib()
-        if kind == "numpy":
-            if stream is not None:
-                raise ValueError("cross: a stream goes with a torch tensor of triangles")
-            offsets = np.zeros(n + 1, np.uint64)
-            p, o = ctypes.c_void_p(tr.ctypes.data), ctypes.c_void_p(offsets.ctypes.data)
-            if capacity is not None:
-                ids = np.zeros(int(capacity), np.uint32)
-                self._check(L.rtbvh_cross_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids), mode))
-                return offsets, ids[:min(int(offsets[n]), len(ids))]
-            self._check(L.rtbvh_cross_host(self._h, p, n, o, None, 0, mode | _L.CROSS_SIZES))
-            if sizes_only:
-                return offsets
-            ids = np.zeros(int(offsets[n]), np.uint32)
-            self._check(L.rtbvh_cross_host(self._h, p, n, o, ctypes.c_void_p(ids.ctypes.data), len(ids),
-                                           mode | _L.CROSS_FILL))
-            return offsets, ids
-        import torch
-        offsets = torch.empty(n + 1, dtype=torch.int64, device=tr.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(tr.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(tr.device).synchronize()
-        s = ctypes.c_void_p(handle) if handle else None
-        p, o = ctypes.c_void_p(tr.data_ptr()), ctypes.c_void_p(offsets.data_ptr())
-
-        def call(ids, m):
-            self._check(L.rtbvh_cross_async(self._h, p, n, o, ctypes.c_void_p(ids.data_ptr()) if ids is not None
-                                            and ids.numel() else None, 0 if ids is None else ids.shape[0], m, s))
-            if handle == 0:
-                self.synchronize()
-
-        if capacity is not None:
-            ids = torch.empty(int(capacity), dtype=torch.int32, device=tr.device)
-            call(ids, mode)
-            return offsets, ids
-        call(None, mode | _L.CROSS_SIZES)
-        if sizes_only:
-            return offsets
-        if handle:   # (.item() copies on the current stream: make that the one the sizes ran on)
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device=tr.device)
-            with torch.cuda.stream(ts):
-                total = int(offsets[n].item())
-        else:
-            total = int(offsets[n].item())
-        ids = torch.empty(total, dtype=torch.int32, device=tr.device)
-        call(ids, mode | _L.CROSS_FILL)
-        return offsets, ids
+        return self._lists(L.rtbvh_cross_host, L.rtbvh_cross_async, tr, len(tr), np.uint32, (), "int32",
+                           _L.CROSS_SIZES, _L.CROSS_FILL, mode, mode, capacity, sizes_only, stream)
 
     def cross_first(self, tris, mode: int = 0, out=None, stream=None):
         """rtbvh_cross_first_async / rtbvh_cross_first_host: for each query triangle the first id of its cross() list
@@ -1276,16 +1040,8 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.int32 and tuple(out.shape) == (n,) and
                   out.device == tr.device and out.is_contiguous()):
             raise ValueError(f"cross_first: out must be a contiguous ({n},) int32 tensor on {tr.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(tr.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(tr.device).synchronize()
-        self._check(_L.lib().rtbvh_cross_first_async(self._h, ctypes.c_void_p(tr.data_ptr()), n,
-                                                     ctypes.c_void_p(out.data_ptr()), mode,
-                                                     ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_cross_first_async, stream, tr.device, ctypes.c_void_p(tr.data_ptr()), n,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def cross_pairs(self, tris) -> np.ndarray:
@@ -1301,9 +1057,7 @@ class Context:
         """rtbvh_cross_counts: queries, ids (the total; for cross_first the queries with a member), internal-node and
         leaf steps (summed over the passes) of the last CROSS_COUNT query (the other queries' counts are kept
         apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_cross_counts(self._h, _L.ptr(out)))
-        return dict(zip(("queries", "ids", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("cross", ("queries", "ids", "internal_steps", "leaf_steps"))
 
     # -- clearance queries --
     def clearance(self, tris, max_dist2=float("inf"), mode: int = 0, stream=None):
@@ -1337,24 +1091,14 @@ class Context:
             return out
         import torch
         out = torch.empty((n, 8), dtype=torch.float32, device=tr.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(tr.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(tr.device).synchronize()
-        self._check(_L.lib().rtbvh_clearance_async(self._h, ctypes.c_void_p(tr.data_ptr()), n, bound,
-                                                   ctypes.c_void_p(out.data_ptr()), mode,
-                                                   ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_clearance_async, stream, tr.device, ctypes.c_void_p(tr.data_ptr()), n, bound,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     def clearance_counts(self) -> dict:
         """rtbvh_clearance_counts: queries, results found, internal-node and leaf steps of the last CLEARANCE_COUNT
         query (the other queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_clearance_counts(self._h, _L.ptr(out)))
-        return dict(zip(("queries", "found", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("clearance", ("queries", "found", "internal_steps", "leaf_steps"))
 
     # -- signed-distance queries --
     def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
@@ -1388,16 +1132,8 @@ class Context:
         elif not (_is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and
                   out.device == pts.device and out.is_contiguous()):
             raise ValueError(f"signed: out must be a contiguous ({n}, 8) float32 tensor on {pts.device}")
-        if stream is None:
-            stream = torch.cuda.current_stream(pts.device)
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        if handle == 0:
-            torch.cuda.default_stream(pts.device).synchronize()
-        self._check(_L.lib().rtbvh_signed_async(self._h, ctypes.c_void_p(pts.data_ptr()), n,
-                                                ctypes.c_void_p(out.data_ptr()), mode,
-                                                ctypes.c_void_p(handle) if handle else None))
-        if handle == 0:
-            self.synchronize()
+        self._async(_L.lib().rtbvh_signed_async, stream, pts.device, ctypes.c_void_p(pts.data_ptr()), n,
+                    ctypes.c_void_p(out.data_ptr()), mode)
         return out
 
     @staticmethod
@@ -1458,9 +1194,7 @@ class Context:
     def signed_counts(self) -> dict:
         """rtbvh_signed_counts: points, points inside, internal-node and leaf steps (summed over all the walks) of
         the last SIGNED_COUNT query (the other queries' counts are kept apart)."""
-        out = np.zeros(4, np.uint64)
-        self._check(_L.lib().rtbvh_signed_counts(self._h, _L.ptr(out)))
-        return dict(zip(("points", "inside", "internal_steps", "leaf_steps"), (int(v) for v in out)))
+        return self._counts("signed", ("points", "inside", "internal_steps", "leaf_steps"))
 
     # -- outputs --
     def read_framebuffer(self) -> np.ndarray:
