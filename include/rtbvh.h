@@ -355,8 +355,9 @@ rtbvh_status rtbvh_synchronize(rtbvh_ctx* ctx);
  * rtbvh_compute_bvh, rtbvh_trace*, rtbvh_trace_band_async, rtbvh_trace_tiles, rtbvh_query_*, rtbvh_nearest_*,
  * rtbvh_within_*, rtbvh_knn_*, rtbvh_allhits_*, rtbvh_overlap_*, rtbvh_signed_*, rtbvh_khits_* and
  * rtbvh_verify_walk return RTBVH_ERR_NOT_READY, as do rtbvh_collide_async, rtbvh_collide_host, rtbvh_cross_async,
- * rtbvh_cross_host, rtbvh_cross_first_async, rtbvh_cross_first_host, rtbvh_clearance_async and
- * rtbvh_clearance_host, and the rtbvh_read_* calls return the last build's tree.
+ * rtbvh_cross_host, rtbvh_cross_first_async, rtbvh_cross_first_host, rtbvh_clearance_async,
+ * rtbvh_clearance_host, rtbvh_sweep_async and rtbvh_sweep_host, and the rtbvh_read_* calls return the last build's
+ * tree.
  * RTBVH_ERR_INVALID_ARG: NULL positions, a stride below 3, first + count past the scene's vertices;
  * RTBVH_ERR_NOT_READY before rtbvh_set_scene; count == 0 is RTBVH_OK and touches nothing. */
 rtbvh_status rtbvh_update_vertices_async(rtbvh_ctx* ctx, const float* dev_positions, uint32_t pos_stride,
@@ -484,6 +485,12 @@ rtbvh_status rtbvh_query_walk_counts(rtbvh_ctx* ctx, uint64_t out[4]);
  *    answer; all three vertices NaN: every candidate's d is a NaN, dist2 is a NaN, never an answer.  dist2 = +inf
  *    satisfies max_dist2 = +inf.  A point or a needle is a valid query, and a valid scene triangle: a zero-length
  *    segment has A or E = 0, its quotients are NaN or infinite, and clamp01 and the box clamps make points of them.
+ *  - Sweeps.  A triangle without area has nn = 0 (or a den of 0 or NaN): the face candidate never counts, and a
+ *    needle or a point is still touched through its edges and vertices -- a zero-length edge has ee = 0, so a_ = 0
+ *    fails `a_ > 0`, and its end points answer as vertices.  The start overlap is the closest-point section's dist2,
+ *    with its rules: a triangle with a non-finite vertex stands at a corner of its leaf box there, and feature 1 can
+ *    report it.  A NaN fails every test of the candidates as written; all three vertices NaN: the leaf box is NaN,
+ *    (B) fails, never a member.  An infinite leaf box passes (B) where the slabs are not NaN.
  *  - Boxes and triangles (overlap, cross, collide).  (B) compares the leaf box: a NaN fails it, an infinity meets.
  *    In RTBVH_OVERLAP_TRIANGLE a NaN separates nothing, so a non-finite triangle whose box meets the query box is
  *    listed, and a needle is decided by its edge axes.  In collide a triangle with one non-finite vertex keeps a
@@ -1012,6 +1019,119 @@ rtbvh_status rtbvh_clearance_host(rtbvh_ctx* ctx, const rtbvh_tri* tris, uint64_
 /* The last RTBVH_CLEARANCE_COUNT query (waits for it): queries, results found, internal-node steps, leaf steps.  Its
  * own words: the other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting clearance query. */
 rtbvh_status rtbvh_clearance_counts(rtbvh_ctx* ctx, uint64_t out[4]);
+
+/* ---- sphere-sweep queries: the first contact of a moving sphere ---------------------------------
+ * (No reference equivalent; the sweep of the raycast / overlap / sweep triad of collision queries.)  A sphere of
+ * radius r starts with its centre at c and moves along d: centre(t) = c + t * d.  The query asks for the first t in
+ * [0, t_max] at which it touches the mesh, where, and on which feature.  c, d and r live in the space the BVH was
+ * built in, as the rays'; d need not be unit, and r is a distance of that space (an object-space distance only under
+ * an identity WVP, as for the closest-point queries).
+ * Specified operation for operation, in fp32 without contraction, dots as (x*x' + y*y') + z*z', cross as in the
+ * self-collision section, `/` and sqrtf the IEEE (correctly rounded) results, independently of the tree and of the
+ * walk: the answer is the brute force over all scene triangles, byte for byte.
+ * A scene triangle x is its leaf record (a, e1, e2, [lo, hi]); V0 = a, V1 = fl(a + e1), V2 = fl(a + e2) and the
+ * segments S0 = (a, e1), S1 = (a, e2), S2 = (V1, fl(e2 - e1)) are the clearance and self-collision sections'.
+ * For a sweep (c, d, r, t_max) let dd = dot(d, d) and inv = 1 / d per component.
+ * There is no walk and no result for: a non-finite component of c or d; d all zero; !(r >= 0) or r infinite;
+ * !(t_max >= 0) (NaN included).  -0 counts as +0 for r and t_max; t_max = +inf: no limit.
+ *  (B) The leaf box grown by r, [fl(lo - r), fl(hi + r)] per component, passes the all-hits box rule with t_max: with
+ *      t0 = (fl(lo - r) - c) * inv, t1 = (fl(hi + r) - c) * inv per axis and mn, mx as in that section's (B), the box
+ *      passes iff 0 <= mx && mn <= mx && !(mn > t_max).  mn_x is that mn.
+ *  (T) The pair's t, point and feature:
+ *      1. Start overlap.  dist2 and q of the closest-point section for the point c (its clamp into [lo, hi] included).
+ *         If dist2 <= r*r: t = +0, point = q, feature = 1, and nothing else is tried.
+ *      2. Otherwise the first smallest of up to seven candidates, in the order face, S0, S1, S2, V0, V1, V2.  A
+ *         candidate counts only if every "needs" below holds and 0 <= t && t <= t_max; a NaN fails each comparison
+ *         as written; a later candidate replaces an earlier one only if its t is strictly smaller.
+ *         Face (feature 2):
+ *             n = cross(e1, e2);  nn = dot(n, n);                       needs nn > 0
+ *             s = dot(n, c - a);  if s < 0: n = -n, s = -s
+ *             ln = sqrtf(nn);  h = s - r*ln;  dn = dot(n, d);           needs dn < 0 && h >= 0
+ *             t = h / (-dn);  p = (c + d*t) - n*(r/ln);  ap = p - a
+ *             d1 = dot(e1, ap);  d2 = dot(e2, ap);  e11 = dot(e1, e1);  e12 = dot(e1, e2);  e22 = dot(e2, e2)
+ *             den = e11*e22 - e12*e12;  u = (e22*d1 - e12*d2) / den;  v = (e11*d2 - e12*d1) / den
+ *                                                                       needs u >= 0 && v >= 0 && u + v <= 1
+ *             point = p
+ *         Edge (A, E) = Si (feature 3 + i):
+ *             m = c - A;  ee = dot(E, E);  md = dot(m, E);  nd = dot(d, E);  mm = dot(m, m);  mdd = dot(m, d)
+ *             a_ = ee*dd - nd*nd;  k = mm - r*r;  c_ = ee*k - md*md;  b_ = ee*mdd - nd*md
+ *                                                                       needs a_ > 0 && c_ > 0 && b_ < 0
+ *             disc = b_*b_ - a_*c_;                                     needs disc >= 0
+ *             t = c_ / (sqrtf(disc) - b_)        (the root without cancellation)
+ *             s_ = md + t*nd;                                           needs 0 <= s_ && s_ <= ee
+ *             point = A + E*(s_/ee)
+ *         Vertex V = Vi (feature 6 + i):
+ *             m = c - V;  b = dot(m, d);  cc = dot(m, m) - r*r;         needs cc > 0 && b < 0
+ *             disc = b*b - dd*cc;                                       needs disc >= 0
+ *             t = cc / (sqrtf(disc) - b);  point = V
+ *      Every reported point is then clamped per component, point = fmaxf(lo, fminf(hi, point)), as the closest-point
+ *      section's q.
+ * x is a MEMBER of the sweep iff (B) holds and (T) yields a t.  Its key is tk_x = fmaxf(t_x, mn_x) + 0 (fmaxf drops a
+ * NaN; the + 0 makes +0 of a -0, which h = -0 can give at r = 0): 0 <= tk_x <= t_max, so its bits order as the floats.
+ * The result is the member with the smallest (tk bits, triangle id), reported with its genuine t, point and feature,
+ * never with tk: khits at k = 1 with another leaf test.  The box is in the key for khits' reason: t_x can be a few
+ * ulps below mn_x, and only a key that no box around x undershoots can be walked with pruning.
+ * In exact arithmetic the smallest candidate IS the first contact: each candidate is a moment the centre is exactly
+ * r from a point of the triangle's plane, of an edge's line or of a vertex, kept only where that point lies on the
+ * triangle; the first such moment touches the face's interior, an edge's interior or a vertex.  r = 0 is allowed: a
+ * thin ray by these formulas (no EPSILON; a triangle is hit from either side); no equality with rtbvh_query_*'s bits
+ * is promised.  Limits: a contact within rounding of two features reports either, the same on every tree; the clamped
+ * key orders contacts whose t differ by rounding by their leaf boxes' entries, as khits does.
+ * Exactness.  Rounding is monotone, so the grown boxes nest as the boxes do; the slab test is monotone in the box, so
+ * every tree box B around x, grown, passes the first two slab conditions when x's grown leaf box does, and starts at
+ * mn(B) <= mn_x <= tk_x.  The walk enters a box, grown by r, iff 0 <= mx && mn <= mx && !(mn > bound), bound = t_max
+ * until a member is found, then the best tk (non-strict: ties are visited for the id tie-break).  A leaf's own box is
+ * tested by (B) as written.  A child's box is tested without the axes whose inv is infinite: there 0 * inf = NaN
+ * drops a face at exactly c_k, so a flat grown leaf box passes (B) while a box around it fails -- the one case where
+ * the slab test is not monotone (the all-hits queries' exception, where the ray test never accepts such a triangle;
+ * a sphere does touch it, through its edges).  Without those axes the test is monotone, enters every box (B) enters,
+ * and its mn is not above (B)'s; with no axis left (|d_k| <= 2^-128 on all three) every child is entered.  So visiting order, tree form, refit or rebuild and RTBVH_SWEEP_SORT cannot change a
+ * byte. */
+/* A sweep, 32 B (two 16-B words): rtbvh_ray's layout with the reserved word as the radius. */
+typedef struct {
+    float origin[3];
+    float t_max;
+    float direction[3];
+    float radius;
+} rtbvh_sweep;
+/* A result, 32 B (two 16-B words): t of first contact (centre = origin + t * direction), the contact point on the
+ * triangle (in its leaf box), the triangle's id in triangle order, and the feature touched: 1 the sphere overlaps the
+ * triangle at t = 0 (point: the closest point to the origin), 2 the face, 3..5 the edge segment S0..S2, 6..8 the
+ * vertex V0..V2.  A miss: t = -1, point = 0, tri = 0xFFFFFFFF, feature = 0.  reserved = 0 always. */
+typedef struct {
+    float t;
+    float point[3];
+    uint32_t tri;
+    uint32_t feature;
+    uint32_t reserved[2];
+} rtbvh_sweep_hit;
+enum {
+    RTBVH_SWEEP_ANY = 1u << 0,   /* does it touch anything within t_max: the walk ends at the first member, whose own
+                                    record {t, point, tri, feature} is the result (which member is unspecified).
+                                    Whether a sweep hits equals the default mode's answer */
+    RTBVH_SWEEP_SORT = 1u << 1,  /* walk the sweeps in RTBVH_QUERY_SORT's order of (direction octant, origin Morton):
+                                    same results, each at its sweep's own index */
+    RTBVH_SWEEP_COUNT = 1u << 2  /* count sweeps, hits and steps for rtbvh_sweep_counts (slower) */
+    /* (every other bit is rejected) */
+};
+/* n sweeps at dev_sweeps and n results at dev_hits (device memory of the context's device, 16-B aligned), result k for
+ * sweep k, enqueued on `stream` (hipStream_t, NULL = the context stream).  The rules of rtbvh_nearest_async hold one
+ * for one: the walk reads the tree the last build or refit wrote (node records, or the topology and node boxes; never
+ * the quantized nodes); the call waits for the last build and only enqueues; the library orders it among all the other
+ * queries, which share the query scratch, and the next build waits for it; the first RTBVH_SWEEP_SORT query and each
+ * larger one grow the sort's buffers (shared with the other queries' SORT), which waits on the host.
+ * n == 0 returns RTBVH_OK and touches nothing; RTBVH_ERR_NOT_READY before a build and after a vertex update until
+ * the next build or refit; RTBVH_ERR_INVALID_ARG for NULL pointers with n > 0, unknown mode bits, and n >= 2^31.
+ * A walk that hits rtbvh_config.stack_limit ends with the best found so far -- a genuine member's record, its key not
+ * below the true best -- and the next synchronising call returns RTBVH_ERR_STACK_OVERFLOW. */
+rtbvh_status rtbvh_sweep_async(rtbvh_ctx* ctx, const rtbvh_sweep* dev_sweeps, uint64_t n, rtbvh_sweep_hit* dev_hits,
+                               uint32_t mode, void* stream);
+/* Host-memory convenience wrapper of the above (synchronous, on the context stream). */
+rtbvh_status rtbvh_sweep_host(rtbvh_ctx* ctx, const rtbvh_sweep* sweeps, uint64_t n, rtbvh_sweep_hit* hits,
+                              uint32_t mode);
+/* The last RTBVH_SWEEP_COUNT query (waits for it): sweeps, hits, internal-node steps, leaf steps.  Its own words: the
+ * other queries' counts keep theirs.  RTBVH_ERR_NOT_READY before any counting sweep query. */
+rtbvh_status rtbvh_sweep_counts(rtbvh_ctx* ctx, uint64_t out[4]);
 
 /* ---- box-overlap queries: every triangle that meets an axis-aligned box the caller chose --------
  * (No reference equivalent.)  The boxes live in the space the BVH was built in, as the other queries' inputs.  The

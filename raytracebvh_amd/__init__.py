@@ -17,12 +17,13 @@ from ._lib import (ALLHITS_BY_T, ALLHITS_COUNT, ALLHITS_FILL, ALLHITS_SIZES, ALL
                    CLEARANCE_COUNT, CLEARANCE_DTYPE, CLEARANCE_SORT,
                    REGION_COUNT, REGION_DTYPE, REGION_FILL, REGION_NO_ACCEPT, REGION_SIZES, REGION_TRIANGLE,
                    REGION_SPLIT_AUTO, REGION_SPLIT_MAX_PIECES, REGION_SPLIT_SHIFT,
+                   SWEEP_ANY, SWEEP_COUNT, SWEEP_DTYPE, SWEEP_HIT_DTYPE, SWEEP_SORT,
                    QUERY_CERTIFIED, QUERY_CLOSEST, QUERY_COUNT, QUERY_SORT, RAY_DTYPE, WITHIN_COUNT, WITHIN_FILL, WITHIN_SIZES,
                    WITHIN_SORT, RtbvhError, lib)
 from .graphics import (Context, Graphics, box_region, check_cross_tris, check_nearest_points, check_overlap_boxes,
-                       check_query_rays, check_region_planes, check_vertex_array, comm_destroy, comm_unique_id,
-                       frustum_planes, make_boxes, make_points, make_rays, make_regions, make_tris, region_split, save_bmp,
-                       slab_region)
+                       check_query_rays, check_region_planes, check_sweeps, check_vertex_array, comm_destroy,
+                       comm_unique_id, frustum_planes, make_boxes, make_points, make_rays, make_regions, make_sweeps,
+                       make_tris, region_split, save_bmp, slab_region)
 from .scene import (EYE_REFERENCE, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_UP, Scene, camera_look, camera_orbit,
                     camera_reference, load_npz, load_obj, synthetic)
 
@@ -49,4 +50,5 @@ __all__ = ["Context", "Graphics", "Scene", "load_obj", "load_npz", "synthetic", 
            "REGION_DTYPE", "REGION_COUNT", "REGION_TRIANGLE", "REGION_SIZES", "REGION_FILL", "REGION_NO_ACCEPT",
            "REGION_SPLIT_SHIFT", "REGION_SPLIT_AUTO", "REGION_SPLIT_MAX_PIECES", "region_split",
            "make_regions", "box_region", "slab_region", "frustum_planes", "check_region_planes",
+           "SWEEP_DTYPE", "SWEEP_HIT_DTYPE", "SWEEP_ANY", "SWEEP_SORT", "SWEEP_COUNT", "make_sweeps", "check_sweeps",
            "check_query_rays", "check_vertex_array"]

@@ -57,6 +57,7 @@ EXPORTS = [
     "rtbvh_cross_async", "rtbvh_cross_host", "rtbvh_cross_first_async", "rtbvh_cross_first_host", "rtbvh_cross_counts",
     "rtbvh_clearance_async", "rtbvh_clearance_host", "rtbvh_clearance_counts",
     "rtbvh_region_async", "rtbvh_region_host", "rtbvh_region_counts", "rtbvh_region_split_counts",
+    "rtbvh_sweep_async", "rtbvh_sweep_host", "rtbvh_sweep_counts",
     "rtbvh_update_vertices_async", "rtbvh_update_vertices_host", "rtbvh_refit_async", "rtbvh_refit",
 ]
 COMM_ID_BYTES = 128
@@ -116,6 +117,13 @@ assert REGION_DTYPE.itemsize == 96
 REGION_COUNT, REGION_TRIANGLE, REGION_SIZES, REGION_FILL, REGION_NO_ACCEPT = 4, 8, 16, 32, 64   # RTBVH_REGION_*
 # the split field of a region mode (bits 16..19: at most 2^v pieces a region, 15 automatic) and the bound on n * K
 REGION_SPLIT_SHIFT, REGION_SPLIT_AUTO, REGION_SPLIT_MAX_PIECES = 16, 15 << 16, 1 << 20
+# rtbvh_sweep (32 B: RAY_DTYPE with the radius in the reserved word) and rtbvh_sweep_hit (32 B), include/rtbvh.h; a
+# miss: t = -1, point = 0, tri = 0xFFFFFFFF, feature = 0
+SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "<f4", (3,)), ("radius", "<f4")])
+SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", (3,)), ("tri", "<u4"), ("feature", "<u4"),
+                            ("reserved", "<u4", (2,))])
+assert SWEEP_DTYPE.itemsize == 32 and SWEEP_HIT_DTYPE.itemsize == 32
+SWEEP_ANY, SWEEP_SORT, SWEEP_COUNT = 1, 2, 4   # RTBVH_SWEEP_*
 
 
 class Config(ctypes.Structure):
@@ -291,6 +299,9 @@ def lib() -> ctypes.CDLL:
         "rtbvh_khits_async": (i32, [vp, vp, u64, u32, vp, u32, vp]),
         "rtbvh_khits_host": (i32, [vp, vp, u64, u32, vp, u32]),
         "rtbvh_khits_counts": (i32, [vp, vp]),
+        "rtbvh_sweep_async": (i32, [vp, vp, u64, vp, u32, vp]),
+        "rtbvh_sweep_host": (i32, [vp, vp, u64, vp, u32]),
+        "rtbvh_sweep_counts": (i32, [vp, vp]),
         "rtbvh_allhits_async": (i32, [vp, vp, u64, vp, vp, u64, u32, vp]),
         "rtbvh_allhits_host": (i32, [vp, vp, u64, vp, vp, u64, u32]),
         "rtbvh_allhits_counts": (i32, [vp, vp]),

@@ -218,7 +218,7 @@ struct LastTrace {
 // What a caller gets when several arguments are wrong is fixed too: query_rules.
 enum Kind : uint32_t {
     K_QUERY, K_NEAREST, K_WITHIN, K_ALLHITS, K_OVERLAP, K_KNN, K_SIGNED, K_KHITS, K_COLLIDE, K_CROSS, K_CLEARANCE,
-    K_REGION, K_REGION_SPLIT, K_KINDS
+    K_REGION, K_REGION_SPLIT, K_SWEEP, K_KINDS
 };
 struct KindRow {
     uint32_t at, words;        // its count block: QueryChain::scratch + at, 8-byte words
@@ -238,6 +238,7 @@ constexpr KindRow KINDS[K_KINDS] = {
     {QUERY_CLEARANCE_AT, QUERY_COUNT_WORDS, "no RTBVH_CLEARANCE_COUNT query yet"},
     {QUERY_REGION_AT, REGION_COUNT_WORDS, "no RTBVH_REGION_COUNT query yet"},
     {QUERY_REGION_SPLIT_AT, REGION_SPLIT_COUNT_WORDS, "no counting region query with a split field yet"},
+    {QUERY_SWEEP_AT, QUERY_COUNT_WORDS, "no RTBVH_SWEEP_COUNT query yet"},
 };
 static_assert(QUERY_SIGNED_NEAR_AT == QUERY_SIGNED_AT + 2 * QUERY_COUNT_WORDS, "the signed queries' two blocks are one");
 struct QueryChain {
@@ -2442,6 +2443,8 @@ constexpr RecordKind KNN{"knn", "points", "knn: unknown mode bits", "knn: NULL p
                          RTBVH_KNN_SORT | RTBVH_KNN_COUNT};
 constexpr RecordKind KHITS{"khits", "rays", "khits: unknown mode bits", "khits: NULL rays or hits",
                            RTBVH_KHITS_SORT | RTBVH_KHITS_COUNT};
+constexpr RecordKind SWEEP{"sweep", "sweeps", "sweep: unknown mode bits", "sweep: NULL sweeps or hits",
+                           RTBVH_SWEEP_ANY | RTBVH_SWEEP_SORT | RTBVH_SWEEP_COUNT};
 constexpr RecordKind SIGNED{"signed", "points", "signed: unknown mode bits", "signed: NULL points or results",
                             RTBVH_SIGNED_SORT | RTBVH_SIGNED_COUNT | RTBVH_SIGNED_VOTE3 | RTBVH_SIGNED_INSIDE_ONLY};
 constexpr RecordKind CROSS_FIRST{"cross_first", "triangles", "cross_first: bad mode bits",
@@ -3390,5 +3393,47 @@ rtbvh_status rtbvh_khits_host(rtbvh_ctx* c, const rtbvh_ray* rays, uint64_t n, u
 }
 
 rtbvh_status rtbvh_khits_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_KHITS, out); }
+
+// ---- sphere-sweep queries ------------------------------------------------------------------------------
+// One walk, as the closest-point queries'; the walk order is the ray queries' (a sweep is a ray's two words).
+rtbvh_status rtbvh_sweep_async(rtbvh_ctx* c, const rtbvh_sweep* dev_sweeps, uint64_t n, rtbvh_sweep_hit* dev_hits,
+                               uint32_t mode, void* stream) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    bool run;
+    TRY(record_rules(c, SWEEP, mode, nullptr, dev_sweeps, n, dev_hits, &run));
+    if (!run) return RTBVH_OK;
+    static_assert(sizeof(rtbvh_sweep) == 32 && sizeof(rtbvh_sweep_hit) == 32, "sweep record layouts");
+    const bool sort = (mode & RTBVH_SWEEP_SORT) != 0, count = (mode & RTBVH_SWEEP_COUNT) != 0;
+    const uint32_t N = (uint32_t)n;
+    Need need;
+    need.sort = sort ? N : 0;
+    hipStream_t s;
+    TRY(enter_chain(c, stream, need, &s));
+    TRY(zero_work(c, s));
+    TRY(zero_counts(c, K_SWEEP, count, s));
+    SweepArgs a{};
+    fill_tree(c, a, QUERY_SWEEP_AT);
+    a.sweeps = reinterpret_cast<const float4*>(dev_sweeps);
+    a.hits = reinterpret_cast<float4*>(dev_hits);
+    a.n = N;
+    if (sort) a.perm = walk_order(c, launch_query_keys, a.sweeps, N, s);
+    launch_sweep(a, (mode & RTBVH_SWEEP_ANY) != 0, count, s);
+    return leave_chain(c, K_SWEEP, count, "sweep kernels", s);
+}
+
+rtbvh_status rtbvh_sweep_host(rtbvh_ctx* c, const rtbvh_sweep* sweeps, uint64_t n, rtbvh_sweep_hit* hits,
+                              uint32_t mode) {
+    if (!c) return RTBVH_ERR_INVALID_ARG;
+    bool run;
+    TRY(record_rules(c, SWEEP, mode, nullptr, sweeps, n, hits, &run));
+    if (!run) return RTBVH_OK;
+    return host_records(c, SWEEP.name, sweeps, (size_t)n * sizeof(rtbvh_sweep), hits,
+                        (size_t)n * sizeof(rtbvh_sweep_hit), [&](char* in, char* out) {
+                            return rtbvh_sweep_async(c, reinterpret_cast<const rtbvh_sweep*>(in), n,
+                                                     reinterpret_cast<rtbvh_sweep_hit*>(out), mode, nullptr);
+                        });
+}
+
+rtbvh_status rtbvh_sweep_counts(rtbvh_ctx* c, uint64_t out[4]) { return kind_counts(c, K_SWEEP, out); }
 
 }  // extern "C"

@@ -693,7 +693,7 @@ constexpr uint32_t QUERY_LEAF_NAN_AT = QUERY_REGION_AT + 2 * REGION_COUNT_WORDS;
 // longest piece walk), behind the leaf-NaN word
 constexpr uint32_t REGION_SPLIT_COUNT_WORDS = 3;
 constexpr uint32_t QUERY_REGION_SPLIT_AT = QUERY_LEAF_NAN_AT + 2;
-constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_REGION_SPLIT_AT + 2 * REGION_SPLIT_COUNT_WORDS;
+constexpr uint32_t QUERY_REGION_SPLIT_END = QUERY_REGION_SPLIT_AT + 2 * REGION_SPLIT_COUNT_WORDS;
 static_assert(QUERY_REGION_AT % 2 == 0 && QUERY_REGION_SPLIT_AT % 2 == 0, "the count block's 8-byte words");
 void launch_region(const RegionArgs& a, bool fill, bool count, bool tri, hipStream_t s);
 
@@ -723,5 +723,30 @@ void launch_region_offsets(const unsigned long long* poff, unsigned long long* o
                            hipStream_t s);
 // *word (zeroed by the caller) = 1 if any of the T leaf records holds a NaN in its box words 10..15
 void launch_leaf_nan(const float4* leaf, uint32_t T, uint32_t* word, hipStream_t s);
+
+// ---- sphere-sweep queries (trace.hip k_sweep; rtbvh_sweep_async) -------------
+// Sweeps (two float4 each: {origin, t_max}, {direction, radius}) on the same tree forms, and one rtbvh_sweep_hit
+// (two float4: {t, point}, {tri, feature, 0, 0}) stored per sweep at its own index.
+struct SweepArgs {
+    const Inner* inner;       // as QueryArgs
+    const uint4* topo;
+    const float* nbox;
+    bool nb;
+    const float4* leaf;
+    uint32_t T;
+    const float4* sweeps;     // [2n]
+    float4* hits;             // [2n]
+    uint32_t n;
+    const uint32_t* perm;     // walk order (RTBVH_SWEEP_SORT), or null
+    uint32_t* next;           // NEXT_SEGS zeroed work counters NEXT_STRIDE words apart
+    unsigned long long* counts;     // RTBVH_SWEEP_COUNT: [4] sweeps, hits, internal-node steps, leaf steps (zeroed)
+    unsigned long long* overflow;   // the context's overflow word
+    int stack_limit;          // <= STACK_SIZE
+};
+// the sweep queries' own count block, at the end of the scratch block (behind the split region queries')
+constexpr uint32_t QUERY_SWEEP_AT = QUERY_REGION_SPLIT_END;
+constexpr uint32_t QUERY_ALLOC_WORDS = QUERY_SWEEP_AT + 2 * QUERY_COUNT_WORDS;   // the whole scratch block
+static_assert(QUERY_SWEEP_AT % 2 == 0, "the count block's 8-byte words");
+void launch_sweep(const SweepArgs& a, bool any, bool count, hipStream_t s);
 
 }  // namespace rtbvh

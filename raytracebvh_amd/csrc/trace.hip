@@ -4903,7 +4903,269 @@ __global__ __launch_bounds__(BLOCK, CLEARANCE_WAVES) void k_clearance(ClearanceA
     }
 }
 
+// ---- sphere-sweep queries (rtbvh_sweep_async): the first contact of a moving sphere --------------------------
+// For each sweep (c, d, r, t_max) the member with the smallest (tk bits, triangle id), tk = fmaxf(t, mn) + 0 with mn
+// the slab entry of the member's own leaf box grown by r: k_khits at k = 1 with another leaf test and every box grown
+// by r.  include/rtbvh.h has the formulas -- the start overlap through triangle_dist2, unchanged, then the first
+// smallest of seven candidates (face, three edge segments, three vertices) -- and DESIGN.md 5q why the walk returns
+// the brute-force answer bit for bit: growing rounds monotonically, so the grown boxes nest as the boxes do, no
+// grown box around a member's leaf box starts above its tk, and a box is entered iff it passes the first two slab
+// conditions and !(mn > bound), bound = t_max until a member is found, then the best tk -- a leaf's own box by (B)
+// itself, a child's box by (B) without the axes of an infinite 1 / d (the node branch below has why).
+// k_khits' frame without the LDS list: the best key, its leaf slot (w.bl), its feature and its genuine t live in
+// registers; the winner's point is recomputed at the end from its leaf record by the same functions on the same
+// inputs (the edge candidates' s_/ee and the walk's point clamps are then never computed in the walk).
+// Plain fp32 as specified: no fma, no fast intrinsics, every `/` and sqrtf the IEEE result.  The seven candidates run
+// as one loop that is not unrolled, so one candidate's intermediates are live at a time; SWEEP_WAVES is chosen from
+// the instances' register counts.
+#ifndef RTBVH_SWEEP_WAVES   // (an A/B build sets another launch bound: EXTRA=-DRTBVH_SWEEP_WAVES=<n>)
+#define RTBVH_SWEEP_WAVES 6
+#endif
+constexpr uint32_t SWEEP_WAVES = RTBVH_SWEEP_WAVES;
+// Candidate k of the header's list (0 the face, 1..3 the segments S0..S2, 4..6 the vertices V0..V2): its t, or a
+// NaN where one of its "needs" fails; POINT: its point as well, before the clamp.
+template <bool POINT>
+__device__ __forceinline__ float sweep_candidate(int k, f3 c, f3 d, float dd, float r, f3 a, f3 e1, f3 e2, f3& pt) {
+    const float none = __uint_as_float(0x7FC00000u);
+    if (k == 0) {
+        f3 n = cross(e1, e2);
+        const float nn = dot(n, n);
+        if (!(nn > 0.f)) return none;
+        float s = dot(n, sub(c, a));
+        if (s < 0.f) {
+            n = mk(-n.x, -n.y, -n.z);
+            s = -s;
+        }
+        const float ln = sqrtf(nn), h = s - r * ln, dn = dot(n, d);
+        if (!(dn < 0.f && h >= 0.f)) return none;
+        const float t = h / (-dn);
+        const f3 p = sub(add(c, mul(d, t)), mul(n, r / ln)), ap = sub(p, a);
+        const float d1 = dot(e1, ap), d2 = dot(e2, ap);
+        const float e11 = dot(e1, e1), e12 = dot(e1, e2), e22 = dot(e2, e2);
+        const float den = e11 * e22 - e12 * e12;
+        const float u = (e22 * d1 - e12 * d2) / den, v = (e11 * d2 - e12 * d1) / den;
+        if (!(u >= 0.f && v >= 0.f && u + v <= 1.f)) return none;
+        if (POINT) pt = p;
+        return t;
+    }
+    const f3 v1 = add(a, e1);
+    if (k <= 3) {
+        const f3 A = k == 3 ? v1 : a, E = k == 1 ? e1 : k == 2 ? e2 : sub(e2, e1);
+        const f3 m = sub(c, A);
+        const float ee = dot(E, E), md = dot(m, E), nd = dot(d, E), mm = dot(m, m), mdd = dot(m, d);
+        const float a_ = ee * dd - nd * nd, k_ = mm - r * r, c_ = ee * k_ - md * md, b_ = ee * mdd - nd * md;
+        if (!(a_ > 0.f && c_ > 0.f && b_ < 0.f)) return none;
+        const float disc = b_ * b_ - a_ * c_;
+        if (!(disc >= 0.f)) return none;
+        const float t = c_ / (sqrtf(disc) - b_);   // the root without cancellation
+        const float s_ = md + t * nd;
+        if (!(0.f <= s_ && s_ <= ee)) return none;
+        if (POINT) pt = add(A, mul(E, s_ / ee));
+        return t;
+    }
+    const f3 V = k == 4 ? a : k == 5 ? v1 : add(a, e2);
+    const f3 m = sub(c, V);
+    const float b = dot(m, d), cc = dot(m, m) - r * r;
+    if (!(cc > 0.f && b < 0.f)) return none;
+    const float disc = b * b - dd * cc;
+    if (!(disc >= 0.f)) return none;
+    if (POINT) pt = V;
+    return cc / (sqrtf(disc) - b);
+}
+// (T) of the pair: the feature (0: no t) and the t
+__device__ __forceinline__ uint32_t sweep_pair(f3 c, f3 d, float r, float tmax, f3 a, f3 e1, f3 e2, f3 lo, f3 hi,
+                                               float& t) {
+    float u, v;
+    f3 q;
+    t = 0.f;
+    if (triangle_dist2(c, a, e1, e2, lo, hi, u, v, q) <= r * r) return 1u;   // the start overlap
+    const float dd = dot(d, d);
+    uint32_t feature = 0;
+#pragma unroll 1
+    for (int k = 0; k < 7; k++) {
+        const float tc = sweep_candidate<false>(k, c, d, dd, r, a, e1, e2, q);
+        if (0.f <= tc && tc <= tmax && (feature == 0 || tc < t)) {   // the first smallest
+            t = tc;
+            feature = 2u + (uint32_t)k;
+        }
+    }
+    return feature;
+}
+template <bool ANY, bool COUNT, bool NB>
+__global__ __launch_bounds__(BLOCK, SWEEP_WAVES) void k_sweep(SweepArgs a) {
+    const uint32_t n = a.n, T = a.T;
+    const uint32_t lane = lane_id();
+    const int limit = a.stack_limit;
+    const float4* __restrict__ leaf = a.leaf;
+    const RecordTree rec{a.inner};
+    const NodeBoxTree nbt{a.topo, a.nbox, leaf};
+    Counts c = {0, 0, 0, 0, 0};
+    uint32_t nsweeps = 0, nhits = 0;
+    bool has = false;
+    uint32_t r = 0;
+    Walk w{0u, INVALID, 0, false, 0.f, 0u, 0u};   // (bl: the best member's sorted leaf index; hit, best unused)
+    uint64_t key = 0;
+    uint32_t feature = 0;   // the best member's, and its genuine t
+    float bt = 0.f;
+    float tmax = 0.f, rad = 0.f;
+    f3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
+    __shared__ uint32_t s_stk[SB][BLOCK];
+    uint32_t stack[STACK_SIZE - SB];   // entries [SB, STACK_SIZE)
+    BlockStack st{&s_stk[0][threadIdx.x], stack};
+    const float4 none0 = make_float4(-1.f, 0.f, 0.f, 0.f), none1 = make_float4(__uint_as_float(INVALID), 0.f, 0.f, 0.f);
+    Refill rf;
+    while (true) {
+        refill_claim(rf, a.next, n, has, [&](uint32_t p) {   // this lane takes the p-th sweep of the walk order
+            r = a.perm ? a.perm[p] : p;
+            const float4 q0 = a.sweeps[2 * (size_t)r], q1 = a.sweeps[2 * (size_t)r + 1];
+            o = mk(q0.x, q0.y, q0.z);
+            tmax = q0.w + 0.f;   // (-0 -> +0: the key's bits order as the floats)
+            d = mk(q1.x, q1.y, q1.z);
+            rad = q1.w + 0.f;
+            inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+            if (COUNT) nsweeps++;
+            const bool finite = fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY &&
+                                fabsf(d.x) < INFINITY && fabsf(d.y) < INFINITY && fabsf(d.z) < INFINITY;
+            const bool zero = d.x == 0.f && d.y == 0.f && d.z == 0.f;
+            if (!finite || zero || !(rad >= 0.f) || !(rad < INFINITY) || !(tmax >= 0.f)) {   // no walk: a miss
+                a.hits[2 * (size_t)r] = none0;
+                a.hits[2 * (size_t)r + 1] = none1;
+            } else {
+                has = true;
+                w = walk_start(NB ? nbt.root(T) : rec.root(T), T);
+                key = (uint64_t)__float_as_uint(tmax) << 32 | 0xFFFFFFFFull;
+                feature = 0;
+                bt = 0.f;
+            }
+        });
+        if (__ballot(has) == 0 && rf.drained) break;
+        if (!has) continue;
+        bool done = false;
+        const bool isleaf = (w.node & LEAF_BIT) != 0;
+        // one fetch for every active lane, leaf or node, before the branch (k_nearest)
+        v4f q0, q1, q2, q3;
+        uint32_t cl = 0, cr = 0;
+        if (!NB || isleaf) {
+            const v4f* rr = isleaf ? reinterpret_cast<const v4f*>(leaf + 4 * (size_t)(w.node & ~LEAF_BIT))
+                                   : reinterpret_cast<const v4f*>(a.inner + w.node);
+            q0 = rr[0]; q1 = rr[1]; q2 = rr[2]; q3 = rr[3];
+            pin(q0); pin(q1); pin(q2); pin(q3);
+            if (!NB && !isleaf) {
+                const uint32_t own = __float_as_uint(q3.z);
+                cl = child_slot(__float_as_uint(q3.x), own, 0);
+                cr = child_slot(__float_as_uint(q3.y), own, 1);
+            }
+        } else {
+            const ChildPair ch = nbt.children(w.node);
+            cl = ch.cl;
+            cr = ch.cr;
+            q0 = v4f{ch.llo.x, ch.llo.y, ch.lhi.x, ch.lhi.y};   // the record's layout
+            q1 = v4f{ch.rlo.x, ch.rlo.y, ch.rhi.x, ch.rhi.y};
+            q2 = v4f{ch.lz0, ch.lz1, ch.rz0, ch.rz1};
+            q3 = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+        const float bound = key_t(key);   // t_max until a member is found (ANY: to the end)
+        const f2v rr2 = {rad, rad};
+        if (--w.guard == 0) {
+            c.overflow++;
+            done = true;
+        } else if (isleaf) {
+            if (COUNT) c.leaf++;
+            float mn;   // the leaf's own grown box first, with the current bound (words 10..15 of the record)
+            if (query_box<true>(o, inv, f2v{q2.z, q2.w} - rr2, f2v{q3.y, q3.z} + rr2, q3.x - rad, q3.w + rad, false, 0.f,
+                                bound, mn)) {
+                float t;
+                const uint32_t f = sweep_pair(o, d, rad, tmax, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y),
+                                              mk(q1.z, q1.w, q2.x), mk(q2.z, q2.w, q3.x), mk(q3.y, q3.z, q3.w), t);
+                const uint64_t cand = (uint64_t)__float_as_uint(fmaxf(t, mn) + 0.f) << 32 |
+                                      (__float_as_uint(q2.y) & ~LEAF_BIT);
+                if (f != 0 && cand < key) {
+                    key = cand;
+                    w.bl = w.node & ~LEAF_BIT;
+                    feature = f;
+                    bt = t;
+                    if (ANY) done = true;
+                }
+            }
+            walk_pop(w, st);
+            done = done || w.sp == -1;
+        } else {
+            if (COUNT) c.internal++;
+            // A child's box: the slab test without the axes whose 1 / d is infinite (a NaN there drops the axis out of
+            // mn and mx).  On such an axis 0 * inf = NaN drops a face at exactly o_k, so a flat leaf box there passes
+            // (B) while a box around it with its other face elsewhere gives [+-inf, +-inf] and fails: the one case
+            // where the slab test is not monotone in the box -- and here, unlike a ray, a sphere does
+            // touch such a triangle, through its edges.  Without the axis the test is monotone again, enters every
+            // box the full test enters, and its mn is never above the full one's.
+            // A direction below 2^-128 on all three axes leaves no axis: every child is entered.
+            const float qnan = __uint_as_float(0x7FC00000u);
+            const bool ix = fabsf(inv.x) == INFINITY, iy = fabsf(inv.y) == INFINITY, iz = fabsf(inv.z) == INFINITY;
+            const f3 invn = mk(ix ? qnan : inv.x, iy ? qnan : inv.y, iz ? qnan : inv.z);
+            const bool all = ix && iy && iz;
+            float ml, mr;
+            const bool lh = query_box<true>(o, invn, q0.xy - rr2, q0.zw + rr2, q2.x - rad, q2.y + rad, false, 0.f, bound, ml) || all;
+            const bool rh = query_box<true>(o, invn, q1.xy - rr2, q1.zw + rr2, q2.z - rad, q2.w + rad, false, 0.f, bound, mr) || all;
+            if (!lh && !rh) {
+                walk_pop(w, st);
+            } else if (lh && rh && w.sp + 1 >= limit) {   // the stack limit: both children lost, counted
+                c.overflow++;
+                walk_pop(w, st);
+            } else {
+                const bool swap = lh && rh && mr < ml;   // the nearer child first, left on a tie
+                if (lh && rh) {
+                    st.store(w.sp, w.top);   // push the other
+                    w.sp++;
+                    w.top = swap ? cl : cr;
+                }
+                w.node = swap ? cr : (lh ? cl : cr);
+            }
+            done = w.sp == -1;
+        }
+        if (done) {
+            float4 o0 = none0, o1 = none1;
+            if (feature != 0) {   // the winner's point, recomputed from its leaf record
+                const float4* lr = leaf + 4 * (size_t)w.bl;
+                const float4 la = lr[0], lb = lr[1], lc = lr[2], ld = lr[3];
+                const f3 ta = mk(la.x, la.y, la.z), te1 = mk(la.w, lb.x, lb.y), te2 = mk(lb.z, lb.w, lc.x);
+                const f3 lo = mk(lc.z, lc.w, ld.x), hi = mk(ld.y, ld.z, ld.w);
+                f3 pt = mk(0.f, 0.f, 0.f);
+                if (feature == 1u) {
+                    float u, v;
+                    triangle_dist2(o, ta, te1, te2, lo, hi, u, v, pt);
+                } else {
+                    sweep_candidate<true>((int)feature - 2, o, d, dot(d, d), rad, ta, te1, te2, pt);
+                }
+                pt = clamp_box(lo, hi, pt);
+                o0 = make_float4(bt, pt.x, pt.y, pt.z);
+                o1 = make_float4(__uint_as_float((uint32_t)key), __uint_as_float(feature), 0.f, 0.f);
+            }
+            a.hits[2 * (size_t)r] = o0;
+            a.hits[2 * (size_t)r + 1] = o1;
+            has = false;
+            if (COUNT) nhits += feature != 0;
+        }
+    }
+    if (COUNT || __ballot(c.overflow != 0)) {
+        unsigned long long v[5] = {nsweeps, nhits, c.internal, c.leaf, c.overflow};
+        wave_sum(v);
+        if (lane == 0) {
+            if (COUNT)
+                for (int k = 0; k < 4; k++) atomicAdd(&a.counts[k], v[k]);
+            if (v[4]) atomicAdd(a.overflow, v[4]);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_sweep(const SweepArgs& a, bool any, bool count, hipStream_t s) {
+    if (a.n == 0) return;
+    // the persistent grid of the kernel's occupancy, or a workgroup per 256 sweeps when that is fewer
+    const uint32_t need = (a.n + BLOCK - 1) / BLOCK, blocks = need < 256 * SWEEP_WAVES ? need : 256 * SWEEP_WAVES;
+    with_bools([&](auto ANY, auto COUNT, auto NB) {
+        hipLaunchKernelGGL((k_sweep<ANY, COUNT, NB>), dim3(blocks), dim3(BLOCK), 0, s, a);
+    }, any, count, a.nb);
+}
 
 void launch_clearance(const ClearanceArgs& a, bool count, hipStream_t s) {
     if (a.n == 0) return;

@@ -75,6 +75,64 @@ def check_query_rays(rays, device=None):
     return "numpy", rays.view(_L.RAY_DTYPE).reshape(-1)
 
 
+def make_sweeps(origins, directions, radius, t_max=float("inf")):
+    """Packs (N, 3) origins and directions, a radius and a t_max (each one value, or N of them) as sphere sweeps:
+    torch tensors give an (N, 8) float32 tensor on their device, anything else a SWEEP_DTYPE array (include/rtbvh.h
+    rtbvh_sweep).  The sweeps live in the space the BVH was built in, the radius too; directions need not be unit."""
+    if _is_tensor(origins) or _is_tensor(directions):
+        import torch
+        dev = origins.device if _is_tensor(origins) else directions.device
+        o = torch.as_tensor(origins, dtype=torch.float32, device=dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=dev).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"make_sweeps: {tuple(o.shape)} origins and {tuple(d.shape)} directions")
+        sweeps = torch.empty((o.shape[0], 8), dtype=torch.float32, device=dev)
+        sweeps[:, 0:3] = o
+        sweeps[:, 3] = torch.as_tensor(t_max, dtype=torch.float32, device=dev)
+        sweeps[:, 4:7] = d
+        sweeps[:, 7] = torch.as_tensor(radius, dtype=torch.float32, device=dev)
+        return sweeps
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f"make_sweeps: {o.shape} origins and {d.shape} directions")
+    sweeps = np.zeros(len(o), _L.SWEEP_DTYPE)
+    sweeps["origin"] = o
+    sweeps["t_max"] = np.asarray(t_max, np.float32)
+    sweeps["direction"] = d
+    sweeps["radius"] = np.asarray(radius, np.float32)
+    return sweeps
+
+
+def check_sweeps(sweeps, device=None):
+    """Context.sweep's input check: ("torch", sweeps) for an (N, 8) float32 contiguous CUDA tensor (on `device` when
+    given), ("numpy", SWEEP_DTYPE view) for a C-contiguous SWEEP_DTYPE array or (N, 8) float32 array; ValueError for
+    anything else.  Calls nothing in the library."""
+    if _is_tensor(sweeps):
+        import torch
+        if sweeps.dtype != torch.float32 or sweeps.dim() != 2 or sweeps.shape[1] != 8:
+            raise ValueError(f"sweep: sweeps must be an (N, 8) float32 tensor (make_sweeps), got "
+                             f"{tuple(sweeps.shape)} {sweeps.dtype}")
+        if not sweeps.is_cuda:
+            raise ValueError("sweep: a torch tensor of sweeps must be on the context's GPU (numpy arrays take the "
+                             "host path)")
+        if device is not None and sweeps.device.index != device:
+            raise ValueError(f"sweep: sweeps on {sweeps.device}, the context on device {device}")
+        if not sweeps.is_contiguous():
+            raise ValueError("sweep: sweeps must be contiguous")
+        return "torch", sweeps
+    if not isinstance(sweeps, np.ndarray):
+        raise ValueError("sweep: sweeps must be a torch CUDA tensor or a numpy array")
+    if sweeps.dtype == _L.SWEEP_DTYPE:
+        if sweeps.ndim != 1:
+            raise ValueError(f"sweep: a SWEEP_DTYPE array must be one-dimensional, got shape {sweeps.shape}")
+    elif sweeps.dtype != np.float32 or sweeps.ndim != 2 or sweeps.shape[1] != 8:
+        raise ValueError(f"sweep: sweeps must be SWEEP_DTYPE or (N, 8) float32, got {sweeps.shape} {sweeps.dtype}")
+    if not sweeps.flags["C_CONTIGUOUS"]:
+        raise ValueError("sweep: sweeps must be C-contiguous")
+    return "numpy", sweeps.view(_L.SWEEP_DTYPE).reshape(-1)
+
+
 def make_points(points, max_dist2=float("inf")):
     """Packs (N, 3) points (and one max_dist2, or N of them) as closest-point queries: a torch tensor gives an
     (N, 4) float32 tensor on its device, anything else a POINT_DTYPE array (include/rtbvh.h rtbvh_point).  The
@@ -1099,6 +1157,38 @@ class Context:
         """rtbvh_clearance_counts: queries, results found, internal-node and leaf steps of the last CLEARANCE_COUNT
         query (the other queries' counts are kept apart)."""
         return self._counts("clearance", ("queries", "found", "internal_steps", "leaf_steps"))
+
+    # -- sphere-sweep queries --
+    def sweep(self, sweeps, mode: int = 0, stream=None):
+        """rtbvh_sweep_async / rtbvh_sweep_host: for each sphere sweep (make_sweeps: a sphere of a radius moving from
+        an origin along a direction, up to t_max) its first contact with the mesh -- t, the contact point on the
+        triangle, the triangle and the feature touched (1 overlapping at the start, 2 the face, 3..5 an edge, 6..8 a
+        vertex) -- in the space the BVH was built in (include/rtbvh.h).
+
+        An (N, 8) float32 contiguous CUDA tensor on the context's device goes to the device entry with no host copy
+        and no synchronisation, enqueued on `stream` (a torch stream or a hipStream_t handle; default: the current
+        torch stream; torch's legacy default stream as in query), and returns an (N, 8) float32 device tensor
+        {t, point, tri, feature, 0, 0}: read the ids with out[:, 4].view(torch.int32) (a miss: t = -1, tri = -1,
+        feature = 0).  A SWEEP_DTYPE or (N, 8) float32 numpy array goes through the synchronous host entry and
+        returns a SWEEP_HIT_DTYPE array.  mode: SWEEP_ANY, SWEEP_SORT, SWEEP_COUNT.  ValueError for a wrong shape,
+        dtype, device or layout."""
+        kind, sw = check_sweeps(sweeps, getattr(self, "device", None))
+        n = len(sw)
+        if kind == "numpy":
+            out = np.zeros(n, _L.SWEEP_HIT_DTYPE)
+            self._check(_L.lib().rtbvh_sweep_host(self._h, ctypes.c_void_p(sw.ctypes.data), n,
+                                                  ctypes.c_void_p(out.ctypes.data), mode))
+            return out
+        import torch
+        out = torch.empty((n, 8), dtype=torch.float32, device=sw.device)
+        self._async(_L.lib().rtbvh_sweep_async, stream, sw.device, ctypes.c_void_p(sw.data_ptr()), n,
+                    ctypes.c_void_p(out.data_ptr()), mode)
+        return out
+
+    def sweep_counts(self) -> dict:
+        """rtbvh_sweep_counts: sweeps, hits, internal-node and leaf steps of the last SWEEP_COUNT query (the other
+        queries' counts are kept apart)."""
+        return self._counts("sweep", ("sweeps", "hits", "internal_steps", "leaf_steps"))
 
     # -- signed-distance queries --
     def signed(self, points, max_dist2=None, mode: int = 0, out=None, stream=None):
